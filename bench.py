@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the rasterizer hot path: fwd+bwd Gaussians/s (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -50,6 +50,12 @@ WORKLOADS = {
     # c5's culled variant: orbit radius 1.2 around the unit ball, the frustum cull removes ~2/3
     "c5culled": dict(scene="B", n=10_000_000, w=3840, h=2160, sh=3, radius=1.2),
 }
+
+
+# --dump-outputs: arrays larger than these are written as a fixed, seeded sample of their rows (a 1080p image is whole)
+DUMP_POINT_ROWS = 1 << 17
+DUMP_PIXELS = 1 << 21
+DUMP_MAX_BYTES = 64 << 20
 
 
 def yaw(T: torch.Tensor, deg: float) -> torch.Tensor:
@@ -173,6 +179,38 @@ def cpu_baseline(g, cam, cfg, budget_s: float = 25.0, chunk_tiles: int = 1024):
                       f"full pass {est:.1f}s"))
 
 
+def _seeded_rows(n: int, k: int):
+  """The same ``k`` of ``n`` row indices (ascending) on every run, or None when all ``n`` rows fit."""
+  if n <= k:
+    return None
+  return torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+
+
+def dump_outputs(path: str, image, loss, grads: dict, visible, point_state) -> dict:
+  """Writes what the timed step hands its caller -- the rendered image, the loss, the parameter gradients, the
+  ``visible`` accumulator and the controller's point statistics -- as ``path/<name>.npy`` (float32); per-point arrays
+  and the image are sampled by ``_seeded_rows`` when larger than DUMP_POINT_ROWS / DUMP_PIXELS.  Returns name -> shape."""
+  import numpy as np
+  H, W = image.shape[:2]
+  pix = _seeded_rows(H * W, DUMP_PIXELS)
+  rows = _seeded_rows(visible.shape[0], DUMP_POINT_ROWS)
+  arrays = {"image": image if pix is None else image.reshape(H * W, -1)[pix.to(image.device)], "loss": loss.reshape(1)}
+  per_point = {f"d_{k}": v for k, v in grads.items()}
+  per_point["visible"] = visible
+  per_point.update({f"point_state_{f}": getattr(point_state, f)
+                    for f in ("prune_cost", "split_score", "max_scale_px", "points_in_view", "visibility")})
+  for k, v in per_point.items():
+    arrays[k] = v if rows is None else v[rows.to(v.device)]
+  arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}     # points_in_view: int16 -> float32
+  total = sum(a.nbytes for a in arrays.values())
+  if total > DUMP_MAX_BYTES:
+    raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+  os.makedirs(path, exist_ok=True)
+  for k, a in arrays.items():
+    np.save(os.path.join(path, f"{k}.npy"), a)
+  return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def measure_scale_workload(name: str, dev, steps: int = 10, warm: int = 12):
   """One-GPU, one-camera step of the workload the multi-GPU runs use (c3): the baseline a scaling curve over
   ``bench.py --gpus N`` needs (those runs render camera k of the same scene on GPU k; per-GPU work is this step)."""
@@ -248,10 +286,16 @@ def main():
                        "largest relative difference of the summed gradients (rehearsal aid; not timed)")
   ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                   help="nccl = RCCL over xGMI (default); gloo only for rehearsing the multi-rank path on one GPU")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write what the last one computed on rank 0 (image, loss, gradients, "
+                       "visible accumulator, point statistics) as DIR/<name>.npy, float32; a seeded sample of the rows of "
+                       "larger arrays, at most 64 MB in all")
   args = ap.parse_args()
 
   if args.gpus < 1:
     raise SystemExit("--gpus must be >= 1")
+  if args.steps < 1 or args.warmup < 0:
+    raise SystemExit("--steps must be >= 1 and --warmup >= 0")
   if args.workload is None:
     args.workload = "c2" if args.gpus == 1 else "c3"
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -333,7 +377,7 @@ def main():
       else:
         loss = sta.clamped_mse_loss(r.image, target_image)      # = F.mse_loss(image.clamp(0, 1), target), trainer.py:472-475
       loss.backward()
-    last["r"] = r
+    last["r"], last["loss"] = r, loss
     return r
 
   def step():
@@ -379,6 +423,9 @@ def main():
   per_step_ms = sorted(step_trace)
   median_ms = per_step_ms[len(per_step_ms) // 2] if len(per_step_ms) % 2 else \
       0.5 * (per_step_ms[len(per_step_ms) // 2 - 1] + per_step_ms[len(per_step_ms) // 2])
+  dumped = None
+  if args.dump_outputs and rank == 0:      # before anything below renders again
+    dumped = dump_outputs(args.dump_outputs, last["r"].image, last["loss"], dp.grads, dp.visible, point_state)
   if world > 1:
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -505,6 +552,8 @@ def main():
                              "profiles/r04_parity_observed.txt"},
         "roofline": k7,
     }
+    if dumped is not None:
+      out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if check is not None:
       out["config"]["collective_check_rel_err"] = check
       out["config"]["statistics_check_bit_identical"] = stats_check
