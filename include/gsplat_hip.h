@@ -44,6 +44,10 @@ extern "C" {
                                   (m* = moments of G dL/dG about the splat's mean, m0 the zeroth; the per-splat sweep turns
                                   their sums into du = A mx + B my, dv = B mx + C my, dA = -mxx/2, dB = -mxy, dC = -myy/2,
                                   dopacity = m0 / opacity) */
+#define GSR_MAX_FEATURES 16     /* feature channels of the three-call form: C in 1..GSR_MAX_FEATURES */
+#define GSR_WIDE_MIN_FEATURES 4 /* C >= 4 takes the wide path: features in a second table feat_rows [M, CW], CW = 4, 8 or 16
+                                   (the smallest that holds C; zero-padded), geometry rows with zero colour slots, and
+                                   per-pair partials of 8 + CW floats:  mx my mxx mxy | myy m0 prune split | df0 .. df(CW-1) */
 
 #ifndef GSR_HAVE_RASTER_PARAMS
 #define GSR_HAVE_RASTER_PARAMS
@@ -84,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 30) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 31) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -218,6 +222,11 @@ int gsr_depth_keys(const float* depth, int64_t M, uint32_t bias, uint32_t max_ke
  * the same rows straight from gsr_project_sh_forward. */
 int gsr_pack_rows(const float* gaussians2d, const float* depth, const float* features, int64_t M, int32_t C,
                   const GsrRasterParamsC* params_host, float* rows_out, float* screen_scale_out, void* stream);
+/* The same for GSR_WIDE_MIN_FEATURES <= C <= GSR_MAX_FEATURES, in one launch: rows_out [M,16] with zero colour slots and
+ * feat_rows_out [M,CW] (CW = 4, 8 or 16, see GSR_WIDE_MIN_FEATURES; columns C..CW-1 zero). */
+int gsr_pack_rows_wide(const float* gaussians2d, const float* depth, const float* features, int64_t M, int32_t C,
+                       const GsrRasterParamsC* params_host, float* rows_out, float* feat_rows_out, float* screen_scale_out,
+                       void* stream);
 /* For rank k in depth order (order[k] = splat id): gathers the splat's row -- the one crossing of the depth-order
  * permutation on the forward side, one 64-byte line per splat -- and writes the number of tiles its support touches (a
  * tile counts when the support reaches the pixel centres of its upper or lower half) and tile_hits_out [M,4] uint32:
@@ -292,6 +301,15 @@ int gsr_composite_forward(const float* rows /* [M,16] */, const uint32_t* sorted
                                                    to THREE WORDS PAST the O-th entry (values unused): the buffer must be
                                                    readable that far (gsr_frame_plan sizes it so) */,
                           void* stream);
+/* Wide frames (GSR_WIDE_MIN_FEATURES <= C <= GSR_MAX_FEATURES): the features come from feat_rows [M,CW]
+ * (gsr_pack_rows_wide), every tile is composited by one wave (no segments); image [H,W,C], the other outputs as
+ * gsr_composite_forward.  Channels, final_T, last, median and the visibility partials are bit-identical to
+ * gsr_composite_forward without segments for the same splats. */
+int gsr_composite_forward_wide(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
+                               const uint32_t* sorted_splat, const uint32_t* sorted_inst, const uint32_t* tile_range,
+                               int32_t W, int32_t H, int32_t C, const GsrRasterParamsC* params_host, float* image_out,
+                               float* final_T_out, int32_t* last_out, float* median_depth_out, float* vis_partial_out,
+                               float* pair_vis_out, void* stream);
 #ifndef GSR_PREFETCH_MIN_ROWS
 #define GSR_PREFETCH_MIN_ROWS 1000000
 #endif
@@ -304,6 +322,12 @@ int gsr_composite_backward(const float* rows /* [M,16] */, const uint32_t* sorte
                            const float* dL_dimage, const float* image /* the forward output; needed with segments */,
                            float* partial_out, const GsrSegmentsC* segments_host /* the forward pass's, or NULL */,
                            void* stream);
+/* Wide frames: partial_out [O, 8 + CW] (see GSR_WIDE_MIN_FEATURES), written only for pairs with pair_vis > 0. */
+int gsr_composite_backward_wide(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
+                                const uint32_t* sorted_splat, const uint32_t* sorted_inst, const float* pair_vis,
+                                const uint32_t* tile_range, int32_t W, int32_t H, int32_t C,
+                                const GsrRasterParamsC* params_host, const float* final_T, const int32_t* last,
+                                const float* dL_dimage, float* partial_out, void* stream);
 
 /* ---- deterministic per-splat reductions of the per-(tile,splat) partials -------------------------------- */
 /* visibility_out [M] indexed by splat (not rank).  capacity = slots vis_partial holds (the pair count, or the bound
@@ -317,8 +341,14 @@ int gsr_reduce_visibility(const float* vis_partial, const uint32_t* offsets, con
  * the conic of the forward row).  The visibility column holds the same bits gsr_reduce_visibility returns. */
 int gsr_reduce_gradients(const float* partial, const float* vis_partial, const uint32_t* offsets,
                          const uint32_t* count, const uint32_t* order, int64_t M, float* grad_rows_out, void* stream);
+/* The same for the [O, 8 + CW] partials of gsr_composite_backward_wide, summed in the same order: grad_rows_out [M,16]
+ * as above with df0..df2 = 0, and d_features_out [M,C] written directly (indexed by splat). */
+int gsr_reduce_gradients_wide(const float* partial, const float* vis_partial, const uint32_t* offsets,
+                              const uint32_t* count, const uint32_t* order, int64_t M, int32_t C, float* grad_rows_out,
+                              float* d_features_out, void* stream);
 /* The rows taken apart for the three-call form: d_gaussians2d [M,6], d_features [M,C]; prune_cost / split_score /
- * visibility [M] (each may be NULL). */
+ * visibility [M] (each may be NULL).  d_features may be NULL (any C up to GSR_MAX_FEATURES): the feature gradient of a
+ * wide frame comes from gsr_reduce_gradients_wide. */
 int gsr_unpack_grad_rows(const float* rows /* the forward rows [M,16] */, const float* grad_rows, int64_t M, int32_t C,
                          float* d_gaussians2d, float* d_features, float* prune_cost_out, float* split_score_out,
                          float* visibility_out, void* stream);
@@ -356,7 +386,7 @@ typedef struct GsrFrameC {
   const float* gaussians2d;     /* [N,6] */
   const float* depth;           /* [N]   */
   const float* features;        /* [N,C] */
-  int32_t C;                    /* 1..3 (3 in the one-call form) */
+  int32_t C;                    /* 1..3, or up to GSR_MAX_FEATURES with feature_table (3 in the one-call form) */
   const uint32_t* depth_order;  /* [N] or NULL: the depth order when the caller has it already (skips the depth sort) */
   /* One-call form only, all three or none: a second stream on which the depth sort (keys from the positions) runs
    * while the projection / colour sweep occupies `stream`; event_fork is recorded on `stream` behind the cull,
@@ -364,6 +394,9 @@ typedef struct GsrFrameC {
   void* side_stream;
   void* event_fork;
   void* event_join;
+  /* Projected mode: 1 = the caller takes C >= GSR_WIDE_MIN_FEATURES through the wide path (the plan lays out the
+   * feature table feat_rows, K6 wide composites every tile with one wave: seg_pairs is ignored); 0 = C <= 3 only. */
+  int32_t feature_table;
 } GsrFrameC;
 /* Byte offsets of the frame's buffers inside the two caller-owned arenas (-1: not present in this frame).  `out`:
  * everything the Rendering or the backward pass still needs after the forward pass; the first zero_bytes bytes are
@@ -379,6 +412,7 @@ typedef struct GsrFramePlanC {
   /* work arena */
   int64_t cull_ws, sort_ws, scan_ws, tsort_ws, keys_a, keys_b, tile_hits, tkeys_a, tkeys_b;
   int64_t cull_ws_bytes, sort_ws_bytes, scan_ws_bytes, tsort_ws_bytes;
+  int64_t feat_rows;            /* out arena: [N,CW] feature table of a wide frame, -1 otherwise */
 } GsrFramePlanC;
 /* Where the ping-pong sorts left their results (byte offsets into `out`) and the segment tables of the frame. */
 typedef struct GsrFrameResultC {

@@ -14,8 +14,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GSPLAT_HIP_LIB: load another build of the same library (kernel experiments, tools/k67_bench.py); never a fallback
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
+MAX_FEATURES = 16                  # GSR_MAX_FEATURES
+WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
 
 
 class GsrRasterParamsC(C.Structure):
@@ -39,7 +41,8 @@ class GsrFrameC(C.Structure):
               ("compute_visibility", C.c_int32), ("needs_grad", C.c_int32), ("seg_pairs", C.c_int32),
               ("seg_min_pairs", C.c_int32), ("pair_capacity", C.c_int64), ("gaussians2d", C.c_void_p),
               ("depth", C.c_void_p), ("features", C.c_void_p), ("C", C.c_int32), ("depth_order", C.c_void_p),
-              ("side_stream", C.c_void_p), ("event_fork", C.c_void_p), ("event_join", C.c_void_p)]
+              ("side_stream", C.c_void_p), ("event_fork", C.c_void_p), ("event_join", C.c_void_p),
+              ("feature_table", C.c_int32)]
 
 
 FRAME_PLAN_FIELDS = ("out_bytes", "work_bytes", "zero_begin", "zero_bytes", "prune_cost", "split_score", "counts",
@@ -47,7 +50,7 @@ FRAME_PLAN_FIELDS = ("out_bytes", "work_bytes", "zero_begin", "zero_bytes", "pru
                      "final_T", "last", "median", "count", "offsets", "vals_a", "vals_b", "tvals_a", "tvals_b", "trank_a",
                      "trank_b", "pair_vis", "seg_tables", "seg_pix", "seg_last", "seg_capacity", "seg_heavy_capacity",
                      "cull_ws", "sort_ws", "scan_ws", "tsort_ws", "keys_a", "keys_b", "tile_hits", "tkeys_a", "tkeys_b",
-                     "cull_ws_bytes", "sort_ws_bytes", "scan_ws_bytes", "tsort_ws_bytes")
+                     "cull_ws_bytes", "sort_ws_bytes", "scan_ws_bytes", "tsort_ws_bytes", "feat_rows")
 
 
 class GsrFramePlanC(C.Structure):
@@ -122,6 +125,7 @@ PROTOTYPES = {
     "gsr_project_backward_rows": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _p,
                                             _p, _p, _i32, _p, _p, _p, _p, _p]),
     "gsr_pack_rows": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p]),
+    "gsr_pack_rows_wide": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p, _p]),
     "gsr_tile_count": (C.c_int, [_p, _p, _i64, _i32, _i32, _pp, _p, _p, _p, _p]),
     "gsr_tile_count_offsets_workspace_bytes": (_sz, [_i64]),
     "gsr_tile_count_offsets": (C.c_int, [_p, _p, _i64, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
@@ -133,6 +137,8 @@ PROTOTYPES = {
     "gsr_segment_plan": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "gsr_composite_forward": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _ps, _i32, _p]),
     "gsr_composite_backward": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _ps, _p]),
+    "gsr_composite_forward_wide": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _p]),
+    "gsr_composite_backward_wide": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p]),
     "gsr_opt_point_weights": (C.c_int, [_p, _p, _i64, _p, _p, _f, _f, _f, _f, _i32, _p, _p]),
     "gsr_opt_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _f, _f, _f, _f, _f, _p]),
     "gsr_pixel_loss_workspace_bytes": (_sz, [_i64]),
@@ -165,6 +171,7 @@ PROTOTYPES = {
                                     _p, _p, _p, _p]),
     "gsr_reduce_visibility": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p]),
     "gsr_reduce_gradients": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p]),
+    "gsr_reduce_gradients_wide": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
     "gsr_unpack_grad_rows": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
 }
 

@@ -416,6 +416,80 @@ __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* __restric
   g[3] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// reduce_grad_kernel for the [O, 8 + CW] partials of a wide frame (composite_wide.inc): the same slots summed in the same
+// association (serial in id order up to GSR_REDUCE_SERIAL slots, 64-slot groups by the wave tree beyond), straight from
+// global memory, one thread per rank.  Writes the packed gradient row with df0..df2 = 0 and the feature gradient [M, C].
+template <int CW>
+__global__ __launch_bounds__(256) void reduce_grad_wide_kernel(const float* __restrict__ partial,
+                                                               const float* __restrict__ vis_partial,
+                                                               const uint32_t* __restrict__ offsets,
+                                                               const uint32_t* __restrict__ count,
+                                                               const uint32_t* __restrict__ order, int64_t M, int C,
+                                                               float* __restrict__ grows, float* __restrict__ dfeat) {
+  constexpr int NV = 8 + CW;
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool have = k < M;
+  const uint32_t b = have ? offsets[k] : 0u, n = have ? count[k] : 0u;
+  const bool serial = n <= GSR_REDUCE_SERIAL;
+  float a[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) a[v] = 0.f;
+  float vsum = 0.f;
+  if (serial) {
+    for (uint32_t j = b; j < b + n; ++j) {
+      const float pv = vis_partial[j];
+      vsum += pv;
+      if (pv > 0.f) {                                          // slots never written by the backward pass hold garbage
+        const float* p = partial + (size_t)NV * j;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) a[v] += p[v];
+      }
+    }
+  }
+  const int lane = gsr_lane();
+  uint64_t todo = __ballot(!serial);
+  while (todo) {
+    const int l = __builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const uint32_t bl = (uint32_t)__builtin_amdgcn_readlane((int)b, l), nl = (uint32_t)__builtin_amdgcn_readlane((int)n, l);
+    float t[NV + 1];                                           // (only lane 63's copies are meaningful)
+#pragma unroll
+    for (int v = 0; v <= NV; ++v) t[v] = 0.f;
+    for (uint32_t g = 0; g < nl; g += 64u) {
+      const uint32_t j = g + (uint32_t)lane;
+      const float pv = j < nl ? vis_partial[bl + j] : 0.f;
+      float pr[NV];
+#pragma unroll
+      for (int v = 0; v < NV; ++v) pr[v] = 0.f;
+      if (pv > 0.f) {
+        const float* p = partial + (size_t)NV * (bl + j);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) pr[v] = p[v];
+      }
+#pragma unroll
+      for (int v = 0; v < NV; ++v) t[v] += gsr_wave_sum_to_lane63(pr[v]);
+      t[NV] += gsr_wave_sum_to_lane63(pv);
+    }
+#pragma unroll
+    for (int v = 0; v <= NV; ++v) t[v] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t[v]), 63));
+    if (lane == l) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) a[v] = t[v];
+      vsum = t[NV];
+    }
+  }
+  if (!have) return;
+  const int64_t s = order ? (int64_t)order[k] : k;
+  float4* g = reinterpret_cast<float4*>(grows + GSR_ROW_FLOATS * s);
+  g[0] = make_float4(a[0], a[1], a[2], a[3]);
+  g[1] = make_float4(a[4], a[5], a[6], a[7]);
+  g[2] = make_float4(0.f, 0.f, 0.f, vsum);
+  g[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int c = 0; c < CW; ++c)
+    if (c < C) dfeat[(int64_t)C * s + c] = a[8 + c];
+}
+
 // The packed gradient rows taken apart again for the three-call form (autograd hands d_gaussians2d / d_features on to the
 // caller's own graph): one sequential sweep in splat order.
 template <int C>
@@ -440,6 +514,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const float* __restric
   if (prune) prune[m] = g1.z;
   if (split) split[m] = g1.w;
   if (vis) vis[m] = g2.w;
+  if (C == 0) return;                                        // (wide frames: the feature gradient is written elsewhere)
   dfeat[C * m] = g2.x;
   if (C > 1) dfeat[C * m + 1] = g2.y;
   if (C > 2) dfeat[C * m + 2] = g2.z;
@@ -568,16 +643,33 @@ int gsr_reduce_gradients(const float* partial, const float* vis_partial, const u
   return GSR_OK;
 }
 
+int gsr_reduce_gradients_wide(const float* partial, const float* vis_partial, const uint32_t* offsets,
+                              const uint32_t* count, const uint32_t* order, int64_t M, int32_t C, float* grad_rows_out,
+                              float* d_features_out, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
+  if (C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
+  if (M == 0) return GSR_OK;
+  if (!offsets || !count || !grad_rows_out || !d_features_out || !vis_partial) return GSR_ERR_INVALID_ARGUMENT;
+  const unsigned g = grid_for(M, 256);
+  if (C <= 4) reduce_grad_wide_kernel<4><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
+  else if (C <= 8) reduce_grad_wide_kernel<8><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
+  else reduce_grad_wide_kernel<16><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
+  GSR_CHECK_LAUNCH();
+  return GSR_OK;
+}
+
 int gsr_unpack_grad_rows(const float* rows, const float* grad_rows, int64_t M, int32_t C, float* d_gaussians2d,
                          float* d_features, float* prune_cost_out, float* split_score_out, float* visibility_out,
                          void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
-  if (C < 1 || C > 3) return GSR_ERR_UNSUPPORTED;
+  if (C < 1 || C > (d_features ? 3 : GSR_MAX_FEATURES)) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
-  if (!rows || !grad_rows || !d_gaussians2d || !d_features) return GSR_ERR_INVALID_ARGUMENT;
+  if (!rows || !grad_rows || !d_gaussians2d) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  if (C == 1) unpack_rows_kernel<1><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
+  if (!d_features) unpack_rows_kernel<0><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, nullptr, prune_cost_out, split_score_out, visibility_out);
+  else if (C == 1) unpack_rows_kernel<1><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
   else if (C == 2) unpack_rows_kernel<2><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
   else unpack_rows_kernel<3><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
   GSR_CHECK_LAUNCH();

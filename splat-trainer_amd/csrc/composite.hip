@@ -1036,6 +1036,8 @@ inline bool seg_ok(const GsrSegmentsC* sg, bool median) {
 
 }  // namespace
 
+#include "composite_wide.inc"      // K6 / K7 of frames with 4..16 feature channels
+
 extern "C" {
 
 #ifdef GSR_K6_TRACE

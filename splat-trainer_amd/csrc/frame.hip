@@ -58,7 +58,9 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
     return GSR_ERR_INVALID_ARGUMENT;
   const bool projected = f->position == nullptr;
   if (!projected && f->K != 1 && f->K != 4 && f->K != 9 && f->K != 16) return GSR_ERR_UNSUPPORTED;
-  if (f->C < 1 || f->C > 3 || (!projected && f->C != 3)) return GSR_ERR_UNSUPPORTED;
+  if (f->C < 1 || f->C > GSR_MAX_FEATURES || (!projected && f->C != 3)) return GSR_ERR_UNSUPPORTED;
+  const bool wide = f->C >= GSR_WIDE_MIN_FEATURES;         // features in their own table, unsegmented composite
+  if (wide && !f->feature_table) return GSR_ERR_UNSUPPORTED;
   if (f->params.tile_size != 16) return GSR_ERR_UNSUPPORTED;
   memset(p, 0, sizeof(*p));
   const int64_t N = f->N, cap = f->pair_capacity;
@@ -93,11 +95,12 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
   p->trank_a = out.take(4 * cap + 16);         // (+ 3 words: K6's large-frame walk fetches list words four at a time)
   p->trank_b = out.take(4 * cap + 16);
   p->pair_vis = vis_partial ? out.take(4 * cap) : -1;
+  p->feat_rows = wide ? out.take(4 * (f->C <= 4 ? 4 : f->C <= 8 ? 8 : 16) * N) : -1;
   // segment tables and pixel slots (forward checkpoints read by the backward pass)
   p->seg_capacity = 0;
   p->seg_heavy_capacity = 0;
   p->seg_tables = p->seg_pix = p->seg_last = -1;
-  if (f->seg_pairs != 0 && cap > 0) {
+  if (f->seg_pairs != 0 && cap > 0 && !wide) {
     const int64_t sc = gsr_segment_capacity(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T, f->needs_grad ? 1 : 0);
     if (sc > 0) {
       int64_t hc = gsr_segment_heavy_capacity(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T, f->needs_grad ? 1 : 0);
@@ -166,8 +169,12 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
   GSR_TRY(gsr_depth_key_range(f->near_plane, f->far_plane, &key_bias, &key_max));
   uint32_t* keys_a = at<uint32_t>(work, p->keys_a);
   if (projected) {
-    GSR_TRY(gsr_pack_rows(f->gaussians2d, f->depth, f->features, N, f->C, &f->params, rows,
-                          at<float>(out, p->screen_scale), stream_));
+    if (p->feat_rows >= 0)
+      GSR_TRY(gsr_pack_rows_wide(f->gaussians2d, f->depth, f->features, N, f->C, &f->params, rows,
+                                 at<float>(out, p->feat_rows), at<float>(out, p->screen_scale), stream_));
+    else
+      GSR_TRY(gsr_pack_rows(f->gaussians2d, f->depth, f->features, N, f->C, &f->params, rows,
+                            at<float>(out, p->screen_scale), stream_));
     if (!f->depth_order) GSR_TRY(gsr_depth_keys(f->depth, N, key_bias, key_max, keys_a, stream_));
   } else {
     int64_t* indexes = at<int64_t>(out, p->indexes);
@@ -271,10 +278,16 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
     }
     if (event_k6_begin && hipEventRecord(reinterpret_cast<hipEvent_t>(event_k6_begin), stream) != hipSuccess)
       return GSR_ERR_LAUNCH_FAILED;
-    GSR_TRY(gsr_composite_forward(rows, sorted_splat, sorted_inst, tile_range, f->W, f->H, f->C, &f->params, image,
-                                  at<float>(out, p->final_T), at<int32_t>(out, p->last), at<float>(out, p->median),
-                                  at<float>(out, p->vis_partial), at<float>(out, p->pair_vis), seg,
-                                  N >= GSR_PREFETCH_MIN_ROWS ? 1 : 0, stream_));
+    if (p->feat_rows >= 0)
+      GSR_TRY(gsr_composite_forward_wide(rows, at<float>(out, p->feat_rows), sorted_splat, sorted_inst, tile_range, f->W,
+                                         f->H, f->C, &f->params, image, at<float>(out, p->final_T),
+                                         at<int32_t>(out, p->last), at<float>(out, p->median),
+                                         at<float>(out, p->vis_partial), at<float>(out, p->pair_vis), stream_));
+    else
+      GSR_TRY(gsr_composite_forward(rows, sorted_splat, sorted_inst, tile_range, f->W, f->H, f->C, &f->params, image,
+                                    at<float>(out, p->final_T), at<int32_t>(out, p->last), at<float>(out, p->median),
+                                    at<float>(out, p->vis_partial), at<float>(out, p->pair_vis), seg,
+                                    N >= GSR_PREFETCH_MIN_ROWS ? 1 : 0, stream_));
     if (event_k6_end && hipEventRecord(reinterpret_cast<hipEvent_t>(event_k6_end), stream) != hipSuccess)
       return GSR_ERR_LAUNCH_FAILED;
     if (f->compute_visibility && !f->needs_grad)

@@ -423,6 +423,36 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict_
   *reinterpret_cast<float2*>(sscale + 2 * m) = gsr_screen_scale(ab.x, ab.y, co.x);
 }
 
+// Wide frames (C >= GSR_WIDE_MIN_FEATURES): the same geometry row with zero colour slots, and the features in their own
+// table [M, CW] (zero-padded past C), both written whole by one thread per splat.
+template <int CW>
+__global__ __launch_bounds__(256) void pack_rows_wide_kernel(const float* __restrict__ g2d, const float* __restrict__ depth,
+                                                             const float* __restrict__ feat, int64_t M, int C,
+                                                             GsrRasterParams rp, float* __restrict__ rows,
+                                                             float* __restrict__ feat_rows, float* __restrict__ sscale) {
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const float* g = g2d + 6 * m;
+  const float2 uv = *reinterpret_cast<const float2*>(g);
+  const float2 ab = *reinterpret_cast<const float2*>(g + 2);
+  const float2 co = *reinterpret_cast<const float2*>(g + 4);
+  float4* r = reinterpret_cast<float4*>(rows + (int64_t)GSR_ROW_FLOATS * m);
+  r[0] = make_float4(uv.x, uv.y, ab.x, ab.y);
+  r[1] = make_float4(co.x, co.y, gsr_qlim(co.y, rp), 0.f);
+  r[2] = make_float4(0.f, 0.f, depth[m], log2f(co.y));
+  const float2 bb = gsr_pixel_bbox(uv.x, uv.y, ab.x, ab.y, co.x, co.y, rp);
+  r[3] = make_float4(bb.x, bb.y, 0.f, 0.f);
+  *reinterpret_cast<float2*>(sscale + 2 * m) = gsr_screen_scale(ab.x, ab.y, co.x);
+  const float* f = feat + (int64_t)C * m;
+  float4* fr = reinterpret_cast<float4*>(feat_rows + (int64_t)CW * m);
+#pragma unroll
+  for (int q = 0; q < CW / 4; ++q) {
+    const int c = 4 * q;
+    fr[q] = make_float4(c < C ? f[c] : 0.f, c + 1 < C ? f[c + 1] : 0.f, c + 2 < C ? f[c + 2] : 0.f,
+                        c + 3 < C ? f[c + 3] : 0.f);
+  }
+}
+
 // Backward of the fused kernel's geometry half, fed by the packed per-splat gradient rows the reduction leaves
 // (binning.hip: reduce_grad_kernel):   du dv dA dB | dC dop prune split | df0 df1 df2 visibility | - - - -.
 // One sequential sweep in splat order: K2 backward into the N-sized gradient tensors (rows ``idx``; "+=" when ACC), the
@@ -768,7 +798,7 @@ inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 
 
 extern "C" {
 
-int gsr_abi_version(void) { return 30; }
+int gsr_abi_version(void) { return 31; }
 
 const char* gsr_error_string(int code) {
   switch (code) {
@@ -916,6 +946,23 @@ int gsr_pack_rows(const float* gaussians2d, const float* depth, const float* fea
   if (C == 1) pack_rows_kernel<1><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
   else if (C == 2) pack_rows_kernel<2><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
   else pack_rows_kernel<3><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
+  GSR_CHECK_LAUNCH();
+  return GSR_OK;
+}
+
+int gsr_pack_rows_wide(const float* gaussians2d, const float* depth, const float* features, int64_t M, int32_t C,
+                       const GsrRasterParamsC* params_host, float* rows_out, float* feat_rows_out, float* screen_scale_out,
+                       void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
+  const GsrRasterParams rp = to_params(params_host);
+  if (C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
+  if (M == 0) return GSR_OK;
+  if (!gaussians2d || !depth || !features || !rows_out || !feat_rows_out || !screen_scale_out) return GSR_ERR_INVALID_ARGUMENT;
+  const unsigned g = grid_for(M, 256);
+  if (C <= 4) pack_rows_wide_kernel<4><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
+  else if (C <= 8) pack_rows_wide_kernel<8><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
+  else pack_rows_wide_kernel<16><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

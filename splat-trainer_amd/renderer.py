@@ -426,7 +426,7 @@ class _RasterState:
                "sorted_inst", "tile_range", "vis_partial", "pair_vis", "final_T", "last", "median", "visibility",
                "prune_cost", "split_score", "screen_scale", "want_median", "compute_visibility", "needs_grad",
                "segments", "segment_buffers", "seg_pairs", "seg_min", "image", "key_range", "vis_ready", "vis_capacity",
-               "near_far")
+               "near_far", "feat_rows")
 
   def materialize_visibility(self) -> torch.Tensor:
     """points.visibility = per-splat sum of the forward pass's per-pair partials.  A frame that is back-propagated gets
@@ -501,6 +501,36 @@ def _blank_frame(st: _RasterState, dev) -> torch.Tensor:
   return torch.zeros(H, W, C_, dtype=torch.float32, device=dev)
 
 
+def _wide_width(C_: int) -> int:
+  """Width of a wide frame's feature table (include/gsplat_hip.h: GSR_WIDE_MIN_FEATURES)."""
+  return 4 if C_ <= 4 else (8 if C_ <= 8 else 16)
+
+
+def _composite_backward_wide(st: _RasterState, d_image: torch.Tensor, d_feat: torch.Tensor, dev) -> torch.Tensor:
+  """K7 wide + its per-splat reduction (C >= 4): the packed (M,16) gradient rows with df0..df2 = 0; the feature gradient
+  is written straight into ``d_feat`` (M, C)."""
+  lib = _lib.load()
+  if st.vis_partial is None:
+    raise _lib.GsplatHipError("backward called on a rendering made without gradient state")
+  stream = _stream()
+  dimg = _f32c(d_image)
+  partial = torch.empty(st.O, 8 + _wide_width(st.C), dtype=torch.float32, device=dev)
+  timer = KERNEL_TIMER
+  if timer is not None:
+    timer.begin("composite_backward")
+  _lib.check(lib.gsr_composite_backward_wide(_ptr(st.rows), _ptr(st.feat_rows), _ptr(st.sorted_splat),
+                                             _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.tile_range), st.W, st.H,
+                                             st.C, C.byref(st.params), _ptr(st.final_T), _ptr(st.last), _ptr(dimg),
+                                             _ptr(partial), stream), "gsr_composite_backward_wide")
+  if timer is not None:
+    timer.end("composite_backward")
+  grows = torch.empty(st.M, ROW_FLOATS, dtype=torch.float32, device=dev)
+  _lib.check(lib.gsr_reduce_gradients_wide(_ptr(partial), _ptr(st.vis_partial), _ptr(st.offsets), _ptr(st.count),
+                                           _ptr(st.order), st.M, st.C, _ptr(grows), _ptr(d_feat), stream),
+             "gsr_reduce_gradients_wide")
+  return grows
+
+
 def _composite_backward_rows(st: _RasterState, d_image: Optional[torch.Tensor], dev) -> torch.Tensor:
   """K7 + the per-splat reduction: the packed (M,16) gradient rows of the frame
   (du dv dA dB | dC dop prune split | df0 df1 df2 visibility | 0 0 0 0), zeros when nothing was composited."""
@@ -553,6 +583,7 @@ class _RasterFn(torch.autograd.Function):
                              st.near_far[1], st.params, 0, int(st.want_median), int(st.compute_visibility),
                              int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, g.data_ptr(), d.data_ptr(),
                              f.data_ptr(), st.C, order.data_ptr() if order is not None else None)
+      frame.feature_table = int(st.C >= _lib.WIDE_MIN_FEATURES)
       _, _, _, image = _run_frame(frame, st, g.device, st.M, projected=True)
     ctx.st = st
     ctx.in_dtypes = (g2d.dtype, feats.dtype)      # e.g. fp16 colours from an autocast MLP (mlp_scene.py:362)
@@ -568,11 +599,12 @@ class _RasterFn(torch.autograd.Function):
     d_g2d = alloc(st.M, 6, dtype=torch.float32, device=dev)
     d_feat = alloc(st.M, st.C, dtype=torch.float32, device=dev)
     if live:
-      grows = _composite_backward_rows(st, d_image, dev)
+      wide = st.C >= _lib.WIDE_MIN_FEATURES
+      grows = _composite_backward_wide(st, d_image, d_feat, dev) if wide else _composite_backward_rows(st, d_image, dev)
       # prune_cost / split_score (/ visibility) are written straight into the tensors the Rendering already holds
-      _lib.check(lib.gsr_unpack_grad_rows(_ptr(st.rows), _ptr(grows), st.M, st.C, _ptr(d_g2d), _ptr(d_feat), _ptr(st.prune_cost),
-                                          _ptr(st.split_score), _ptr(_vis_out(st, live)), _stream()),
-                 "gsr_unpack_grad_rows")
+      _lib.check(lib.gsr_unpack_grad_rows(_ptr(st.rows), _ptr(grows), st.M, st.C, _ptr(d_g2d),
+                                          None if wide else _ptr(d_feat), _ptr(st.prune_cost), _ptr(st.split_score),
+                                          _ptr(_vis_out(st, live)), _stream()), "gsr_unpack_grad_rows")
     return d_g2d.to(ctx.in_dtypes[0]), d_feat.to(ctx.in_dtypes[1]), None, None, None
 
 
@@ -656,6 +688,7 @@ def _run_frame(frame: "_lib.GsrFrameC", st: _RasterState, dev, rows_bound: int, 
   st.visibility = V(plan.visibility, (M,), (1,))
   st.prune_cost, st.split_score = V(plan.prune_cost, (M,), (1,)), V(plan.split_score, (M,), (1,))
   st.vis_capacity = capacity
+  st.feat_rows = base + plan.feat_rows if plan.feat_rows >= 0 else None
   if not st.compute_visibility:
     st.visibility.zero_()
   st.vis_ready = not (st.compute_visibility and st.needs_grad)    # without gradients the driver reduced it already
@@ -808,13 +841,14 @@ def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features:
                      render_median_depth: bool = False, _depth_order=None, **_unused) -> Rendering:
   """K4 tile binning -> K5 radix sort -> K6 composite; autograd backward = K7 (+ per-point heuristics).
 
-  ``features`` is (M, C) with C in {1, 2, 3}.  ``points.prune_cost`` / ``points.split_score`` of the
+  ``features`` is (M, C) with 1 <= C <= 16 (C >= 4: the wide path -- a feature table next to the packed rows, every tile
+  composited by one wave; C <= 3 keeps the packed rows' three colour slots).  ``points.prune_cost`` / ``points.split_score`` of the
   returned Rendering are filled in place when ``loss.backward()`` runs (trainer.py:512-514 reads them
   afterwards); ``points.visibility`` is available right after the forward pass (reg_loss,
   mlp_scene.py:268-288, needs ``points.visible`` before backward)."""
   _require_device(gaussians2d, features, depth)
-  if features.dim() != 2 or not (1 <= features.shape[1] <= 3):
-    raise ValueError(f"features must be (M, C) with C in 1..3, got {tuple(features.shape)}")
+  if features.dim() != 2 or not (1 <= features.shape[1] <= _lib.MAX_FEATURES):
+    raise ValueError(f"features must be (M, C) with C in 1..{_lib.MAX_FEATURES}, got {tuple(features.shape)}")
   if config.tile_size != 16:
     raise ValueError("the HIP kernels are specialised for tile_size=16")
   W, H = camera_params.image_size
@@ -833,7 +867,7 @@ def _init_state(st: _RasterState, camera_params: CameraParams, config: RasterCon
   st.params = _lib.raster_params(config)
   st.want_median = bool(render_median_depth)
   st.compute_visibility = bool(config.compute_visibility or config.compute_point_heuristic)
-  st.vis_partial = st.pair_vis = st.segments = st.segment_buffers = st.rows = st.image = None
+  st.vis_partial = st.pair_vis = st.segments = st.segment_buffers = st.rows = st.image = st.feat_rows = None
   st.vis_ready, st.vis_capacity = True, 0
   st.seg_pairs, st.seg_min = int(config.segment_pairs), int(config.segment_min_pairs)
   st.near_far = (float(camera_params.near_plane), float(camera_params.far_plane))
