@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 31) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 32) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -136,6 +136,28 @@ int gsr_project_backward(const float* position, const float* log_scaling, const 
                          const float* projection, const GsrRasterParamsC* params_host, const float* dL_dgaussians2d,
                          const float* dL_ddepth, float* d_position, float* d_log_scaling, float* d_rotation,
                          float* d_alpha_logit, int32_t accumulate, void* stream);
+
+/* ---- camera gradient: dL/dT_camera_world and dL/dprojection (deterministic, no float atomics) -------------------
+ * d_camera: 20 device floats = dL/dT_camera_world [16] (4x4 row major, row 3 zero) then dL/d(fx, fy, cx, cy).  Every
+ * block of the camera-gradient kernels writes one partial row of 20 floats; camera_partials holds
+ * gsr_camera_grad_partial_rows(count) such rows (count: the number of threads the kernel runs, M or N as noted). */
+int64_t gsr_camera_grad_partial_rows(int64_t count);
+/* gsr_project_backward plus the camera gradient (count = M); M = 0 writes zeros to d_camera.  The parameter gradients
+ * are those of gsr_project_backward, bit for bit (the camera terms come from a kernel of their own). */
+int gsr_project_backward_camera(const float* position, const float* log_scaling, const float* rotation_xyzw,
+                                const float* alpha_logit, const int64_t* indexes, int64_t M, const float* T_camera_world,
+                                const float* projection, const GsrRasterParamsC* params_host,
+                                const float* dL_dgaussians2d, const float* dL_ddepth, float* d_position,
+                                float* d_log_scaling, float* d_rotation, float* d_alpha_logit, int32_t accumulate,
+                                float* camera_partials, float* d_camera, void* stream);
+/* dL/d(camera position) [3] of the SH colours, from the Jacobian gsr_sh_forward saved (count = M); jacobian NULL
+ * (K = 1) writes zeros. */
+int gsr_sh_camera_position_grad(const float* dL_dcolors, const float* jacobian, int64_t M, float* camera_partials,
+                                float* d_camera_pos, void* stream);
+/* Sums `rows` partial rows in order.  T_camera_world given: folds the camera-position columns through cam = -R^T t and
+ * writes the 20 floats above; NULL: writes dL/d(camera position) [3] alone. */
+int gsr_camera_grad_finish(const float* camera_partials, int64_t rows, const float* T_camera_world, float* d_camera,
+                           void* stream);
 
 /* ---- K3 spherical-harmonics colour forward / backward  (evaluate_sh_at) --------------------------------- */
 /* sh_features [N,3,K], K in {1,4,9,16}; colour = 0.5 + sum_k sh[c][k] Y_k(normalize(p - camera_pos)). */
@@ -208,6 +230,17 @@ int gsr_project_backward_rows(const float* position, const float* log_scaling, c
                               float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
                               int32_t mode, float* d_colors_out, float* prune_cost_out, float* split_score_out,
                               float* visibility_out, void* stream);
+/* The same sweep plus the camera gradient (gsr_project_backward_camera's d_camera; count = M), with the view-direction
+ * term -(d colour / d position)^T dL/dcolour of every splat when `jacobian` is given.  The geometry outputs are
+ * required.  The parameter gradients are those of gsr_project_backward_rows, bit for bit. */
+int gsr_project_backward_rows_camera(const float* position, const float* log_scaling, const float* rotation_xyzw,
+                                     const float* alpha_logit, const int64_t* indexes, int64_t M, const int32_t* inverse,
+                                     int64_t N, const float* T_camera_world, const float* projection,
+                                     const GsrRasterParamsC* params_host, const float* rows, const float* grad_rows,
+                                     const float* dL_dgaussians2d_extra, const float* dL_ddepth, const float* jacobian,
+                                     float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
+                                     int32_t mode, float* d_colors_out, float* prune_cost_out, float* split_score_out,
+                                     float* visibility_out, float* camera_partials, float* d_camera, void* stream);
 
 /* ---- K4 tile overlap count / key emit, tile ranges  (render_projected, binning) ------------------------- */
 /* depth -> sortable u32 keys, key = min(bits(depth) - bias, max_key), monotone in depth.  gsr_depth_key_range gives
@@ -461,6 +494,10 @@ typedef struct GsrFrameBackwardC {
   float* d_position; float* d_log_scaling; float* d_rotation; float* d_alpha_logit; int32_t mode;
   float* d_sh; int32_t sh_mode;
   float* prune_cost; float* split_score; float* visibility;
+  /* camera gradient: d_camera [20] as gsr_project_backward_camera, or NULL for none; camera_partials
+   * [gsr_camera_grad_partial_rows(M), 20] scratch.  The view-direction term is included when `jacobian` is given
+   * (K > 1). */
+  float* camera_partials; float* d_camera;
 } GsrFrameBackwardC;
 /* event_k7_begin / event_k7_end: hipEvent_t recorded around the composite backward launch, or NULL. */
 int gsr_frame_backward(const GsrFrameBackwardC* backward_host, void* event_k7_begin, void* event_k7_end, void* stream);

@@ -14,7 +14,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GSPLAT_HIP_LIB: load another build of the same library (kernel experiments, tools/k67_bench.py); never a fallback
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
 MAX_FEATURES = 16                  # GSR_MAX_FEATURES
 WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
@@ -70,7 +70,8 @@ class GsrFrameBackwardC(C.Structure):
               ("grad_rows", C.c_void_p), ("inverse", C.c_void_p), ("d_colors", C.c_void_p), ("d_position", C.c_void_p),
               ("d_log_scaling", C.c_void_p), ("d_rotation", C.c_void_p), ("d_alpha_logit", C.c_void_p),
               ("mode", C.c_int32), ("d_sh", C.c_void_p), ("sh_mode", C.c_int32), ("prune_cost", C.c_void_p),
-              ("split_score", C.c_void_p), ("visibility", C.c_void_p)]
+              ("split_score", C.c_void_p), ("visibility", C.c_void_p), ("camera_partials", C.c_void_p),
+              ("d_camera", C.c_void_p)]
 
 
 class GsrFrameResultC(C.Structure):
@@ -112,6 +113,11 @@ PROTOTYPES = {
     "gsr_frustum_cull": (C.c_int, [_p, _i64, _p, _p, _i32, _i32, _f, _f, _f, _p, _p, _p, _sz, _p]),
     "gsr_project_forward": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _u32, _u32, _p]),
     "gsr_project_backward": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "gsr_camera_grad_partial_rows": (_i64, [_i64]),
+    "gsr_project_backward_camera": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _i32, _p, _p,
+                                              _p]),
+    "gsr_sh_camera_position_grad": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "gsr_camera_grad_finish": (C.c_int, [_p, _i64, _p, _p, _p]),
     "gsr_sh_forward": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p]),
     "gsr_sh_backward": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p]),
     "gsr_sh_backward_multi": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _i32, _p]),
@@ -124,6 +130,8 @@ PROTOTYPES = {
                                          _u32, _p]),
     "gsr_project_backward_rows": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _p,
                                             _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "gsr_project_backward_rows_camera": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p,
+                                                   _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "gsr_pack_rows": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p]),
     "gsr_pack_rows_wide": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p, _p]),
     "gsr_tile_count": (C.c_int, [_p, _p, _i64, _i32, _i32, _pp, _p, _p, _p, _p]),

@@ -357,7 +357,14 @@ int gsr_frame_backward_stages(const GsrFrameBackwardC* b, int32_t stages, void* 
   }
   if (!(stages & 2)) return GSR_OK;
   if (needs_inverse) GSR_TRY(gsr_inverse_map(b->indexes, M, N, b->inverse, stream_));
-  if (M > 0 || b->mode == 2)
+  if (b->d_camera)
+    GSR_TRY(gsr_project_backward_rows_camera(
+        b->position, b->log_scaling, b->rotation_xyzw, b->alpha_logit, b->indexes, M, b->mode == 2 ? b->inverse : nullptr,
+        N, b->T_camera_world, b->projection, &b->params, b->rows, b->grad_rows, b->d_gaussians2d, b->d_depth, b->jacobian,
+        b->d_position, b->d_log_scaling, b->d_rotation, b->d_alpha_logit, b->mode, b->d_colors,
+        live ? b->prune_cost : nullptr, live ? b->split_score : nullptr, live ? b->visibility : nullptr,
+        b->camera_partials, b->d_camera, stream_));
+  else if (M > 0 || b->mode == 2)
     GSR_TRY(gsr_project_backward_rows(b->position, b->log_scaling, b->rotation_xyzw, b->alpha_logit, b->indexes, M,
                                       b->mode == 2 ? b->inverse : nullptr, N, b->T_camera_world, b->projection, &b->params,
                                       b->rows, b->grad_rows, b->d_gaussians2d, b->d_depth, b->jacobian, b->d_position,

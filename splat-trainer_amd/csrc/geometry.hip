@@ -1,6 +1,7 @@
 // K1 frustum cull + wave-ballot compaction, K2 3D->2D projection fwd/bwd, K3 SH colour fwd/bwd.
 // All HBM-streaming kernels: one thread per point, coalesced row reads, no LDS.
 #include "gsr_device.h"
+#include "gsr_dpp_reduce.h"
 #include "../../include/gsplat_hip.h"
 
 static_assert(sizeof(GsrRasterParams) == sizeof(GsrRasterParamsC), "raster params layout");
@@ -109,6 +110,109 @@ __global__ __launch_bounds__(256) void depth_keys_pos_kernel(const float* __rest
   float x, y, z;
   gsr_to_camera(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], x, y, z);
   keys[m] = gsr_depth_key(z, key_bias, key_max);
+}
+
+// ---- camera gradient: deterministic, no float atomics.  Kernels of their own, launched after the unchanged parameter
+// backward (forming the camera terms inside it changes where fp contraction fuses its products: the parameter gradients
+// would differ in the last bit from a run without camera gradient).  Every lane of a 256-thread block holds its splat's
+// CAM_PARTIAL_FLOATS partial sums -- the 16 camera terms of gsr_project_one_bwd<true>, then dL/d(camera position) (3),
+// then a zero pad -- and lanes without a splat hold zeros.  Each row of 16 lanes sums by DPP shifts into
+// its lane 15, the block's 16 row sums go through LDS and are added in row order by 20 threads: one partial row per
+// block.  cam_grad_finish_kernel adds the rows in order and folds the camera-position term into dL/dT.
+constexpr int CAM_PARTIAL_FLOATS = 20;
+constexpr int CAM_POS_AT = GSR_CAM_GRAD_FLOATS;    // columns 16..18: dL/d(camera position)
+
+__device__ __forceinline__ void gsr_block_cam_sum(float (&v)[CAM_PARTIAL_FLOATS], float* __restrict__ out) {
+  __shared__ float s_rows[16][CAM_PARTIAL_FLOATS];  // 4 waves x 4 rows of 16 lanes
+  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) v[j] = gsr_row_sum_to_lane15(v[j]);
+  if ((lane & 15) == 15) {
+#pragma unroll
+    for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) s_rows[4 * wave + (lane >> 4)][j] = v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < CAM_PARTIAL_FLOATS) {
+    float a = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a += s_rows[r][threadIdx.x];
+    out[threadIdx.x] = a;
+  }
+}
+
+// One block: rows of partials in order (thread t: rows t, t + 256, ...), then the block sum as above.  Tcw given: writes
+// dL/dT_camera_world [16] (row 3 zero) and dL/dprojection [4]; Tcw NULL: dL/d(camera position) [3] alone.
+__global__ __launch_bounds__(256) void cam_grad_finish_kernel(const float* __restrict__ partials, int64_t rows,
+                                                              const float* __restrict__ Tcw, float* __restrict__ out) {
+  float v[CAM_PARTIAL_FLOATS];
+#pragma unroll
+  for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) v[j] = 0.f;
+  for (int64_t r = threadIdx.x; r < rows; r += 256) {
+#pragma unroll
+    for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) v[j] += partials[r * CAM_PARTIAL_FLOATS + j];
+  }
+  __shared__ float tot[CAM_PARTIAL_FLOATS];
+  gsr_block_cam_sum(v, tot);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!Tcw) {
+    out[0] = tot[CAM_POS_AT]; out[1] = tot[CAM_POS_AT + 1]; out[2] = tot[CAM_POS_AT + 2];
+    return;
+  }
+  const float unit[4] = {1.f, 1.f, 0.f, 0.f};
+  float dT[12];
+  for (int k = 0; k < 12; ++k) dT[k] = tot[k];
+  gsr_fold_camera_position(gsr_load_cam(Tcw, unit), tot + CAM_POS_AT, dT);
+  for (int k = 0; k < 12; ++k) out[k] = dT[k];
+  for (int k = 12; k < 16; ++k) out[k] = 0.f;
+  for (int k = 0; k < 4; ++k) out[16 + k] = tot[12 + k];
+}
+
+// dL/d(camera position) of the SH colours from the saved Jacobian: the colour depends on p - cam, so it is minus the
+// position term of every visible splat.
+__global__ __launch_bounds__(256) void sh_camera_grad_kernel(const float* __restrict__ dcol, const float* __restrict__ jac,
+                                                             int64_t M, float* __restrict__ partials) {
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float acc[CAM_PARTIAL_FLOATS];
+#pragma unroll
+  for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) acc[j] = 0.f;
+  if (m < M) {
+    const float g3[3] = {dcol[3 * m], dcol[3 * m + 1], dcol[3 * m + 2]};
+    float pj[3];
+    gsr_jac_apply(g3, jac + 9 * m, pj);
+    acc[CAM_POS_AT] = -pj[0]; acc[CAM_POS_AT + 1] = -pj[1]; acc[CAM_POS_AT + 2] = -pj[2];
+  }
+  gsr_block_cam_sum(acc, partials + (int64_t)blockIdx.x * CAM_PARTIAL_FLOATS);
+}
+
+// Camera terms of the three-call K2 backward (gsr_project_backward's inputs): one partial row per block.
+__global__ __launch_bounds__(256) void project_bwd_camera_kernel(const float* __restrict__ pos, const float* __restrict__ ls,
+                                                                 const float* __restrict__ rot,
+                                                                 const float* __restrict__ logit,
+                                                                 const int64_t* __restrict__ idx, int64_t M,
+                                                                 const float* __restrict__ Tcw,
+                                                                 const float* __restrict__ proj, GsrRasterParams rp,
+                                                                 const float* __restrict__ dg2d,
+                                                                 const float* __restrict__ ddepth,
+                                                                 float* __restrict__ cam_partials) {
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float acc[CAM_PARTIAL_FLOATS];
+#pragma unroll
+  for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) acc[j] = 0.f;
+  if (m < M) {
+    const GsrCam cam = gsr_load_cam(Tcw, proj);
+    const int64_t i = idx[m];
+    float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    float s[3] = {ls[3 * i], ls[3 * i + 1], ls[3 * i + 2]};
+    const float4 qv = *reinterpret_cast<const float4*>(rot + 4 * i);
+    float q[4] = {qv.x, qv.y, qv.z, qv.w};
+    float g[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = dg2d[6 * m + k];
+    const float gd = ddepth ? ddepth[m] : 0.f;
+    (void)gsr_project_one_bwd<true>(cam, rp, p, s, q, logit[i], g, gd, acc);
+  }
+  gsr_block_cam_sum(acc, cam_partials + (int64_t)blockIdx.x * CAM_PARTIAL_FLOATS);
 }
 
 template <bool ACC>
@@ -538,6 +642,48 @@ __global__ __launch_bounds__(256) void project_bwd_rows_kernel(
   dlogit[i] = ACC ? dlogit[i] + o.dlogit : o.dlogit;
 }
 
+// Camera terms of the frame's backward sweep (project_bwd_rows_kernel's inputs, any MODE: thread per visible splat),
+// the view-direction term -pj included when the Jacobian is given: one partial row per block.
+__global__ __launch_bounds__(256) void project_bwd_rows_camera_kernel(
+    const float* __restrict__ pos, const float* __restrict__ ls, const float* __restrict__ rot,
+    const float* __restrict__ logit, const int64_t* __restrict__ idx, int64_t M, const float* __restrict__ Tcw,
+    const float* __restrict__ proj, GsrRasterParams rp, const float* __restrict__ grows,
+    const float* __restrict__ dg2d_extra, const float* __restrict__ ddepth, const float* __restrict__ jac,
+    float* __restrict__ cam_partials) {
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float acc[CAM_PARTIAL_FLOATS];
+#pragma unroll
+  for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) acc[j] = 0.f;
+  if (m < M) {
+    const int64_t i = idx[m];
+    const float4* gr = reinterpret_cast<const float4*>(grows + (int64_t)GSR_ROW_FLOATS * m);
+    const float4 g0 = gr[0], g1 = gr[1], g2 = gr[2];
+    const GsrCam cam = gsr_load_cam(Tcw, proj);
+    float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    float s[3] = {ls[3 * i], ls[3 * i + 1], ls[3 * i + 2]};
+    const float4 qv = *reinterpret_cast<const float4*>(rot + 4 * i);
+    float q[4] = {qv.x, qv.y, qv.z, qv.w};
+    // the same d(u, v, A, B, C, opacity) as project_bwd_rows_kernel forms from the moments in the row
+    const GsrProjected fo = gsr_project_one(cam, rp, p, s, q, logit[i]);
+    const float cA = fo.A, cB = fo.B, cC = fo.C;
+    float g[6] = {cA * g0.x + cB * g0.y, cB * g0.x + cC * g0.y, -0.5f * g0.z, -g0.w, -0.5f * g1.x,
+                  fo.opacity > 0.f ? g1.y / fo.opacity : 0.f};
+    if (dg2d_extra) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) g[k] += dg2d_extra[6 * m + k];
+    }
+    const float gd = ddepth ? ddepth[m] : 0.f;
+    (void)gsr_project_one_bwd<true>(cam, rp, p, s, q, logit[i], g, gd, acc);
+    if (jac) {
+      const float g3[3] = {g2.x, g2.y, g2.z};
+      float pj[3];
+      gsr_jac_apply(g3, jac + 9 * m, pj);
+      acc[CAM_POS_AT] = -pj[0]; acc[CAM_POS_AT + 1] = -pj[1]; acc[CAM_POS_AT + 2] = -pj[2];
+    }
+  }
+  gsr_block_cam_sum(acc, cam_partials + (int64_t)blockIdx.x * CAM_PARTIAL_FLOATS);
+}
+
 template <int K, bool ACC>
 __global__ __launch_bounds__(256) void sh_bwd_kernel(const float* __restrict__ dcol, const float* __restrict__ sh,
                                                      const float* __restrict__ pos, const int64_t* __restrict__ idx,
@@ -798,7 +944,7 @@ inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 
 
 extern "C" {
 
-int gsr_abi_version(void) { return 31; }
+int gsr_abi_version(void) { return 32; }
 
 const char* gsr_error_string(int code) {
   switch (code) {
@@ -887,6 +1033,57 @@ int gsr_project_backward(const float* position, const float* log_scaling, const 
                                                                    d_position, d_log_scaling, d_rotation, d_alpha_logit);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
+}
+
+int64_t gsr_camera_grad_partial_rows(int64_t count) { return count > 0 ? (int64_t)grid_for(count, 256) : 0; }
+
+int gsr_camera_grad_finish(const float* partials, int64_t rows, const float* T_camera_world, float* d_camera,
+                           void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (rows < 0 || !d_camera || (rows > 0 && !partials)) return GSR_ERR_INVALID_ARGUMENT;
+  cam_grad_finish_kernel<<<1, 256, 0, stream>>>(partials, rows, T_camera_world, d_camera);
+  GSR_CHECK_LAUNCH();
+  return GSR_OK;
+}
+
+int gsr_project_backward_camera(const float* position, const float* log_scaling, const float* rotation_xyzw,
+                                const float* alpha_logit, const int64_t* indexes, int64_t M, const float* T_camera_world,
+                                const float* projection, const GsrRasterParamsC* params_host,
+                                const float* dL_dgaussians2d, const float* dL_ddepth, float* d_position,
+                                float* d_log_scaling, float* d_rotation, float* d_alpha_logit, int32_t accumulate,
+                                float* camera_partials, float* d_camera, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || !params_host || !T_camera_world || !projection || !d_camera) return GSR_ERR_INVALID_ARGUMENT;
+  if (M > 0 && (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !indexes || !dL_dgaussians2d ||
+                !d_position || !d_log_scaling || !d_rotation || !d_alpha_logit || !camera_partials))
+    return GSR_ERR_INVALID_ARGUMENT;
+  if (M > 0) {
+    // the parameter gradient exactly as gsr_project_backward computes it, then the camera terms
+    const int rc = gsr_project_backward(position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, T_camera_world,
+                                        projection, params_host, dL_dgaussians2d, dL_ddepth, d_position, d_log_scaling,
+                                        d_rotation, d_alpha_logit, accumulate, stream_);
+    if (rc != GSR_OK) return rc;
+    project_bwd_camera_kernel<<<grid_for(M, 256), 256, 0, stream>>>(position, log_scaling, rotation_xyzw, alpha_logit,
+                                                                    indexes, M, T_camera_world, projection,
+                                                                    to_params(params_host), dL_dgaussians2d, dL_ddepth,
+                                                                    camera_partials);
+    GSR_CHECK_LAUNCH();
+  }
+  return gsr_camera_grad_finish(camera_partials, gsr_camera_grad_partial_rows(M), T_camera_world, d_camera, stream_);
+}
+
+int gsr_sh_camera_position_grad(const float* dL_dcolors, const float* jacobian, int64_t M, float* camera_partials,
+                                float* d_camera_pos, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || !d_camera_pos) return GSR_ERR_INVALID_ARGUMENT;
+  const bool live = M > 0 && jacobian != nullptr;        // no Jacobian (K = 1): the colour does not depend on the camera
+  if (live && (!dL_dcolors || !camera_partials)) return GSR_ERR_INVALID_ARGUMENT;
+  if (live) {
+    sh_camera_grad_kernel<<<grid_for(M, 256), 256, 0, stream>>>(dL_dcolors, jacobian, M, camera_partials);
+    GSR_CHECK_LAUNCH();
+  }
+  return gsr_camera_grad_finish(camera_partials, live ? gsr_camera_grad_partial_rows(M) : 0, nullptr, d_camera_pos,
+                                stream_);
 }
 
 int gsr_depth_keys_from_positions(const float* position, const int64_t* indexes, int64_t M, const uint32_t* count_dev,
@@ -997,6 +1194,33 @@ int gsr_project_backward_rows(const float* position, const float* log_scaling, c
 #undef GSR_LAUNCH_PBR
   GSR_CHECK_LAUNCH();
   return GSR_OK;
+}
+
+int gsr_project_backward_rows_camera(const float* position, const float* log_scaling, const float* rotation_xyzw,
+                                     const float* alpha_logit, const int64_t* indexes, int64_t M, const int32_t* inverse,
+                                     int64_t N, const float* T_camera_world, const float* projection,
+                                     const GsrRasterParamsC* params_host, const float* rows, const float* grad_rows,
+                                     const float* dL_dgaussians2d_extra, const float* dL_ddepth, const float* jacobian,
+                                     float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
+                                     int32_t mode, float* d_colors_out, float* prune_cost_out, float* split_score_out,
+                                     float* visibility_out, float* camera_partials, float* d_camera, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (M < 0 || !d_camera || !T_camera_world || !projection || !d_position || (M > 0 && (!indexes || !grad_rows || !camera_partials)))
+    return GSR_ERR_INVALID_ARGUMENT;
+  // the sweep exactly as gsr_project_backward_rows runs it, then the camera terms over the visible splats
+  const int rc = gsr_project_backward_rows(position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, inverse, N,
+                                           T_camera_world, projection, params_host, rows, grad_rows,
+                                           dL_dgaussians2d_extra, dL_ddepth, jacobian, d_position, d_log_scaling,
+                                           d_rotation, d_alpha_logit, mode, d_colors_out, prune_cost_out,
+                                           split_score_out, visibility_out, stream_);
+  if (rc != GSR_OK) return rc;
+  if (M > 0) {
+    project_bwd_rows_camera_kernel<<<grid_for(M, 256), 256, 0, stream>>>(
+        position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, T_camera_world, projection, to_params(params_host),
+        grad_rows, dL_dgaussians2d_extra, dL_ddepth, jacobian, camera_partials);
+    GSR_CHECK_LAUNCH();
+  }
+  return gsr_camera_grad_finish(camera_partials, gsr_camera_grad_partial_rows(M), T_camera_world, d_camera, stream_);
 }
 
 int gsr_sh_forward(const float* sh_features, const float* positions, const int64_t* indexes, int64_t M, int32_t K,

@@ -1,4 +1,5 @@
-// Fused in-place wave64 cross-lane sums used by the composite forward pass (visibility of four pairs at once):
+// Fused in-place wave64 cross-lane sums used by the composite forward pass (visibility of four pairs at once) and the
+// camera-gradient block sums (geometry.hip):
 //   gsr_swap32_add / gsr_swap16_add   v_permlane{32,16}_swap + add: two registers fold into one, each half (quarter) of
 //                                     the lanes ends up holding the partial sum of one of the two values
 //   gsr_row_sum_to_lane15             v_add_f32_dpp vN, vN, vN row_shr:1/2/4/8 -- one VALU op per step (the

@@ -137,10 +137,18 @@ struct GsrProjectGrad {
   float dp[3], dls[3], dq[4], dlogit;
 };
 
+// Camera-gradient accumulator layout (GSR_CAM_GRAD_FLOATS): [4 r + k] = dL/dR[r][k] (k < 3), [4 r + 3] = dL/dt[r] -- the
+// first three rows of dL/dT_camera_world -- then [12..15] = dL/d(fx, fy, cx, cy).
+#define GSR_CAM_GRAD_FLOATS 16
+
 // K2 backward for one splat: g = dL/d[u v A B C opacity], gdepth = dL/ddepth.
+// CAM: also ADD this splat's terms of dL/d(T_camera_world, projection) to cam[GSR_CAM_GRAD_FLOATS], from the
+// intermediates the parameter gradient forms anyway (dL/d camera-space point, dL/d(J R), the camera-space point).  The
+// default instantiation (CAM = false) is the parameter gradient alone, unchanged.
+template <bool CAM = false>
 GSR_HD GsrProjectGrad gsr_project_one_bwd(const GsrCam& c, const GsrRasterParams& rp, const float p[3],
                                           const float ls[3], const float q[4], float logit,
-                                          const float g[6], float gdepth) {
+                                          const float g[6], float gdepth, float* cam = nullptr) {
   GsrProjectGrad o;
   float x, y, z;
   gsr_to_camera(c, p[0], p[1], p[2], x, y, z);
@@ -248,7 +256,35 @@ GSR_HD GsrProjectGrad gsr_project_one_bwd(const GsrCam& c, const GsrRasterParams
   o.dp[0] = c.R[0] * gxc + c.R[3] * gyc + c.R[6] * gzc;
   o.dp[1] = c.R[1] * gxc + c.R[4] * gyc + c.R[7] * gzc;
   o.dp[2] = c.R[2] * gxc + c.R[5] * gyc + c.R[8] * gzc;
+  if (CAM) {
+    // p_c = R p + t
+    const float gpc[3] = {gxc, gyc, gzc};
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) cam[4 * r + k] += gpc[r] * p[k];
+      cam[4 * r + 3] += gpc[r];
+    }
+    // Wm = J R: row 0 of J is (j00, 0, j02), row 1 (0, j11, j12)
+    for (int k = 0; k < 3; ++k) {
+      cam[k] += j00 * gW[k];
+      cam[4 + k] += j11 * gW[3 + k];
+      cam[8 + k] += j02 * gW[k] + j12 * gW[3 + k];
+    }
+    // u = fx x/z + cx, j00 = fx/z, j02 = -fx x/z^2 (v, fy, cy alike)
+    cam[12] += g[0] * x * iz + gJ00 * iz - gJ02 * x * iz2;
+    cam[13] += g[1] * y * iz + gJ11 * iz - gJ12 * y * iz2;
+    cam[14] += g[0];
+    cam[15] += g[1];
+  }
   return o;
+}
+
+// Fold dL/d(camera position) into dL/dT_camera_world through cam = -R^T t:  dR[i][j] -= t[i] dcam[j],
+// dt[i] -= sum_j R[i][j] dcam[j].  dT: the first 12 entries of the accumulator above.
+GSR_HD void gsr_fold_camera_position(const GsrCam& c, const float dcam[3], float* dT) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) dT[4 * i + j] -= c.t[i] * dcam[j];
+    dT[4 * i + 3] -= c.R[3 * i] * dcam[0] + c.R[3 * i + 1] * dcam[1] + c.R[3 * i + 2] * dcam[2];
+  }
 }
 
 // dL/dposition through the view direction from the colour gradient g and the saved d colour / d position (row-major 3x3).

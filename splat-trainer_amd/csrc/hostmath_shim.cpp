@@ -39,6 +39,26 @@ void hm_project_backward(const float* T, const float* proj, const void* params, 
   }
 }
 
+// per-splat camera terms of the K2 backward: cam[M, 16] (gsr_math.h: GSR_CAM_GRAD_FLOATS layout), overwritten
+void hm_project_backward_camera(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
+                                const float* ls, const float* rot, const float* logit, const float* dg2d,
+                                const float* ddepth, float* cam) {
+  GsrRasterParams rp;
+  memcpy(&rp, params, sizeof(rp));
+  GsrCam c = gsr_load_cam(T, proj);
+  for (int64_t m = 0; m < M; ++m) {
+    float* acc = cam + GSR_CAM_GRAD_FLOATS * m;
+    for (int k = 0; k < GSR_CAM_GRAD_FLOATS; ++k) acc[k] = 0.f;
+    gsr_project_one_bwd<true>(c, rp, pos + 3 * m, ls + 3 * m, rot + 4 * m, logit[m], dg2d + 6 * m, ddepth[m], acc);
+  }
+}
+
+// dT[12] += the fold of dL/d(camera position) dcam[3] through cam = -R^T t
+void hm_fold_camera_position(const float* T, const float* dcam, float* dT) {
+  const float proj[4] = {1.f, 1.f, 0.f, 0.f};
+  gsr_fold_camera_position(gsr_load_cam(T, proj), dcam, dT);
+}
+
 void hm_in_view(const float* T, const float* proj, int64_t N, const float* pos, int W, int H, float near_p,
                 float far_p, float margin, uint8_t* mask) {
   GsrCam cam = gsr_load_cam(T, proj);

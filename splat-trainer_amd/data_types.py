@@ -74,6 +74,10 @@ class CameraParams:
 
   @property
   def camera_position(self) -> torch.Tensor:
+    if self.T_camera_world.requires_grad:
+      # a learnable pose is updated in place by its optimiser, and a value cached in grad mode would carry the graph of
+      # the first render into every later one: never cached
+      return -(self.T_camera_world[:3, :3].t() @ self.T_camera_world[:3, 3])
     cached = self.__dict__.get("_camera_position")       # the pose is immutable (frozen dataclass): compute once
     if cached is None:
       R = self.T_camera_world[:3, :3]

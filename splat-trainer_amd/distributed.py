@@ -451,6 +451,11 @@ class CameraShardedStep:
     of the batch -- locally with one fused launch per camera on one rank, through the LIGHT exchange on several (max /
     sum / count as reductions, the two EMA inputs per camera all-gathered and replayed in camera order) -- and nothing
     is returned.  Without it (and ``with_stats``) the full per-camera statistics of the batch are returned instead."""
+    for cam in cameras:
+      T, proj = getattr(cam, "T_camera_world", None), getattr(cam, "projection", None)
+      if (T is not None and T.requires_grad) or (proj is not None and proj.requires_grad):
+        raise ValueError("camera gradients are not supported in data-parallel mode (CameraShardedStep): detach "
+                         "T_camera_world and projection of the batch's cameras")
     position, feature = self.params[0], self.params[4]
     dev = position.device
     N = position.shape[0]

@@ -32,6 +32,7 @@ from .sh import evaluate_sh_at
 
 ROW_FLOATS = 16          # packed per-splat row (64 bytes; include/gsplat_hip.h GSR_ROW_FLOATS)
 PARTIAL_FLOATS = 12
+CAMERA_GRAD_FLOATS = 20   # dL/dT_camera_world (4x4) + dL/dprojection (include/gsplat_hip.h: gsr_project_backward_camera)
 
 
 class KernelTimer:
@@ -118,6 +119,34 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
   if t.dtype is torch.float32 and t.is_contiguous():
     return t.detach()
   return t.detach().to(torch.float32).contiguous()
+
+
+def _f32c_camera(t: torch.Tensor) -> torch.Tensor:
+  """_f32c for T_camera_world / projection, keeping their autograd graph: the camera gradient the nodes below return
+  flows back through the cast, in the caller's dtype."""
+  if t.dtype is torch.float32 and t.is_contiguous():
+    return t
+  return t.to(torch.float32).contiguous()
+
+
+def _wants_camera_grad(camera_params: CameraParams) -> bool:
+  return torch.is_grad_enabled() and (camera_params.T_camera_world.requires_grad or
+                                      camera_params.projection.requires_grad)
+
+
+def _camera_grads(d_camera: Optional[torch.Tensor], dev):
+  """(dL/dT_camera_world (4,4), dL/dprojection (4,)) from the 20 floats the camera-gradient kernels write; zeros when
+  nothing reached the camera."""
+  if d_camera is None:
+    d_camera = torch.zeros(CAMERA_GRAD_FLOATS, dtype=torch.float32, device=dev)
+  return d_camera[:16].view(4, 4), d_camera[16:]
+
+
+def _camera_scratch(count: int, dev):
+  """(partial rows, d_camera) buffers of the camera-gradient kernels run over ``count`` threads."""
+  rows = int(_lib.load().gsr_camera_grad_partial_rows(count))
+  return (torch.empty(max(rows, 1) * CAMERA_GRAD_FLOATS, dtype=torch.float32, device=dev),
+          torch.empty(CAMERA_GRAD_FLOATS, dtype=torch.float32, device=dev))
 
 
 # ------------------------------------------------------------------------------------------- K1 + K2
@@ -384,17 +413,28 @@ class _ProjectFn(torch.autograd.Function):
       live = M > 0 and (d_g2d is not None or d_depth is not None)
       alloc = torch.empty_like if (M == N and live) else torch.zeros_like   # every row is written when nothing was culled
       d_pos, d_ls, d_rot, d_al = alloc(pos), alloc(ls), alloc(rot), alloc(al)
+    want_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+    d_camera = None
     if M > 0 and (d_g2d is not None or d_depth is not None):
       dg = _f32c(d_g2d) if d_g2d is not None else torch.zeros(M, 6, dtype=torch.float32, device=pos.device)
       dd = _f32c(d_depth) if d_depth is not None else None
-      _lib.check(lib.gsr_project_backward(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
-                                          _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
-                                          _ptr(d_ls), _ptr(d_rot), _ptr(d_al), 1 if go is not None else 0,
-                                          _stream()), "gsr_project_backward")
+      if want_cam:
+        partials, d_camera = _camera_scratch(M, pos.device)
+        _lib.check(lib.gsr_project_backward_camera(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
+                                                   _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
+                                                   _ptr(d_ls), _ptr(d_rot), _ptr(d_al), 1 if go is not None else 0,
+                                                   _ptr(partials), _ptr(d_camera), _stream()),
+                   "gsr_project_backward_camera")
+      else:
+        _lib.check(lib.gsr_project_backward(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
+                                            _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
+                                            _ptr(d_ls), _ptr(d_rot), _ptr(d_al), 1 if go is not None else 0,
+                                            _stream()), "gsr_project_backward")
+    d_T, d_proj = _camera_grads(d_camera, pos.device) if want_cam else (None, None)
     if go is not None:
-      return None, None, None, None, None, None, None, None, None, None
+      return None, None, None, None, d_T, d_proj, None, None, None, None
     dt = ctx.in_dtypes
-    return d_pos.to(dt[0]), d_ls.to(dt[1]), d_rot.to(dt[2]), d_al.to(dt[3]), None, None, None, None, None, None
+    return d_pos.to(dt[0]), d_ls.to(dt[1]), d_rot.to(dt[2]), d_al.to(dt[3]), d_T, d_proj, None, None, None, None
 
 
 def project_to_image(gaussians: Gaussians3D, camera_params: CameraParams, config: RasterConfig,
@@ -406,8 +446,8 @@ def project_to_image(gaussians: Gaussians3D, camera_params: CameraParams, config
   ``prefetch={}``: the depth sort render_projected needs is enqueued right away (it only depends on ``depth``) and handed
   back as ``prefetch["depth_order"]`` for ``render_projected(..., _depth_order=prefetch["depth_order"])``."""
   _require_device(gaussians.position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit)
-  T = _f32c(camera_params.T_camera_world)
-  proj = _f32c(camera_params.projection)
+  T = _f32c_camera(camera_params.T_camera_world)
+  proj = _f32c_camera(camera_params.projection)
   params = _lib.raster_params(config)
   W, H = camera_params.image_size
   cull_args = (int(W), int(H), float(camera_params.near_plane), float(camera_params.far_plane),
@@ -709,7 +749,7 @@ class _FrameFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, position, log_scaling, rotation, alpha_logit, feature, T, proj, cam_pos, cull_args, st: _RasterState,
-              grad_out, sh_out, want_pos_grad):
+              grad_out, sh_out, want_jac):
     lib = _lib.load()
     pos, ls, rot, al = _f32c(position), _f32c(log_scaling), _f32c(rotation), _f32c(alpha_logit)
     sh, cam = _f32c(feature), _f32c(cam_pos)
@@ -729,7 +769,7 @@ class _FrameFn(torch.autograd.Function):
       return image, rows[:, 0:6], rows[:, 10:11], indexes
     frame = _lib.GsrFrameC(pos.data_ptr(), ls.data_ptr(), rot.data_ptr(), al.data_ptr(), sh.data_ptr(), N, K, W, H,
                            T.data_ptr(), proj.data_ptr(), cam.data_ptr(), near, far, st.params,
-                           int(bool(want_pos_grad and K > 1)), int(st.want_median), int(st.compute_visibility),
+                           int(bool(want_jac and K > 1)), int(st.want_median), int(st.compute_visibility),
                            int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, None, None, None, 3, None)
     if SIDE_STREAM:
       side, fork, join = _side_stream(dev)
@@ -754,6 +794,9 @@ class _FrameFn(torch.autograd.Function):
     go, sh_out = ctx.grad_out, ctx.sh_out
     collector = sh_out if isinstance(sh_out, _sh.ShFactorCollector) else None
     nothing = (None,) * 13
+    # the camera gradient, view-direction term included (folded natively: None is returned for cam_pos)
+    want_cam = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
+    partials = d_camera = None
     # Geometry gradients: added to caller-owned buffers (mode 1), or every scene row written -- zeros where the camera saw
     # nothing -- when the destination holds nothing worth keeping (fresh tensors for autograd, or buffers the caller
     # declared uninitialised): no zero-fill and no read-modify-write (mode 2; mode 0 + zero-fill when the camera saw
@@ -806,13 +849,16 @@ class _FrameFn(torch.autograd.Function):
       timer = KERNEL_TIMER
       ev = timer.pair("composite_backward") if (timer is not None and live) else (None, None)
       seg = C.addressof(st.segments) if st.segments is not None else None
+      if want_cam:
+        partials, d_camera = _camera_scratch(M, dev)
       args = _lib.GsrFrameBackwardC(
           _ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(sh), N, K, st.W, st.H, st.C, _ptr(T), _ptr(proj), _ptr(cam),
           st.params, M, st.O, _ptr(indexes), _ptr(st.rows), _ptr(st.order), _ptr(st.count), _ptr(st.offsets),
           _ptr(st.sorted_splat), _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.vis_partial), _ptr(st.tile_range),
           _ptr(st.final_T), _ptr(st.last), _ptr(st.image), _ptr(ctx.jac), seg, _ptr(dimg), _ptr(dg), _ptr(dd),
           _ptr(partial), _ptr(grows), _ptr(inv), _ptr(dcol), _ptr(d_pos), _ptr(d_ls), _ptr(d_rot), _ptr(d_al), mode,
-          _ptr(d_sh), sh_mode, _ptr(st.prune_cost), _ptr(st.split_score), _ptr(_vis_out(st, live)))
+          _ptr(d_sh), sh_mode, _ptr(st.prune_cost), _ptr(st.split_score), _ptr(_vis_out(st, live)), _ptr(partials),
+          _ptr(d_camera))
       early = getattr(collector, "on_rows", None) if collector is not None else None
       if early is not None and M > 0:
         # data-parallel: K7 + reduction first; the caller packs the colour-gradient factors straight from the packed rows
@@ -828,12 +874,13 @@ class _FrameFn(torch.autograd.Function):
       # (4th entry: has the position term of this camera's colour gradient been added to d_position already? -- by the
       # sweep above, from the Jacobian the forward pass saved; K = 1 has no such term)
       collector.items.append((indexes, dcol, cam, K == 1 or ctx.jac is not None))
+    cam = _camera_grads(d_camera, dev) if want_cam else (None, None)
     if go is not None:
       return (None, None, None, None, d_sh.to(ctx.in_dtypes[4]) if (d_sh is not None and sh_out is None) else None) + \
-          nothing[5:]
+          cam + nothing[7:]
     dt = ctx.in_dtypes
     return (d_pos.to(dt[0]), d_ls.to(dt[1]), d_rot.to(dt[2]), d_al.to(dt[3]),
-            d_sh.to(dt[4]) if (d_sh is not None and sh_out is None) else None) + nothing[5:]
+            d_sh.to(dt[4]) if (d_sh is not None and sh_out is None) else None) + cam + nothing[7:]
 
 
 def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features: torch.Tensor,
@@ -918,6 +965,10 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   _require_device(position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit, feature)
   if config.tile_size != 16:
     raise ValueError("the HIP kernels are specialised for tile_size=16")
+  cam_grad = _wants_camera_grad(camera_params)
+  if cam_grad and sh_collector is not None:
+    raise ValueError("camera gradients are not supported in data-parallel mode (sh_collector): detach T_camera_world "
+                     "and projection, or render on one device")
   sh_out = None
   if sh_collector is not None:              # data-parallel: exchange colour-gradient factors, not d_sh (sh.py)
     sh_out = sh_collector
@@ -927,7 +978,7 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   st = _RasterState()
   st.M, st.C, st.W, st.H, st.O = 0, 3, int(W), int(H), 0
   _init_state(st, camera_params, config, render_median_depth)
-  st.needs_grad = torch.is_grad_enabled() and (grad_out is not None or sh_collector is not None or any(
+  st.needs_grad = torch.is_grad_enabled() and (grad_out is not None or sh_collector is not None or cam_grad or any(
       t.requires_grad for t in (position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit, feature)))
   cull_args = (int(W), int(H), float(camera_params.near_plane), float(camera_params.far_plane),
                float(config.margin_tiles * config.tile_size))
@@ -937,8 +988,15 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   want_pos_grad = _sh.wants_position_grad(position, sh_out) or (
       sh_collector is not None and sh_collector.position_term_local and torch.is_grad_enabled() and
       (position.requires_grad or grad_out is not None))
+  # (the camera gradient's view-direction term is formed natively from the same saved Jacobian and folded into dL/dT:
+  # the node takes the camera position without a graph)
+  if camera_params.T_camera_world.requires_grad:
+    T_ = camera_params.T_camera_world.detach()       # the pose as it is now (an optimiser updates it in place)
+    cam_pos = -(T_[:3, :3].t() @ T_[:3, 3])
+  else:
+    cam_pos = camera_params.camera_position
   image, g2d, depth, indexes = _FrameFn.apply(position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit,
-                                              feature, _f32c(camera_params.T_camera_world),
-                                              _f32c(camera_params.projection), camera_params.camera_position, cull_args,
-                                              st, grad_out, sh_out, want_pos_grad)
+                                              feature, _f32c_camera(camera_params.T_camera_world),
+                                              _f32c_camera(camera_params.projection), cam_pos, cull_args, st,
+                                              grad_out, sh_out, want_pos_grad or cam_grad)
   return _rendering_of(st, image, indexes, g2d, depth, camera_params)

@@ -82,13 +82,14 @@ class _SHFn(torch.autograd.Function):
       out = torch.empty(M, 3, dtype=torch.float32, device=sh.device)
       # d colour / d position is cheap to form while the coefficient row is in registers; saving it (36 B per
       # splat) spares the backward pass a second sweep over the 12K-byte rows
+      # (the camera position's gradient is formed from it too)
       jac = torch.empty(M, 9, dtype=torch.float32, device=sh.device) if (want_pos_grad and K > 1 and M > 0) else None
       _lib.check(lib.gsr_sh_forward(_ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(out), _ptr(jac), None,
                                     _stream()), "gsr_sh_forward")
     ctx.save_for_backward(sh, pos, idx, cam)
     ctx.jac = jac
     ctx.grad_out = grad_out
-    ctx.in_dtypes = (sh_features.dtype, positions.dtype)
+    ctx.in_dtypes = (sh_features.dtype, positions.dtype, camera_pos.dtype)
     return out
 
   @staticmethod
@@ -138,10 +139,19 @@ class _SHFn(torch.autograd.Function):
       if M > 0:
         _lib.check(lib.gsr_sh_backward(_ptr(g), _ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(ctx.jac),
                                        _ptr(d_sh), _ptr(d_pos), 1, _stream()), "gsr_sh_backward")
+    d_cam = None
+    if ctx.needs_input_grad[3]:
+      # the colour depends on positions - camera_pos: minus the position term of every splat, summed in a fixed order
+      d_cam = torch.empty(3, dtype=torch.float32, device=pos.device)
+      rows = int(lib.gsr_camera_grad_partial_rows(M)) if ctx.jac is not None else 0
+      partials = torch.empty(max(rows, 1) * 20, dtype=torch.float32, device=pos.device)
+      _lib.check(lib.gsr_sh_camera_position_grad(_ptr(g), _ptr(ctx.jac), M, _ptr(partials), _ptr(d_cam), _stream()),
+                 "gsr_sh_camera_position_grad")
+      d_cam = d_cam.to(ctx.in_dtypes[2])
     if go is not None:
-      return None, None, None, None, None, None, None
+      return None, None, None, d_cam, None, None, None
     return (d_sh.to(ctx.in_dtypes[0]), d_pos.to(ctx.in_dtypes[1]) if d_pos is not None else None,
-            None, None, None, None, None)
+            None, d_cam, None, None, None)
 
 
 def evaluate_sh_at(sh_features: torch.Tensor, positions: torch.Tensor, indexes: torch.Tensor,
@@ -150,7 +160,7 @@ def evaluate_sh_at(sh_features: torch.Tensor, positions: torch.Tensor, indexes: 
 
   colour_c = 0.5 + sum_k sh[idx, c, k] * Y_k(normalize(positions[idx] - camera_pos)), K in {1,4,9,16}
   (degrees 0..3, basis order k = n(n+1)+m as splat_trainer/scene/mlp/rsh.py).  Differentiable wrt
-  ``sh_features`` and, through the view direction, ``positions``; the caller clamps (transfer_sh.py:50).
+  ``sh_features`` and, through the view direction, ``positions`` and ``camera_pos``; the caller clamps (transfer_sh.py:50).
   ``grad_out=(d_sh, d_positions[, owner])``: optional fused accumulation, see ``renderer.GradOut`` (when
   ``owner.feature_uninitialized`` is set, ``d_sh`` is overwritten row for row instead of added to, and the flag is cleared)."""
   for t in (sh_features, positions, indexes, camera_pos):
@@ -160,5 +170,12 @@ def evaluate_sh_at(sh_features: torch.Tensor, positions: torch.Tensor, indexes: 
     raise ValueError(f"sh_features must be (N,3,K) with K in (1,4,9,16), got {tuple(sh_features.shape)}")
   if indexes.dtype != torch.int64:
     raise TypeError("indexes must be int64")
-  want_pos_grad = wants_position_grad(positions, grad_out)
+  cam_grad = torch.is_grad_enabled() and camera_pos.requires_grad
+  if cam_grad and isinstance(grad_out, ShFactorCollector):
+    raise ValueError("camera gradients are not supported in data-parallel mode (ShFactorCollector): detach the camera "
+                     "position, or evaluate on one device")
+  # the saved Jacobian also gives the camera position's gradient
+  want_pos_grad = wants_position_grad(positions, grad_out) or cam_grad
+  if cam_grad and _precomputed is not None and _precomputed[1] is None and sh_features.shape[2] > 1:
+    _precomputed = None                      # evaluated without the Jacobian: evaluate again with it
   return _SHFn.apply(sh_features, positions, indexes, camera_pos, grad_out, want_pos_grad, _precomputed)
