@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 32) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 33) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -606,6 +606,25 @@ int gsr_msloss_forward(const float* image, const float* target, int32_t H, int32
 int gsr_msloss_backward(const float* image, const float* target, int32_t H, int32_t W, int32_t C, int32_t levels,
                         float w_l1, float w_mse, float w_ssim, float lo, float hi, const float* grad_scale_dev,
                         void* workspace, size_t workspace_bytes, float* d_image, void* stream);
+
+/* ---- bilateral-grid colour correction (color_corrector/bilateral_corrector.py) ----------------------------- */
+/* grids [N, 12, L, GH, GW] float32 contiguous, one grid per image, 2 <= L, GH, GW <= 64; rgb, out, d_out, d_rgb
+ * [H, W, 3] float32 contiguous, 1 <= H, W <= GSR_BILAGRID_MAX_SIDE.  Image k samples grid k trilinearly at
+ * x = (j + 0.5) / W (GW - 1), y = (i + 0.5) / H (GH - 1), z = clamp(luma(rgb) (L - 1), 0, L - 1) (grid_sample,
+ * align_corners, border padding) and applies the sampled 3x4 affine to rgb.
+ * gsr_bilagrid_slice_backward writes d_rgb (NULL: skipped) and slice k of d_grids (NULL: skipped; the other slices are
+ * left alone); the grid gradient needs gsr_bilagrid_workspace_bytes of workspace.  gsr_bilagrid_tv writes
+ * tv_out[0] = weight * tv, tv = (1/N) sum_axes sum (G shifted - G)^2 / (12 L GH GW), and (d_grids not NULL) weight * dtv/dG,
+ * added to d_grids when accumulate != 0.  No float atomics: every result is bit-reproducible. */
+#define GSR_BILAGRID_MAX_SIDE 32768
+size_t gsr_bilagrid_workspace_bytes(int32_t L, int32_t GH, int32_t GW);
+int gsr_bilagrid_slice_forward(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, int64_t k,
+                               const float* rgb, int32_t H, int32_t W, float* out, void* stream);
+int gsr_bilagrid_slice_backward(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, int64_t k,
+                                const float* rgb, int32_t H, int32_t W, const float* d_out, float* d_rgb, float* d_grids,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int gsr_bilagrid_tv(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, float weight, float* tv_out,
+                    float* d_grids, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "gsr_math.h"
+#include "gsr_bilagrid.h"
 
 extern "C" {
 
@@ -91,6 +92,62 @@ void hm_tile_hits(const void* params, int64_t M, const float* g2d, int tiles_x, 
       for (int tx = e.x0; tx < e.x1; ++tx)
         if (gsr_tile_hit(g[0], g[1], g[2], g[3], g[4], e.qmax, tx, ty)) hits[m * nt + ty * tiles_x + tx] = 1;
   }
+}
+
+// bilateral-grid slice of one image (gsr_bilagrid.h) with ONE grid [12, L, GH, GW]: the cell's corner columns are gathered
+// per pixel into the cols[4][L][12] layout the kernels stage in LDS.
+static void hm_bg_cols(const float* grid, int L, int GH, int GW, int cx, int cy, float* cols) {
+  for (int q = 0; q < 4; ++q)
+    for (int l = 0; l < L; ++l)
+      for (int c = 0; c < GSR_BG_CH; ++c)
+        cols[(q * L + l) * GSR_BG_CH + c] = grid[((c * L + l) * GH + cy + (q >> 1)) * GW + cx + (q & 1)];
+}
+
+void hm_bilagrid_forward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, float* out) {
+  float cols[4 * 64 * GSR_BG_CH];
+  const float inv_2w = 1.f / (2.f * (float)W), inv_2h = 1.f / (2.f * (float)H);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < W; ++j) {
+      const int cx = gsr_bg_cell(j, W, GW), cy = gsr_bg_cell(i, H, GH);
+      hm_bg_cols(grid, L, GH, GW, cx, cy, cols);
+      const float* p = rgb + 3 * ((int64_t)i * W + j);
+      gsr_bg_pixel_fwd(cols, L, gsr_bg_frac(j, cx, W, GW, inv_2w), gsr_bg_frac(i, cy, H, GH, inv_2h), p[0], p[1], p[2],
+                       out + 3 * ((int64_t)i * W + j));
+    }
+}
+
+// d_rgb [H, W, 3] and d_grid [12, L, GH, GW] (summed in double, overwritten)
+void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, const float* d_out,
+                          float* d_rgb, float* d_grid) {
+  float cols[4 * 64 * GSR_BG_CH];
+  const int n_grid = GSR_BG_CH * L * GH * GW;
+  double* acc = new double[n_grid]();
+  const float inv_2w = 1.f / (2.f * (float)W), inv_2h = 1.f / (2.f * (float)H);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < W; ++j) {
+      const int cx = gsr_bg_cell(j, W, GW), cy = gsr_bg_cell(i, H, GH);
+      hm_bg_cols(grid, L, GH, GW, cx, cy, cols);
+      const int64_t o = 3 * ((int64_t)i * W + j);
+      const float tx = gsr_bg_frac(j, cx, W, GW, inv_2w), ty = gsr_bg_frac(i, cy, H, GH, inv_2h);
+      const float* p = rgb + o;
+      gsr_bg_pixel_bwd_rgb(cols, L, tx, ty, p[0], p[1], p[2], d_out + o, d_rgb + o);
+      const GsrBgZ z = gsr_bg_z(gsr_bg_luma(p[0], p[1], p[2]), L);
+      float wxy[4];
+      gsr_bg_xy_weights(tx, ty, wxy);
+      for (int k = 0; k < 2; ++k) {
+        const float wz = k == 0 ? 1.f - z.tz : z.tz;
+        for (int q = 0; q < 4; ++q) {
+          const float w = wz * wxy[q];
+          for (int m = 0; m < 3; ++m) {
+            const float v[4] = {p[0], p[1], p[2], 1.f};
+            for (int n = 0; n < 4; ++n)
+              acc[(((4 * m + n) * L + z.z0 + k) * GH + cy + (q >> 1)) * GW + cx + (q & 1)] += w * (d_out[o + m] * v[n]);
+          }
+        }
+      }
+    }
+  for (int e = 0; e < n_grid; ++e) d_grid[e] = (float)acc[e];
+  delete[] acc;
 }
 
 }  // extern "C"

@@ -89,7 +89,7 @@ class MiniTrainer:
                config: Optional[RasterConfig] = None, lr: float = 1e-3, densify_every: int = 25,
                target_points: Optional[int] = None, prune_rate: float = 0.025, min_views: int = 5,
                max_scale_px: float = 200.0, total_steps: int = 100, seed: int = 0, optimizer=VisibilityAwareLaProp,
-               loss: str = "mse"):
+               loss: str = "mse", corrector=None):
     self.config = config or RasterConfig(compute_visibility=True, compute_point_heuristic=True)
     self.cameras, self.targets = list(cameras), list(targets)
     self.device = gaussians.position.device
@@ -110,6 +110,9 @@ class MiniTrainer:
     if loss not in ("mse", "ref"):
       raise ValueError("loss must be 'mse' (clamped MSE, SURVEY.md section 8d) or 'ref' (the reference's L1 + MSE + SSIM mix)")
     self.loss_kind = loss
+    # bilateral.BilateralCorrector (or anything with correct(rendering, image_idx) and step(t)): the loss is taken on
+    # corrector.correct(r, camera index), and corrector.step(t) follows the optimizer step
+    self.corrector = corrector
 
   @property
   def num_points(self) -> int:
@@ -165,15 +168,16 @@ class MiniTrainer:
     fused = self.device.type == "cuda"
     grad_out = self._grad_target() if fused else None
     total = torch.zeros((), dtype=torch.float32, device=self.device)
-    for cam, target in zip(self.cameras, self.targets):
+    for camera_index, (cam, target) in enumerate(zip(self.cameras, self.targets)):
       with torch.enable_grad():
         r = render_gaussians(self.scene(), cam, self.config, use_sh=True, grad_out=grad_out)
         if r.points.idx.shape[0] == 0:
           raise RuntimeError("No visible points")                     # trainer.py:507-509
+        image = r.image if self.corrector is None else self.corrector.correct(r, camera_index)
         if self.loss_kind == "ref":
-          loss = reference_loss(r.image, target)                      # trainer.py:448-488: L1 + MSE + multi-scale SSIM
+          loss = reference_loss(image, target)                        # trainer.py:448-488: L1 + MSE + multi-scale SSIM
         else:
-          loss = clamped_mse_loss(r.image, target) if fused else F.mse_loss(r.image.clamp(0, 1), target)
+          loss = clamped_mse_loss(image, target) if fused else F.mse_loss(image.clamp(0, 1), target)
         loss.backward()
       with torch.no_grad():
         # point_state.py:34-50 (camera order) and mlp_scene.py:244 (visible[idx] += visibility) in one launch
@@ -182,6 +186,8 @@ class MiniTrainer:
     if grad_out is not None:
       grad_out.finish_batch()               # (a buffer no backward pass reached would be zero-filled here; none with >= 1 camera)
     self.optimizer_step()
+    if self.corrector is not None:
+      self.corrector.step(self.step_idx / self.total_steps)
     self.step_idx += 1
     self.log.losses.append(float(total.item()) / len(self.cameras))
     self.log.num_points.append(self.num_points)
