@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 33) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 34) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -625,6 +625,28 @@ int gsr_bilagrid_slice_backward(const float* grids, int64_t N, int32_t L, int32_
                                 void* workspace, size_t workspace_bytes, void* stream);
 int gsr_bilagrid_tv(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, float weight, float* tv_out,
                     float* d_grids, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- neighbour searches over 3-D points (gaussians/loading.py estimate_scale, visibility/cluster.py k-means) ------
+ * points / x [N, 3] and centroids [K, 3] float32 contiguous, 1 <= N, K <= GSR_NEIGHBOURS_MAX_N.  Squared distance
+ * d = fmaf(dz, dz, fmaf(dy, dy, dx * dx)), dx = q.x - c.x, ...  Brute force (every pair), no float atomics: every result
+ * is bit-reproducible.
+ * gsr_knn: for each i the k (1 <= k <= GSR_KNN_MAX_K, N >= k + 1) smallest distances over j != i, ascending, equal
+ *   distances by lower j: dist2_out [N, k], idx_out [N, k] int64; scale_out [N] (may be NULL) = the mean of sqrt(dist2)
+ *   over the k, summed in ascending order.  NaN distances never enter a list.  Workspace: gsr_knn_workspace_bytes.
+ * gsr_assign_clusters: labels_out [N] int64 = argmin_j d(x_i, c_j), ties to the lowest j, all-NaN distances to 0.
+ * gsr_kmeans_iter: `iters` (>= 1) Lloyd iterations enqueued at once: assign, then every centroid with at least one point
+ *   becomes the float32 mean of its points (sums in a fixed order; an empty cluster keeps its centroid).  centroids is
+ *   updated in place; labels_out receives the LAST assignment, made before the last update.  Workspace:
+ *   gsr_kmeans_workspace_bytes. */
+#define GSR_KNN_MAX_K 16
+#define GSR_NEIGHBOURS_MAX_N 0x7FFFFFFF
+size_t gsr_knn_workspace_bytes(int64_t N, int32_t k);
+int gsr_knn(const float* points, int64_t N, int32_t k, float* dist2_out, int64_t* idx_out, float* scale_out,
+            void* workspace, size_t workspace_bytes, void* stream);
+int gsr_assign_clusters(const float* x, int64_t N, const float* centroids, int64_t K, int64_t* labels_out, void* stream);
+size_t gsr_kmeans_workspace_bytes(int64_t N, int64_t K);
+int gsr_kmeans_iter(const float* x, int64_t N, float* centroids, int64_t K, int32_t iters, int64_t* labels_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the

@@ -11,10 +11,12 @@ from .loss import clamped_l1_loss, clamped_mse_loss, fused_ssim, reference_loss
 from ._lib import GsplatHipError
 from .bilateral import (BilateralCorrector, BilateralCorrectorConfig, BilateralGrid, bilateral_correct,
                         bilateral_tv_loss)
+from .neighbours import assign_clusters, estimate_scale, kmeans, kmeans_iter, knn
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
            "frustum_cull", "project_to_image", "render_projected", "render_gaussians", "evaluate_sh_at",
            "GsplatHipError", "GradOut", "fused_ssim", "clamped_mse_loss", "clamped_l1_loss", "reference_loss", "ShFactorCollector", "TaichiQueue", "count_nonfinite",
            "check_finite", "random_camera", "random_3d_gaussians", "BilateralCorrector", "BilateralCorrectorConfig",
-           "BilateralGrid", "bilateral_correct", "bilateral_tv_loss"]
+           "BilateralGrid", "bilateral_correct", "bilateral_tv_loss", "knn", "estimate_scale", "assign_clusters",
+           "kmeans_iter", "kmeans"]

@@ -14,11 +14,13 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GSPLAT_HIP_LIB: load another build of the same library (kernel experiments, tools/k67_bench.py); never a fallback
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
 MAX_FEATURES = 16                  # GSR_MAX_FEATURES
 WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
 BILAGRID_MAX_SIDE = 32768          # GSR_BILAGRID_MAX_SIDE
+KNN_MAX_K = 16                     # GSR_KNN_MAX_K
+NEIGHBOURS_MAX_N = 0x7FFFFFFF      # GSR_NEIGHBOURS_MAX_N
 
 
 class GsrRasterParamsC(C.Structure):
@@ -186,6 +188,11 @@ PROTOTYPES = {
     "gsr_bilagrid_slice_forward": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i64, _p, _i32, _i32, _p, _p]),
     "gsr_bilagrid_slice_backward": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i64, _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "gsr_bilagrid_tv": (C.c_int, [_p, _i64, _i32, _i32, _i32, _f, _p, _p, _i32, _p, _sz, _p]),
+    "gsr_knn_workspace_bytes": (_sz, [_i64, _i32]),
+    "gsr_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
+    "gsr_assign_clusters": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
+    "gsr_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
+    "gsr_kmeans_iter": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
 }
 
 _lib = None

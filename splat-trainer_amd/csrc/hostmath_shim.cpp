@@ -6,6 +6,7 @@
 
 #include "gsr_math.h"
 #include "gsr_bilagrid.h"
+#include "gsr_neighbours.h"
 
 extern "C" {
 
@@ -148,6 +149,62 @@ void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float*
     }
   for (int e = 0; e < n_grid; ++e) d_grid[e] = (float)acc[e];
   delete[] acc;
+}
+
+
+// brute-force kNN and nearest-centroid assignment (gsr_neighbours.h), one sweep over j = 0 .. N-1 per query: the
+// device's results bit for bit.  Rows [i0, i1) of dist2 [N, k], idx [N, k] int64 and scale [N], written from row 0 of
+// the outputs; returns -1 for k outside 1..16, N <= k or a bad row range.
+}  // extern "C"
+
+template <int K>
+static void hm_knn_k(const float* p, int64_t N, int64_t i0, int64_t i1, float* dist2, int64_t* idx, float* scale) {
+  for (int64_t i = i0; i < i1; ++i) {
+    float d[K];
+    int32_t j[K];
+    gsr_nb_init(d, j);
+    for (int64_t c = 0; c < N; ++c)
+      if (c != i) gsr_nb_insert(d, j, gsr_nb_dist2(p[3 * i], p[3 * i + 1], p[3 * i + 2], p[3 * c], p[3 * c + 1], p[3 * c + 2]),
+                                (int32_t)c);
+    for (int t = 0; t < K; ++t) { dist2[(i - i0) * K + t] = d[t]; idx[(i - i0) * K + t] = j[t]; }
+    scale[i - i0] = gsr_nb_mean_dist(d);
+  }
+}
+
+extern "C" {
+
+int hm_knn(const float* p, int64_t N, int k, int64_t i0, int64_t i1, float* dist2, int64_t* idx, float* scale) {
+  if (k < 1 || k > 16 || N <= k || i0 < 0 || i1 > N || i0 > i1) return -1;
+  switch (k) {
+    case 1: hm_knn_k<1>(p, N, i0, i1, dist2, idx, scale); break;
+    case 2: hm_knn_k<2>(p, N, i0, i1, dist2, idx, scale); break;
+    case 3: hm_knn_k<3>(p, N, i0, i1, dist2, idx, scale); break;
+    case 4: hm_knn_k<4>(p, N, i0, i1, dist2, idx, scale); break;
+    case 5: hm_knn_k<5>(p, N, i0, i1, dist2, idx, scale); break;
+    case 6: hm_knn_k<6>(p, N, i0, i1, dist2, idx, scale); break;
+    case 7: hm_knn_k<7>(p, N, i0, i1, dist2, idx, scale); break;
+    case 8: hm_knn_k<8>(p, N, i0, i1, dist2, idx, scale); break;
+    case 9: hm_knn_k<9>(p, N, i0, i1, dist2, idx, scale); break;
+    case 10: hm_knn_k<10>(p, N, i0, i1, dist2, idx, scale); break;
+    case 11: hm_knn_k<11>(p, N, i0, i1, dist2, idx, scale); break;
+    case 12: hm_knn_k<12>(p, N, i0, i1, dist2, idx, scale); break;
+    case 13: hm_knn_k<13>(p, N, i0, i1, dist2, idx, scale); break;
+    case 14: hm_knn_k<14>(p, N, i0, i1, dist2, idx, scale); break;
+    case 15: hm_knn_k<15>(p, N, i0, i1, dist2, idx, scale); break;
+    default: hm_knn_k<16>(p, N, i0, i1, dist2, idx, scale); break;
+  }
+  return 0;
+}
+
+void hm_assign_clusters(const float* x, int64_t N, const float* c, int64_t K, int64_t* labels) {
+  for (int64_t i = 0; i < N; ++i) {
+    float best = INFINITY;
+    int32_t label = 0;
+    for (int64_t j = 0; j < K; ++j)
+      gsr_nb_argmin_step(best, label, gsr_nb_dist2(x[3 * i], x[3 * i + 1], x[3 * i + 2], c[3 * j], c[3 * j + 1], c[3 * j + 2]),
+                         (int32_t)j);
+    labels[i] = label;
+  }
 }
 
 }  // extern "C"
