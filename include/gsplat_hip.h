@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 34) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 35) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -647,6 +647,45 @@ int gsr_assign_clusters(const float* x, int64_t N, const float* centroids, int64
 size_t gsr_kmeans_workspace_bytes(int64_t N, int64_t K);
 int gsr_kmeans_iter(const float* x, int64_t N, float* centroids, int64_t K, int32_t iters, int64_t* labels_out,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- neural colour model (scene/color_model.py ColorModel, scene/mlp/torch_mlp.py MLP / AffineMLP) ----------
+ * Per row: x = LayerNorm_F([point_features, glo]) (no affine, eps 1e-5); diffuse = lum(base(x), 0); d = normalize(
+ * position - cam_pos) (eps 1e-12); [a, b] = encode(rsh_S(d)); specular = lum(dir(x a + b), -2), lum(o, c)_k =
+ * sigmoid(o_{k+1}) exp(o_0 + c).  base and dir are GLU-MLPs (L hidden layers Linear(in, 2H) -> a sigmoid(b), then
+ * Linear(H, 4)).  Every Linear rounds its input and weight to f16 once and adds the fp32 bias to fp32 products.
+ * Parameters (fp32, row-major [out, in]) by index: 0 base.layers.0.m, 1 base.layers.1.m (L = 2), 2 base.layers.L,
+ * 3 directional_model.encode_dir.mlp.layers.0 [2F, (S+1)^2], 4 directional_model.mlp.layers.0.m, 5 ... .layers.1.m
+ * (L = 2), 6 directional_model.mlp.layers.L; unused entries NULL.  Supported: H = 32, L in {1, 2}, S in 2..5,
+ * 1 <= F = P + G <= 64, color_channels = 3 (anything else: GSR_ERR_UNSUPPORTED).
+ * point_features [M, P], positions [M, 3], diffuse_out / specular_out / d_diffuse / d_specular / d_point_features
+ * [M, 3] or [M, P]; cam_pos [3]; glo_feature [G]; all float32 contiguous.  Both calls first pack the parameters into
+ * the workspace (one launch), so they may change between calls.  gsr_color_backward recomputes the forward; d_diffuse
+ * or d_specular may be NULL (zero); it writes d_point_features and every gradient of `grads` (overwritten, not added);
+ * d_cam_pos NULL skips the camera path.  The workspace holds one gradient slot per workgroup, the grid depends on M
+ * only and there are no float atomics: every result is bit-reproducible. */
+typedef struct GsrColorModel {
+  int32_t P, G, H, L, S, color_channels;
+  const float* weight[7];
+  const float* bias[7];
+} GsrColorModel;
+typedef struct GsrColorGrads {
+  float* d_weight[7];
+  float* d_bias[7];
+  float* d_glo;       /* [G] */
+  float* d_cam_pos;   /* [3] or NULL */
+} GsrColorGrads;
+/* sizeof GsrColorModel (0), GsrColorGrads (1), -1 otherwise */
+int64_t gsr_color_struct_bytes(int32_t which);
+int gsr_color_supported(const GsrColorModel* model);
+size_t gsr_color_forward_workspace_bytes(const GsrColorModel* model);
+size_t gsr_color_backward_workspace_bytes(const GsrColorModel* model, int64_t M);
+int gsr_color_forward(const GsrColorModel* model, const float* point_features, const float* positions,
+                      const float* cam_pos, const float* glo_feature, int64_t M, float* diffuse_out, float* specular_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gsr_color_backward(const GsrColorModel* model, const float* point_features, const float* positions,
+                       const float* cam_pos, const float* glo_feature, int64_t M, const float* d_diffuse,
+                       const float* d_specular, float* d_point_features, const GsrColorGrads* grads, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the

@@ -14,7 +14,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # GSPLAT_HIP_LIB: load another build of the same library (kernel experiments, tools/k67_bench.py); never a fallback
 LIB_PATH = os.environ.get("GSPLAT_HIP_LIB") or os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
 MAX_FEATURES = 16                  # GSR_MAX_FEATURES
 WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
@@ -87,6 +87,16 @@ class GsrColumnC(C.Structure):
 
 
 MAX_COLUMNS = 32
+
+
+class GsrColorModelC(C.Structure):
+  _fields_ = [("P", C.c_int32), ("G", C.c_int32), ("H", C.c_int32), ("L", C.c_int32), ("S", C.c_int32),
+              ("color_channels", C.c_int32), ("weight", C.c_void_p * 7), ("bias", C.c_void_p * 7)]
+
+
+class GsrColorGradsC(C.Structure):
+  _fields_ = [("d_weight", C.c_void_p * 7), ("d_bias", C.c_void_p * 7), ("d_glo", C.c_void_p),
+              ("d_cam_pos", C.c_void_p)]
 
 
 def raster_params(config) -> GsrRasterParamsC:
@@ -193,6 +203,13 @@ PROTOTYPES = {
     "gsr_assign_clusters": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
     "gsr_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
     "gsr_kmeans_iter": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
+    "gsr_color_struct_bytes": (_i64, [_i32]),
+    "gsr_color_supported": (C.c_int, [C.POINTER(GsrColorModelC)]),
+    "gsr_color_forward_workspace_bytes": (_sz, [C.POINTER(GsrColorModelC)]),
+    "gsr_color_backward_workspace_bytes": (_sz, [C.POINTER(GsrColorModelC), _i64]),
+    "gsr_color_forward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
+    "gsr_color_backward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p,
+                                     C.POINTER(GsrColorGradsC), _p, _sz, _p]),
 }
 
 _lib = None
@@ -242,6 +259,10 @@ def load() -> C.CDLL:
       if lib.gsr_struct_bytes(which) != C.sizeof(mirror):
         raise GsplatHipError(f"struct layout mismatch: {mirror.__name__} is {C.sizeof(mirror)} bytes in the binding, "
                              f"{lib.gsr_struct_bytes(which)} in the library; rebuild")
+    for which, mirror in enumerate((GsrColorModelC, GsrColorGradsC)):
+      if lib.gsr_color_struct_bytes(which) != C.sizeof(mirror):
+        raise GsplatHipError(f"struct layout mismatch: {mirror.__name__} is {C.sizeof(mirror)} bytes in the binding, "
+                             f"{lib.gsr_color_struct_bytes(which)} in the library; rebuild")
     _lib = lib
   return _lib
 

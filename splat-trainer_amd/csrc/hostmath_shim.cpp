@@ -7,6 +7,7 @@
 #include "gsr_math.h"
 #include "gsr_bilagrid.h"
 #include "gsr_neighbours.h"
+#include "gsr_color.h"
 
 extern "C" {
 
@@ -204,6 +205,87 @@ void hm_assign_clusters(const float* x, int64_t N, const float* c, int64_t K, in
       gsr_nb_argmin_step(best, label, gsr_nb_dist2(x[3 * i], x[3 * i + 1], x[3 * i + 2], c[3 * j], c[3 * j + 1], c[3 * j + 2]),
                          (int32_t)j);
     labels[i] = label;
+  }
+}
+
+}  // extern "C"
+
+// colour-model row maths (gsr_color.h), one row at a time: the SH basis and its vector-Jacobian product, LayerNorm,
+// GLU, the luminance activation and F.normalize, each with its derivative.
+template <int S>
+static void hm_cm_rsh_s(const float* d, int64_t n, float* out, const float* dsh, float* dd) {
+  const int K = (S + 1) * (S + 1);
+  for (int64_t i = 0; i < n; ++i) {
+    const float* v = d + 3 * i;
+    if (out) gsr_cm_rsh<S>(v[0], v[1], v[2], [&](int c, float y) { out[i * K + c] = y; });
+    if (dd) {
+      float g[3] = {0.f, 0.f, 0.f};
+      gsr_cm_rsh<S>(GsrDual3{v[0], 1.f, 0.f, 0.f}, GsrDual3{v[1], 0.f, 1.f, 0.f}, GsrDual3{v[2], 0.f, 0.f, 1.f},
+                    [&](int c, GsrDual3 y) {
+                      const float k = dsh[i * K + c];
+                      g[0] += k * y.dx; g[1] += k * y.dy; g[2] += k * y.dz;
+                    });
+      for (int k = 0; k < 3; ++k) dd[3 * i + k] = g[k];
+    }
+  }
+}
+
+extern "C" {
+
+// out [n, (S+1)^2] (NULL: skipped); dd [n, 3] = sum_c dsh[c] dY_c/dd (NULL: skipped).  Returns -1 for S outside 0..5.
+int hm_cm_rsh(int S, const float* d, int64_t n, float* out, const float* dsh, float* dd) {
+  switch (S) {
+    case 0: hm_cm_rsh_s<0>(d, n, out, dsh, dd); return 0;
+    case 1: hm_cm_rsh_s<1>(d, n, out, dsh, dd); return 0;
+    case 2: hm_cm_rsh_s<2>(d, n, out, dsh, dd); return 0;
+    case 3: hm_cm_rsh_s<3>(d, n, out, dsh, dd); return 0;
+    case 4: hm_cm_rsh_s<4>(d, n, out, dsh, dd); return 0;
+    case 5: hm_cm_rsh_s<5>(d, n, out, dsh, dd); return 0;
+    default: return -1;
+  }
+}
+
+// rows u [n, F]: y = LayerNorm(u) and du for an upstream dy
+void hm_cm_layernorm(const float* u, int64_t n, int F, const float* dy, float* y, float* du) {
+  for (int64_t i = 0; i < n; ++i) {
+    const float* r = u + i * F;
+    float sum = 0.f, ss = 0.f;
+    for (int f = 0; f < F; ++f) sum += r[f];
+    const float mean = sum / (float)F;
+    for (int f = 0; f < F; ++f) ss += (r[f] - mean) * (r[f] - mean);
+    const float rstd = gsr_cm_ln_rstd(ss, F);
+    float s1 = 0.f, s2 = 0.f;
+    for (int f = 0; f < F; ++f) {
+      y[i * F + f] = (r[f] - mean) * rstd;
+      s1 += dy[i * F + f];
+      s2 += dy[i * F + f] * y[i * F + f];
+    }
+    for (int f = 0; f < F; ++f) du[i * F + f] = gsr_cm_ln_bwd(y[i * F + f], dy[i * F + f], rstd, s1, s2, F);
+  }
+}
+
+void hm_cm_glu(const float* a, const float* b, const float* dh, int64_t n, float* h, float* da, float* db) {
+  for (int64_t i = 0; i < n; ++i) {
+    h[i] = gsr_cm_glu(a[i], b[i]);
+    gsr_cm_glu_bwd(a[i], b[i], dh[i], da[i], db[i]);
+  }
+}
+
+// o [n, 4] -> out [n, 3]; do_ [n, 4] for an upstream dout [n, 3]
+void hm_cm_lum(const float* o, int64_t n, float bias, const float* dout, float* out, float* do_) {
+  for (int64_t i = 0; i < n; ++i) {
+    gsr_cm_lum(o + 4 * i, bias, out + 3 * i);
+    gsr_cm_lum_bwd(o + 4 * i, bias, dout + 3 * i, do_ + 4 * i);
+  }
+}
+
+// v [n, 3] -> d = F.normalize(v) and dv for an upstream dd
+void hm_cm_normalize(const float* v, const float* dd, int64_t n, float* d, float* dv) {
+  for (int64_t i = 0; i < n; ++i) {
+    float inv;
+    bool clamped;
+    gsr_cm_normalize(v + 3 * i, d + 3 * i, inv, clamped);
+    gsr_cm_normalize_bwd(d + 3 * i, inv, clamped, dd + 3 * i, dv + 3 * i);
   }
 }
 
