@@ -19,8 +19,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 HOSTMATH_PATH = os.path.join(PKG_DIR, "libgsr_hostmath.so")
 HIP_SOURCES = ["prims.hip", "geometry.hip", "binning.hip", "composite.hip", "frame.hip", "ssim.hip", "optim.hip", "densify.hip",
                "bilagrid.hip", "neighbours.hip", "color_model.hip"]
-HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_k7_windows.inc", "composite_k7_xflex.inc",
-           "composite_wide.inc",
+HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_wide.inc",
            os.path.join("..", "..", "include", "gsplat_hip.h")]
 
 
@@ -38,18 +37,17 @@ def _hipcc() -> str:
   return exe
 
 
-def build_hip(force: bool = False, verbose: bool = False, out: str = LIB_PATH, defines=(), flags=()) -> str:
-  """``out`` / ``defines`` / ``flags``: experimental variants (``-DNAME[=v]``, raw compiler flags) built next to the product library."""
+def build_hip(force: bool = False, verbose: bool = False) -> str:
   srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
   deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
-  if not force and _newer(out, deps):
-    return out
+  if not force and _newer(LIB_PATH, deps):
+    return LIB_PATH
   cmd = [_hipcc(), "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
-         "-Wno-unused-value", "-o", out] + [f"-D{d}" for d in defines] + list(flags) + srcs
+         "-Wno-unused-value", "-o", LIB_PATH] + srcs
   if verbose:
     print(" ".join(cmd), flush=True)
   subprocess.run(cmd, check=True, cwd=CSRC)
-  return out
+  return LIB_PATH
 
 
 def build_hostmath(force: bool = False, verbose: bool = False) -> str:

@@ -49,26 +49,12 @@ struct __attribute__((packed, aligned(4))) Rank4 { uint32_t x, y, z, w; };
 //
 // eval_q2 / eval_qt / eval_G2 are shared by forward and backward and pin every rounding (explicit fma, contraction
 // off), so both passes take bit-identical contribute / skip decisions.
-// GSR_QT_FORM 1 forms q as d . t with t = conic d (the backward pass needs t anyway: two packed operations instead of
-// six there).  Measured (same box, c2 / c3): K7 374 / 724 us against 380 / 735, but K6 228 / 715 against 203 / 721 -- the
-// forward kernel goes from 79 to 83 SGPRs and loses more on the frame the headline is quoted on than the backward pass
-// gains; capping its SGPRs at 80 leaves it at 212 / 743.  Default: the direct quadratic form in both.
-#ifndef GSR_QT_FORM
-#define GSR_QT_FORM 0
-#endif
 __device__ __forceinline__ v2f eval_q2(v2f dx, float dy, float A, float B, float C) {
 #pragma clang fp contract(off)
-#if GSR_QT_FORM
-  const float bdy = B * dy, cdy = C * dy;
-  const v2f tx = __builtin_elementwise_fma(dx, GSR_V2(A), GSR_V2(bdy));
-  const v2f ty = __builtin_elementwise_fma(dx, GSR_V2(B), GSR_V2(cdy));
-  return __builtin_elementwise_fma(GSR_V2(dy), ty, dx * tx);
-#else
   // q = A dx^2 + 2B dx dy + C dy^2
   const float t = (B + B) * dy;
   const float u = (C * dy) * dy;
   return __builtin_elementwise_fma(dx * A, dx, __builtin_elementwise_fma(GSR_V2(t), dx, GSR_V2(u)));
-#endif
 }
 // ... and t = conic d = (A dx + B dy, B dx + C dy) next to it (backward: gradient of the mean, split score)
 __device__ __forceinline__ void eval_qt(v2f dx, float dy, float A, float B, float C, v2f& q, v2f& tx, v2f& ty) {
@@ -76,11 +62,7 @@ __device__ __forceinline__ void eval_qt(v2f dx, float dy, float A, float B, floa
   const float bdy = B * dy, cdy = C * dy;
   tx = __builtin_elementwise_fma(dx, GSR_V2(A), GSR_V2(bdy));
   ty = __builtin_elementwise_fma(dx, GSR_V2(B), GSR_V2(cdy));
-#if GSR_QT_FORM
-  q = __builtin_elementwise_fma(GSR_V2(dy), ty, dx * tx);
-#else
   q = eval_q2(dx, dy, A, B, C);
-#endif
 }
 __device__ __forceinline__ v2f eval_alpha2(v2f q, float l2op) {     // opacity exp(-q/2) = 2^(q * -0.5*log2(e) + log2 opacity)
 #pragma clang fp contract(off)
@@ -116,19 +98,6 @@ __device__ __forceinline__ Splat load_splat_packed(const float* __restrict__ rec
   s.f1 = 0.f; s.f2 = 0.f; s.depth = 0.f; s.l2op = 0.f;
   s.halves = packed >> 30;
   if (C > 1 || DEPTH) { const float4 r2 = r[2]; s.f1 = r2.x; s.f2 = r2.y; s.depth = r2.z; s.l2op = r2.w; }
-  return s;
-}
-
-// The backward walk's row: with GSR_K7_XFLEX also the x-extent of the splat's pixel box (row word 12).
-struct SplatB : Splat { uint32_t bx; };
-template <int C>
-__device__ __forceinline__ SplatB load_splat_bwd(const float* __restrict__ rec, uint32_t packed) {
-  SplatB s;
-  static_cast<Splat&>(s) = load_splat_packed<C, true>(rec, packed);
-  s.bx = 0u;
-#if GSR_K7_XFLEX
-  s.bx = __float_as_uint(rec[(size_t)GSR_ROW_FLOATS * (packed & 0x3FFFFFFFu) + 12]);
-#endif
   return s;
 }
 
@@ -223,9 +192,7 @@ struct FwdPix {
 // word one block later, the rows of the block after next -- by the time the scalar loads ask for them they sit in L2.
 // PF is chosen by the caller per frame: it pays once the row table has outgrown the caches (3M splats: K6 722 -> 656 us)
 // and costs a frame whose rows sit in L2 anyway (500k: 204 -> 226 us: two more SGPRs, one more loop branch).
-#ifndef GSR_K6_PREFETCH
-#define GSR_K6_PREFETCH 32
-#endif
+constexpr int GSR_K6_PREFETCH = 32;
 template <int C, bool PF>
 __device__ __forceinline__ void fwd_prefetch_init(FwdPix<C>& px, const uint32_t* __restrict__ sorted_rank,
                                                   uint32_t tile_start, uint32_t begin, uint32_t pf_end, int lane) {
@@ -399,10 +366,6 @@ __device__ __forceinline__ void seg_alpha_pass(uint32_t sidx, const float* __res
   out[0] = P2[0].x; out[64] = P2[0].y; out[128] = P2[1].x; out[192] = P2[1].y;
 }
 
-#ifdef GSR_K6_TRACE
-// Diagnostic build only (tools/k6_trace.py): every forward wave records when and where it ran.
-__device__ uint64_t* g_k6_trace = nullptr;      // [num_tiles, 4]: start, end (s_memrealtime), hardware ids, list length | block
-#endif
 template <int C, bool VIS, bool MEDIAN, bool PF>
 __global__ __launch_bounds__(64) void composite_fwd_kernel(const float* __restrict__ rec,
                                                            const uint32_t* __restrict__ sorted_rank,
@@ -438,9 +401,6 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(const float* __restri
   const int px0 = tx * 16 + (lane & 7), py0 = ty * 16 + (lane >> 3);
   const float fx0 = (float)px0 + 0.5f, fy0 = (float)py0 + 0.5f;
   const uint32_t start = tile_range[2 * tile], end = tile_range[2 * tile + 1];
-#ifdef GSR_K6_TRACE
-  const uint64_t trace_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
   FwdPix<C> px;
   fwd_init<C>(px, px0, py0, W, H);
@@ -485,15 +445,6 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(const float* __restri
       if (MEDIAN) median[pix] = (p & 1) ? px.med2[h].y : px.med2[h].x;
     }
   }
-#ifdef GSR_K6_TRACE
-  if (g_k6_trace && lane == 0) {
-    uint64_t* t = g_k6_trace + 4 * (size_t)tile;
-    t[0] = trace_t0; t[1] = __builtin_amdgcn_s_memrealtime();
-    t[2] = (uint64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |            // HW_REG_HW_ID
-           ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);    // HW_REG_XCC_ID
-    t[3] = (uint64_t)(end - start) | ((uint64_t)blockIdx.x << 32);
-  }
-#endif
 }
 
 // Pass C of a heavy tile: the forward walk over one segment, entered with T_in = product of the preceding segments'
@@ -595,27 +546,8 @@ __global__ __launch_bounds__(64) void seg_combine_kernel(int W, int H, int tiles
   }
 }
 
-#ifndef GSR_K7_WAVES
-#define GSR_K7_WAVES 6
-#endif
-#ifndef GSR_K7_SEGMAP             // segment block -> segment: 0 identity, 1 contiguous range per XCD, 2 grouped
-#define GSR_K7_SEGMAP 2
-#endif
-#ifndef GSR_K7_SEG_GROUP_LOG2
-#define GSR_K7_SEG_GROUP_LOG2 5
-#endif
-#ifndef GSR_K7_UNCOND_PREFETCH   // measured: K7 -1.5 % at 500k splats, +2.5 % at 3M (the chunk ends' re-reads): off
-#define GSR_K7_UNCOND_PREFETCH 0
-#endif
-#ifndef GSR_K7_SEG_FIRST
-#define GSR_K7_SEG_FIRST 1
-#endif
-#ifndef GSR_K7_XFLEX             // narrow footprints: one 8-pixel-wide window per tile half instead of the packed half (see the walk)
-#define GSR_K7_XFLEX 0
-#endif
-#ifndef GSR_K7_ADDTID            // per-pair sums parked with ds_write_addtid_b32 (see the reduction)
-#define GSR_K7_ADDTID 1
-#endif
+constexpr int GSR_K7_WAVES = 6;
+constexpr int GSR_K7_SEG_GROUP_LOG2 = 5;
 template <int C>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES, GSR_K7_WAVES))) void composite_bwd_kernel(const float* __restrict__ rec,
                                                            const uint32_t* __restrict__ sorted_rank,
@@ -633,34 +565,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
   // the launch -- one segment of a longer tile, entered with that segment's own end state from the forward pass.
   int tile, lo = 0, seg_hi = 0x7fffffff;
   uint32_t sidx = 0u;
-#if GSR_K7_SEG_FIRST
   // segments (the longest work units) first, then the unsegmented tiles longest class first: the launch has several
   // times more blocks than the chip has slots, the dispatcher hands them out in index order, so what starts last -- and
   // sets the length of the launch's tail -- should be the shortest units
   const bool is_seg = blockIdx.x < seg_blocks;
   if (is_seg) {
-    sidx = blockIdx.x;
-#else
-  const bool is_seg = (int)blockIdx.x >= num_tiles;
-  if (is_seg) {
-    sidx = blockIdx.x - (uint32_t)num_tiles;
-#endif
-#if GSR_K7_SEGMAP == 2
-    sidx = gsr_xcd_group_remap(sidx, GSR_K7_SEG_GROUP_LOG2);     // a tile's segments share an XCD (and its L2)
+    sidx = gsr_xcd_group_remap(blockIdx.x, GSR_K7_SEG_GROUP_LOG2);     // a tile's segments share an XCD (and its L2)
     if (sidx >= min(seg.seg_total[0], seg_capacity)) return;     // (the grid is rounded up past the tables' capacity)
-#elif GSR_K7_SEGMAP == 1
-    if (sidx >= seg.seg_total[0]) return;
-    sidx = (uint32_t)gsr_xcd_remap((int)sidx, (int)seg.seg_total[0]);
-#else
-    if (sidx >= seg.seg_total[0]) return;
-#endif
     const uint32_t* d = seg.seg_desc + 4 * (size_t)sidx;
     tile = (int)d[0];
     const uint32_t tstart = tile_range[2 * tile];
     lo = (int)(d[1] - tstart);
     seg_hi = (int)(d[2] - tstart);
   } else {
-#if GSR_K7_SEG_FIRST
     const uint32_t b = blockIdx.x - seg_blocks;                       // (seg_blocks is a multiple of 8: same XCD)
     if (seg.tile_order) {
       tile = ordered_tile(seg, num_tiles, b, (int)threadIdx.x);
@@ -669,9 +586,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
       if ((int)b >= num_tiles) return;
       tile = gsr_xcd_remap((int)b, num_tiles);
     }
-#else
-    tile = gsr_xcd_remap((int)blockIdx.x, num_tiles);
-#endif
     if (seg.tile_seg && seg.tile_seg[2 * tile + 1] != 0u) return;     // segmented tile: its segment blocks handle it
   }
   const int lane = (int)threadIdx.x;
@@ -679,9 +593,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
   const int px0 = tx * 16 + (lane & 7), py0 = ty * 16 + (lane >> 3);
   const float fx0 = (float)px0 + 0.5f, fy0 = (float)py0 + 0.5f;
   const uint32_t start = tile_range[2 * tile];
-#if GSR_K7_XFLEX
-  const int lx8 = lane & 7, tile_px0 = tx * 16;
-#endif
 
   // per pixel (packed over the two sides of a half): T behind the current splat, g = dL/dC,
   // ga = g . (colour accumulated behind the current splat)
@@ -727,12 +638,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
   const int hi = min(tile_last, seg_hi);
   if (hi <= lo) return;
   __shared__ float red[12 * 80];
-#if GSR_K7_ADDTID
   const int rslot = lane < 44 ? (lane >> 2) * 68 + (lane & 3) * 16 : 0;   // reader 4k+p: quarter p of value k (68-word rows)
-#else
-  const int wslot = (lane >> 4) * 20 + (lane & 15);                  // my cell inside a value's 80-word row
-  const int rslot = lane < 48 ? (lane >> 2) * 80 + (lane & 3) * 20 : 0;   // reader 4k+p: quarter p of value k
-#endif
 
   for (int cbase = lo + (((hi - lo - 1) >> 6) << 6); cbase >= lo; cbase -= 64) {
     const int n = min(64, hi - cbase);
@@ -746,27 +652,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
     uint64_t flags = __ballot(pv > 0.f);
     if (flags == 0ull) continue;
     int j = 63 - __builtin_clzll(flags);
-    SplatB nxt = load_splat_bwd<C>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
+    Splat nxt = load_splat_packed<C, true>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
     uint32_t inst_nxt = (uint32_t)__builtin_amdgcn_readlane(my_inst, j);
     while (true) {
-      const SplatB s = nxt;
+      const Splat s = nxt;
       const uint32_t inst_j = inst_nxt;
       const int pos = cbase + j;
       flags &= ~(1ull << j);
       const bool more = flags != 0ull;
-#if GSR_K7_UNCOND_PREFETCH
-      // prefetch the next contributing pair -- unconditionally (the chunk's last pair re-reads its own row), so that
-      // `nxt` is always a fresh value: no copy of the row from "next" to "current" registers per pair
-      j = more ? 63 - __builtin_clzll(flags) : j;
-      nxt = load_splat_bwd<C>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
-      inst_nxt = (uint32_t)__builtin_amdgcn_readlane(my_inst, j);
-#else
       if (more) {                                             // prefetch the next contributing pair
         j = 63 - __builtin_clzll(flags);
-        nxt = load_splat_bwd<C>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
+        nxt = load_splat_packed<C, true>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
         inst_nxt = (uint32_t)__builtin_amdgcn_readlane(my_inst, j);
       }
-#endif
       const v2f dx2 = (v2f){fx0, fx0 + 8.f} - GSR_V2(s.u);      // (one rounding per pixel: fwd_walk's)
       // Per pair and pixel the geometry gradient enters through ONE scalar, GdG = G dL/dG; what is accumulated are its
       // moments about the splat's mean, sum GdG {dx, dy, dx^2, dx dy, dy^2} -- fewer packed operations per half than
@@ -775,24 +673,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
       // dopacity = m0 / opacity (m0 = sum GdG, the zeroth moment).
       v2f mx2 = GSR_V2(0.f), my2 = mx2, mxx2 = mx2, mxy2 = mx2, myy2 = mx2, dop2 = mx2, prune2 = mx2, split2 = mx2;
       v2f df2[3] = {mx2, mx2, mx2};
-#if GSR_K7_XFLEX
-      // A footprint at most 8 pixels wide inside this tile (wave-uniform, from the row's pixel box) is evaluated on ONE
-      // 8-wide window per tile half instead of the half's 16 columns: lane (lx, ly) takes the column of [a, a + 8)
-      // congruent to lx -- its left-quadrant pixel where lx >= a, its right-quadrant one otherwise -- in plain fp32, the
-      // pixel's state picked out of (and put back into) the halves of the packed register pairs by a per-lane select.
-      const int bx0 = max((int)(int16_t)(s.bx & 0xFFFFu) - tile_px0, 0), bx1 = min(((int)s.bx >> 16) - tile_px0, 15);
-      const bool narrow = bx1 - bx0 < 8;
-      const int xa = min(bx0, 8);
-      const bool sel = lx8 < xa;                                 // this lane's pixel of the window is its right-quadrant one
-      const float dxs = (sel ? fx0 + 8.f : fx0) - s.u;
-#endif
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         if (!(s.halves & (1u << h))) continue;                            // scalar test: support misses this half
         const float dy = (h ? fy0 + 8.f : fy0) - s.v;
-#if GSR_K7_XFLEX
-#include "composite_k7_xflex.inc"
-#endif
         v2f q, tx_, ty_;
         eval_qt(dx2, dy, s.A, s.B, s.C, q, tx_, ty_);
         const bool hit0 = pos < lastc[2 * h] && q.x <= s.qlim;       // the forward walk's test (see fwd_walk)
@@ -844,12 +728,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
       // barrier): every lane parks its 11 values, value-major, then lane 4k+p adds quarter p (16 lanes) of value k with
       // packed adds and two quad DPP steps finish it -- 8 packed adds + 3 scalar ops on the VALU instead of 9 permlane
       // swaps + 9 adds + 12 DPP steps of the register-only transposing tree (the VALU is the binding unit here, the LDS
-      // pipe is idle otherwise).  Rows are padded (16 -> 20 words per quarter, 80 per value) so that the 128-bit reads
-      // of 8 consecutive lanes fall into 32 distinct banks.  Fixed association order => bit-reproducible.
+      // pipe is idle otherwise).  Each value has a row of 68 words: its 64 lanes' cells, parked by lane id with
+      // ds_write_addtid_b32 (no per-lane address register, the rows at 16-bit immediate offsets), plus 4 words of padding
+      // so that the 16-byte reads are conflict-free.  (`red` still has the size of an earlier 80-word row layout.)
+      // Fixed association order => bit-reproducible.
       {
-#if GSR_K7_ADDTID
-        // value rows of 64 lanes (+4 words: conflict-free 16-byte reads), parked by lane id -- no address register, 16-bit
-        // offsets (the two-address form above needs three extra address adds per pair), half the store-path cycles
         asm volatile("s_mov_b32 m0, %11\n"
                      "s_nop 0\n"                                  /* hazard: SALU write of M0 -> LDS add-TID needs a wait state */
                      "ds_write_addtid_b32 %0 offset:0\n"
@@ -865,11 +748,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
                      "ds_write_addtid_b32 %10 offset:2720\n"
                      :: "v"(du), "v"(dv), "v"(dA), "v"(dB), "v"(dC), "v"(dop), "v"(prune), "v"(split), "v"(df[0]), "v"(df[1]),
                         "v"(df[2]), "s"((uint32_t)(uintptr_t)red) : "memory");
-#else
-        float* wr = red + wslot;
-        wr[0 * 80] = du; wr[1 * 80] = dv; wr[2 * 80] = dA; wr[3 * 80] = dB; wr[4 * 80] = dC; wr[5 * 80] = dop;
-        wr[6 * 80] = prune; wr[7 * 80] = split; wr[8 * 80] = df[0]; wr[9 * 80] = df[1]; wr[10 * 80] = df[2];
-#endif
         gsr_wave_lds_fence();                                  // parks above are visible to the reader lanes below
         const float4* rd = reinterpret_cast<const float4*>(red + rslot);
         const float4 a = rd[0], b = rd[1], c = rd[2], d = rd[3];
@@ -888,15 +766,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
     }
   }
 }
-
-// K7 with flexible 64-pixel windows and the tile's pixel state in LDS: measured and rejected, lives in
-// composite_k7_windows.inc and is compiled only for the variant build that reproduces the numbers on file.
-#ifndef GSR_K7_WINDOWS
-#define GSR_K7_WINDOWS 0
-#endif
-#if GSR_K7_WINDOWS
-#include "composite_k7_windows.inc"
-#endif
 
 // Plans the frame, one thread per tile.  A tile longer than `seg_pairs` is cut into segments (the last one shorter),
 // numbered consecutively from a slot range the tile reserves with one integer atomic on the (zero-initialised) segment
@@ -1040,12 +909,6 @@ inline bool seg_ok(const GsrSegmentsC* sg, bool median) {
 
 extern "C" {
 
-#ifdef GSR_K6_TRACE
-int gsr_debug_set_k6_trace(uint64_t* buffer) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_k6_trace), &buffer, sizeof(buffer)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 int gsr_segment_thresholds(int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int64_t O, int32_t num_tiles, int32_t needs_grad,
                            int32_t* seg_pairs_out, int32_t* heavy_min_out) {
   if (!seg_pairs_out || !heavy_min_out || num_tiles <= 0) return GSR_ERR_INVALID_ARGUMENT;
@@ -1181,13 +1044,6 @@ int gsr_composite_backward(const float* rec, const uint32_t* sorted_rank, const 
   const uint32_t seg_blocks = segments_host ? (uint32_t)((segments_host->capacity + seg_round - 1) / seg_round * seg_round) : 0u;
   const uint32_t seg_cap = (uint32_t)(segments_host ? segments_host->capacity : 0);
   const int grid = 8 * gsr_tile_band_stride(nt) + (int)seg_blocks;
-#if GSR_K7_WINDOWS
-  if (C == 1) composite_bwd_win_kernel<1><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
-  else if (C == 2) composite_bwd_win_kernel<2><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
-  else composite_bwd_win_kernel<3><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
-  GSR_CHECK_LAUNCH();
-  return GSR_OK;
-#endif
   if (C == 1) composite_bwd_kernel<1><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
   else if (C == 2) composite_bwd_kernel<2><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
   else composite_bwd_kernel<3><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);

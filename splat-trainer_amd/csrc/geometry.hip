@@ -95,23 +95,6 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const float* __restric
   if (depth_keys) depth_keys[m] = gsr_depth_key(o.depth, key_bias, key_max);
 }
 
-// The depth sort's keys straight from the positions (12 bytes per visible splat): lets the sort start right behind the cull,
-// on a second stream, while the fused K2 + K3 kernel streams the coefficient rows on the first.  Same depth bits as the
-// projection writes into the rows (gsr_to_camera: formed in double, rounded once).
-__global__ __launch_bounds__(256) void depth_keys_pos_kernel(const float* __restrict__ pos, const int64_t* __restrict__ idx,
-                                                             int64_t M, const uint32_t* __restrict__ count_dev,
-                                                             const float* __restrict__ Tcw, const float* __restrict__ proj,
-                                                             uint32_t* __restrict__ keys, uint32_t key_bias,
-                                                             uint32_t key_max) {
-  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= M || (count_dev != nullptr && m >= (int64_t)*count_dev)) return;
-  const GsrCam cam = gsr_load_cam(Tcw, proj);
-  const int64_t i = idx[m];
-  float x, y, z;
-  gsr_to_camera(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], x, y, z);
-  keys[m] = gsr_depth_key(z, key_bias, key_max);
-}
-
 // ---- camera gradient: deterministic, no float atomics.  Kernels of their own, launched after the unchanged parameter
 // backward (forming the camera terms inside it changes where fp contraction fuses its products: the parameter gradients
 // would differ in the last bit from a run without camera gradient).  Every lane of a 256-thread block holds its splat's
@@ -382,9 +365,6 @@ __device__ __forceinline__ float2 gsr_screen_scale(float A, float B, float C) {
 // instruction covers whole 64-byte lines instead of 64 different ones) and each thread then takes its own row out of
 // LDS.  Odd row pitch (3K or 3K + 1 words): conflict-free 4-byte LDS accesses, and at degree 3 three blocks (48 waves'
 // worth of rows would not fit with a 16-byte aligned pitch) share a CU's 160 KB.
-#ifndef GSR_PSF_STAGE_OUT
-#define GSR_PSF_STAGE_OUT 1
-#endif
 template <int K>
 struct ShStage {
   static constexpr int ROW = 3 * K;
@@ -400,7 +380,7 @@ __global__ __launch_bounds__(256) void project_sh_fwd_kernel(
     GsrRasterParams rp, float* __restrict__ rows, float* __restrict__ sscale, float* __restrict__ jac,
     const uint32_t* __restrict__ count_dev, uint32_t* __restrict__ depth_keys, uint32_t key_bias, uint32_t key_max) {
   constexpr int ROW = ShStage<K>::ROW, PITCH = ShStage<K>::PITCH;
-  constexpr int OUT_FLOATS = GSR_PSF_STAGE_OUT ? 256 * (GSR_ROW_FLOATS + 1 + 9) : 0;     // rows + Jacobians on the way out
+  constexpr int OUT_FLOATS = 256 * (GSR_ROW_FLOATS + 1 + 9);     // rows + Jacobians on the way out
   constexpr int STAGE_FLOATS = 256 * PITCH > OUT_FLOATS ? 256 * PITCH : OUT_FLOATS;
   __shared__ float s_rows[STAGE_FLOATS];
   __shared__ int32_t s_idx[256];
@@ -452,7 +432,6 @@ __global__ __launch_bounds__(256) void project_sh_fwd_kernel(
     for (int k = 0; k < K; ++k) w[ch][k] = mine[ch * K + k];
   float col[3], J[9];
   gsr_sh_colour_w<K, JAC>(w, p[0] - cam_pos[0], p[1] - cam_pos[1], p[2] - cam_pos[2], col, J);
-#if GSR_PSF_STAGE_OUT
   // The rows and the Jacobians leave through LDS as well: the block's 256 x 64 B (and 256 x 36 B) are contiguous in
   // memory, so the staged copy goes out with fully coalesced 16-byte stores (whole lines per wave instruction) instead
   // of four (nine) stores per thread at a 64-byte (36-byte) stride.
@@ -488,21 +467,6 @@ __global__ __launch_bounds__(256) void project_sh_fwd_kernel(
     float* jout = jac + 9 * m0;
     for (int e = tid; e < nrows * 9; e += 256) jout[e] = s_jac[e];
   }
-#else
-  if (!valid) return;
-  float4* r = reinterpret_cast<float4*>(rows + (int64_t)GSR_ROW_FLOATS * m);
-  r[0] = make_float4(o.u, o.v, o.A, o.B);
-  r[1] = make_float4(o.C, o.opacity, gsr_qlim(o.opacity, rp), col[0]);
-  r[2] = make_float4(col[1], col[2], o.depth, log2f(o.opacity));
-  const float2 bb = gsr_pixel_bbox(o.u, o.v, o.A, o.B, o.C, o.opacity, rp);
-  r[3] = make_float4(bb.x, bb.y, 0.f, 0.f);
-  *reinterpret_cast<float2*>(sscale + 2 * m) = gsr_screen_scale(o.A, o.B, o.C);
-  if (depth_keys) depth_keys[m] = gsr_depth_key(o.depth, key_bias, key_max);
-  if (JAC) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) jac[9 * m + e] = J[e];
-  }
-#endif
 }
 
 // The (M,6) + (M,) + (M,C) tensors of the three-call form packed into the same rows (render_projected takes them from the
@@ -944,7 +908,7 @@ inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 
 
 extern "C" {
 
-int gsr_abi_version(void) { return 35; }
+int gsr_abi_version(void) { return 36; }
 
 const char* gsr_error_string(int code) {
   switch (code) {
@@ -1084,19 +1048,6 @@ int gsr_sh_camera_position_grad(const float* dL_dcolors, const float* jacobian, 
   }
   return gsr_camera_grad_finish(camera_partials, live ? gsr_camera_grad_partial_rows(M) : 0, nullptr, d_camera_pos,
                                 stream_);
-}
-
-int gsr_depth_keys_from_positions(const float* position, const int64_t* indexes, int64_t M, const uint32_t* count_dev,
-                                  const float* T_camera_world, const float* projection, uint32_t depth_key_bias,
-                                  uint32_t depth_key_max, uint32_t* keys_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
-  if (M == 0) return GSR_OK;
-  if (!position || !indexes || !T_camera_world || !projection || !keys_out) return GSR_ERR_INVALID_ARGUMENT;
-  depth_keys_pos_kernel<<<grid_for(M, 256), 256, 0, stream>>>(position, indexes, M, count_dev, T_camera_world, projection,
-                                                             keys_out, depth_key_bias, depth_key_max);
-  GSR_CHECK_LAUNCH();
-  return GSR_OK;
 }
 
 int gsr_project_sh_forward(const float* position, const float* log_scaling, const float* rotation_xyzw,

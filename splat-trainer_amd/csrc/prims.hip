@@ -165,9 +165,7 @@ constexpr int RS_MAX_BINS = 512;
 
 // 4096-element tiles from 1 M elements on (measured with the wave-private scatter, 3 M keys: scatter 38 -> 25 us per pass,
 // histogram and digit scan shrink with the block count; at 500 k the small tiles win: 10 against 15 us)
-#ifndef GSR_RS_BIG_MIN
-#define GSR_RS_BIG_MIN (1ll << 20)
-#endif
+constexpr long long GSR_RS_BIG_MIN = 1ll << 20;
 inline int rs_rounds_for(int64_t n) { return n < GSR_RS_BIG_MIN ? 4 : 16; }     // 1024 or 4096 pairs per block
 inline int rs_digit_bits(int bits) { return (bits + 8) / 9 < (bits + 7) / 8 ? 9 : 8; }
 
@@ -242,17 +240,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_digit_scan_kernel(const uint32_
 // (Round 2's form ranked 256 elements per round across the four waves: three block barriers and ~26 LDS operations per
 // element, most of them on bins the round never touched; this one has four barriers per BLOCK and ~7 LDS operations per
 // element.)
-// GSR_RS_NEXT_HIST (experiment): price of forming the NEXT pass's block histograms while this pass
-// scatters -- one integer atomic per element on hist'[next digit][destination block] (a block's elements go to ~BINS
-// destination runs of ~TILE / BINS elements each, so (destination block, next digit) pairs hardly repeat inside a block:
-// nothing to pre-aggregate).  The adds go to a dummy table; the sort's results are untouched.  See profiles/r04_sorts.txt.
-#ifndef GSR_RS_NEXT_HIST
-#define GSR_RS_NEXT_HIST 0
-#endif
-#if GSR_RS_NEXT_HIST
-__device__ uint32_t g_rs_dummy_hist[512 * 4096];
-#endif
-
 template <bool TWO, int ROUNDS, int BITS>
 __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* __restrict__ keys_in,
                                                                 const uint32_t* __restrict__ vals_in,   // null -> iota
@@ -359,9 +346,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
     keys_out[dst] = k;
     vals_out[dst] = s_val[e];
     if (TWO) vals2_out[dst] = s_val2[e];
-#if GSR_RS_NEXT_HIST
-    atomicAdd(&g_rs_dummy_hist[(((k >> (shift + BITS)) & (BINS - 1)) * 4096u + min(dst / (uint32_t)TILE, 4095u))], 1u);
-#endif
   }
 }
 

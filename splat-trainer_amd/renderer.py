@@ -174,9 +174,6 @@ def frustum_cull(position: torch.Tensor, camera_params: CameraParams, config: Ra
 
 # ------------------------------------------------------------------------------- data-dependent sizes
 _TLS = threading.local()
-# GSPLAT_HIP_NO_SPECULATION=1: enqueue nothing before the size it depends on has reached the host (A/B measurements;
-# results are bit-identical either way, tests/test_gpu_render.py::test_speculative_emit_and_early_colours_do_not_change_results)
-SPECULATE = os.environ.get("GSPLAT_HIP_NO_SPECULATION", "0") != "1"
 
 
 def _readback_slot(device):
@@ -189,27 +186,6 @@ def _readback_slot(device):
     event.record(_lib.current_stream())
     host = torch.empty(8, dtype=torch.int32).pin_memory()
     pool[key] = (host, event, (C.c_int32 * 8).from_address(host.data_ptr()))    # + the same words as a ctypes array
-  return pool[key]
-
-
-# GSPLAT_HIP_SIDE_STREAM=1: the frame driver puts the depth sort on a second stream next to the fused K2 + K3 sweep.
-# Measured (same box, median ms/step, off -> on): c1 0.511 -> 0.583, c2 0.958 -> 0.979, c3 2.705 -> 2.682: the cross-stream
-# hand-off costs more than the nine small sort launches hide except at millions of splats; off by default.
-SIDE_STREAM = os.environ.get("GSPLAT_HIP_SIDE_STREAM", "0") == "1"
-
-
-def _side_stream(device):
-  """(stream, fork event, join event) of this thread for ``device``: the frame driver puts the depth sort on the side
-  stream while the fused projection + colour sweep runs on the current one (csrc/frame.hip).  Created once; the events
-  have been recorded once so that their native handles exist."""
-  pool = _TLS.__dict__.setdefault("side", {})
-  key = device.index
-  if key not in pool:
-    stream = torch.cuda.Stream(device=device)
-    fork, join = torch.cuda.Event(), torch.cuda.Event()
-    fork.record(_lib.current_stream())
-    join.record(_lib.current_stream())
-    pool[key] = (stream, fork, join)
   return pool[key]
 
 
@@ -666,7 +642,7 @@ def _pair_capacity(dev_index, N: int):
   once, decays 1.5 % per frame), in steps of 1/16 of its power of two so that the arenas keep their sizes -- and the
   caching allocator its blocks -- from frame to frame; a first frame starts from 4 pairs per scene row."""
   guesses = _TLS.__dict__.setdefault("overlap_guess", {})
-  raw = guesses.get(dev_index, 0) if SPECULATE else 0
+  raw = guesses.get(dev_index, 0)
   if raw <= 0:
     raw = max(4 * N, 1 << 16)
   step = 1 << max(raw.bit_length() - 5, 0)
@@ -771,9 +747,6 @@ class _FrameFn(torch.autograd.Function):
                            T.data_ptr(), proj.data_ptr(), cam.data_ptr(), near, far, st.params,
                            int(bool(want_jac and K > 1)), int(st.want_median), int(st.compute_visibility),
                            int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, None, None, None, 3, None)
-    if SIDE_STREAM:
-      side, fork, join = _side_stream(dev)
-      frame.side_stream, frame.event_fork, frame.event_join = side.cuda_stream, fork.cuda_event, join.cuda_event
     out, plan, M, image = _run_frame(frame, st, dev, N, projected=False)
     indexes = _arena_view(out, plan.indexes, (M,), torch.int64)
     rows = st.rows

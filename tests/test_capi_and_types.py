@@ -47,7 +47,7 @@ def test_host_only_entry_points(built_libs):
   assert lib.gsr_struct_bytes(6) == -1
 
 
-def test_frame_plan_lays_out_disjoint_aligned_buffers(built_libs):
+def test_frame_plan_lays_out_disjoint_aligned_buffers_by_field_name(built_libs):
   """gsr_frame_plan (host only): every buffer of a frame gets its own 256-byte aligned range inside the arena it belongs
   to, the zero-filled head of the output arena covers exactly the buffers that must start at zero, optional buffers
   are absent (-1) when not asked for, sizes follow N / the pair capacity / the image, in both modes of the driver."""
@@ -55,9 +55,12 @@ def test_frame_plan_lays_out_disjoint_aligned_buffers(built_libs):
   cfg = sta.RasterConfig(compute_visibility=True, compute_point_heuristic=True)
 
   def plan(N, W, H, cap, K=16, jac=1, median=0, vis=1, grad=1, projected=False, C_=3):
-    f = _lib.GsrFrameC(None if projected else 1, 1, 1, 1, 1, N, K, W, H, 1, 1, 1, 0.1, 100.0, _lib.raster_params(cfg), jac,
-                       median, vis, grad, -1, 0, cap, 1 if projected else None, 1 if projected else None,
-                       1 if projected else None, C_, None, None, None, None)
+    src = 1 if projected else None
+    f = _lib.GsrFrameC(position=None if projected else 1, log_scaling=1, rotation_xyzw=1, alpha_logit=1, sh_features=1,
+                       N=N, K=K, W=W, H=H, T_camera_world=1, projection=1, camera_pos=1, near_plane=0.1, far_plane=100.0,
+                       params=_lib.raster_params(cfg), want_jacobian=jac, want_median=median, compute_visibility=vis,
+                       needs_grad=grad, seg_pairs=-1, seg_min_pairs=0, pair_capacity=cap, gaussians2d=src, depth=src,
+                       features=src, C=C_, depth_order=None)
     p = _lib.GsrFramePlanC()
     rc = lib.gsr_frame_plan(C.byref(f), C.byref(p))
     return rc, p

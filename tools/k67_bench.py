@@ -1,9 +1,8 @@
-"""K6 / K7 timing of one build of the library on the c2 (or c3) workload, with a digest of the gradients so that variants
-can be checked for bit-identity.  Used with GSPLAT_HIP_LIB=<variant .so> to compare kernel experiments:
+"""K6 / K7 timing of the library on the c2 (or c3) workload, with a digest of the gradients so that two builds can be
+checked for bit-identity.  To compare against an older build, run the same tool from a git worktree of that commit:
 
-    python splat-trainer_amd/build.py      # product build
-    python -c "import importlib.util,sys; ..."   # or: tools/build_variant.py NAME -DFLAG
-    GSPLAT_HIP_LIB=/path/libvariant.so python tools/k67_bench.py [c2|c3] [steps]
+    python splat-trainer_amd/build.py
+    python tools/k67_bench.py [c2|c3] [steps]
 """
 import hashlib
 import os
@@ -70,6 +69,6 @@ ks = timer.summary()
 h = hashlib.sha256()
 for t in (r.image, r.points.prune_cost, r.points.split_score, r.points.visibility) + tuple(p.grad for p in params):
   h.update(t.detach().cpu().numpy().tobytes())
-print(f"{os.environ.get('GSPLAT_HIP_LIB', 'product')} seg {cfg.segment_pairs}/{cfg.segment_min_pairs}: {which} O {r.num_overlaps}  K6 {ks['composite_forward'][1] * 1e3:.1f} us  "
+print(f"seg {cfg.segment_pairs}/{cfg.segment_min_pairs}: {which} O {r.num_overlaps}  K6 {ks['composite_forward'][1] * 1e3:.1f} us  "
       f"K7 {ks['composite_backward'][1] * 1e3:.1f} us  step {e0.elapsed_time(e1) / steps * 1e3:.0f} us  digest {h.hexdigest()[:16]}",
       flush=True)

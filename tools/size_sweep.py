@@ -3,7 +3,7 @@
 (GSR_RS_BIG_MIN), the automatic segment lengths -- is crossed somewhere between 0.25 M and 3 M splats.
     python tools/size_sweep.py [A|B|AB] [n_millions ...]
 One line per (scene, N): median step time (HIP events per step), K6 / K7 (events around the launches), pairs.
-GSPLAT_HIP_LIB=<variant .so> selects a build with a switch forced one way (tools/build_variant.py)."""
+To compare against an older build, run the same tool from a git worktree of that commit."""
 import os
 import statistics
 import sys
@@ -17,7 +17,6 @@ from splat_trainer_amd import renderer, synthetic
 
 scenes = sys.argv[1] if len(sys.argv) > 1 else "AB"
 sizes = [float(a) for a in sys.argv[2:]] or [0.25, 0.5, 0.8, 1.0, 1.2, 1.5, 2.0, 3.0]
-tag = os.path.basename(os.environ.get("GSPLAT_HIP_LIB", "product")).replace("libgsplat_hip_", "").replace(".so", "")
 cfg = sta.RasterConfig(compute_visibility=True, compute_point_heuristic=True)
 for sc in scenes:
   for nm in sizes:
@@ -54,7 +53,7 @@ for sc in scenes:
     renderer.KERNEL_TIMER = None
     ks = timer.summary()
     per = [ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(K)]
-    print(f"{tag:10s} scene {sc} N {nm:4.2f} M  O {r.num_overlaps:9d}  step median {statistics.median(per):7.0f} us  "
+    print(f"scene {sc} N {nm:4.2f} M  O {r.num_overlaps:9d}  step median {statistics.median(per):7.0f} us  "
           f"K6 {ks['composite_forward'][1] * 1e3:6.1f}  K7 {ks['composite_backward'][1] * 1e3:6.1f}", flush=True)
     del g, params, scene, r
     torch.cuda.empty_cache()
