@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 36) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 37) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -673,6 +673,38 @@ int gsr_color_backward(const GsrColorModel* model, const float* point_features, 
                        const float* cam_pos, const float* glo_feature, int64_t M, const float* d_diffuse,
                        const float* d_specular, float* d_point_features, const GsrColorGrads* grads, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* ---- scene regulariser and post-step projection (scene/mlp_scene.py:246-288 compute_reg / reg_loss, :236-237) ----
+ * Per row i of the M culled points, j = idx[i]: s = exp(log_scaling[j]); norm = (s . s) / depths[i]^2; aspect =
+ * max(s) / min(s); op = (1 - exp(-4 opacity[i]))^2 norm; spec = sum_k |specular[i,k]| (0 when specular is NULL);
+ * w = visibility[i] when visibility_weighted, else 1.  The four terms scale, opacity, aspect, specular are the means of
+ * {norm, op, aspect, spec} w over the rows with visibility[i] > 0 (the mask is applied in the kernel over all M rows and
+ * the count stays on the device; no such row: every term 0); loss = sum_k weight[k] term[k], a zero weight dropping
+ * its term.  gsr_reg_forward writes loss_out[0] and terms_out[5] = the four unweighted terms and the count; fixed-order
+ * sums, no float atomics: bit-reproducible.  gsr_reg_backward takes the forward's terms and the device scalar d_loss,
+ * writes d_opacity [M], d_depths [M], d_specular [M,3] for every row (zero where masked; each may be NULL) and ADDS the
+ * log_scaling term into rows idx[i] of d_log_scaling [N,3] (may be NULL; the rows of idx are unique).  visibility is a
+ * constant.  M = 0 is valid (loss 0).
+ * gsr_scene_post_step, in place over N rows: rotation_xyzw[i] /= max(|rotation_xyzw[i]|, eps) (16-byte aligned) and
+ * log_scaling[i] = clamp(log_scaling[i], lo, hi). */
+typedef struct GsrReg {
+  const int64_t* idx;          /* [M] */
+  const float* log_scaling;    /* [N, 3] */
+  const float* depths;         /* [M] */
+  const float* opacity;        /* [M] */
+  const float* specular;       /* [M, 3] or NULL */
+  const float* visibility;     /* [M] */
+  int64_t M, N;
+  float weight[4];             /* scale, opacity, aspect, specular */
+  int32_t visibility_weighted;
+} GsrReg;
+int64_t gsr_reg_struct_bytes(void);
+size_t gsr_reg_workspace_bytes(int64_t M);
+int gsr_reg_forward(const GsrReg* args, float* loss_out, float* terms_out, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int gsr_reg_backward(const GsrReg* args, const float* terms, const float* d_loss, float* d_opacity, float* d_depths,
+                     float* d_specular, float* d_log_scaling, void* stream);
+int gsr_scene_post_step(float* rotation_xyzw, float* log_scaling, int64_t N, float eps, float lo, float hi, void* stream);
 
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the

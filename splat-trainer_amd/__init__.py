@@ -13,6 +13,8 @@ from .bilateral import (BilateralCorrector, BilateralCorrectorConfig, BilateralG
                         bilateral_tv_loss)
 from .neighbours import assign_clusters, estimate_scale, kmeans, kmeans_iter, knn
 from .color_model import ColorModel, ColorModelConfig, Colors
+from .reg import reg_loss
+from .mlp_scene import MLPScene, MLPSceneConfig
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -20,4 +22,4 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "GsplatHipError", "GradOut", "fused_ssim", "clamped_mse_loss", "clamped_l1_loss", "reference_loss", "ShFactorCollector", "TaichiQueue", "count_nonfinite",
            "check_finite", "random_camera", "random_3d_gaussians", "BilateralCorrector", "BilateralCorrectorConfig",
            "BilateralGrid", "bilateral_correct", "bilateral_tv_loss", "knn", "estimate_scale", "assign_clusters",
-           "kmeans_iter", "kmeans", "ColorModel", "ColorModelConfig", "Colors"]
+           "kmeans_iter", "kmeans", "ColorModel", "ColorModelConfig", "Colors", "reg_loss", "MLPScene", "MLPSceneConfig"]

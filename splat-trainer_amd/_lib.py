@@ -13,7 +13,7 @@ import torch
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 36
+ABI_VERSION = 37
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
 MAX_FEATURES = 16                  # GSR_MAX_FEATURES
 WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
@@ -95,6 +95,12 @@ class GsrColorModelC(C.Structure):
 class GsrColorGradsC(C.Structure):
   _fields_ = [("d_weight", C.c_void_p * 7), ("d_bias", C.c_void_p * 7), ("d_glo", C.c_void_p),
               ("d_cam_pos", C.c_void_p)]
+
+
+class GsrRegC(C.Structure):
+  _fields_ = [("idx", C.c_void_p), ("log_scaling", C.c_void_p), ("depths", C.c_void_p), ("opacity", C.c_void_p),
+              ("specular", C.c_void_p), ("visibility", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),
+              ("weight", C.c_float * 4), ("visibility_weighted", C.c_int32)]
 
 
 def raster_params(config) -> GsrRasterParamsC:
@@ -207,6 +213,11 @@ PROTOTYPES = {
     "gsr_color_forward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     "gsr_color_backward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p,
                                      C.POINTER(GsrColorGradsC), _p, _sz, _p]),
+    "gsr_reg_struct_bytes": (_i64, []),
+    "gsr_reg_workspace_bytes": (_sz, [_i64]),
+    "gsr_reg_forward": (C.c_int, [C.POINTER(GsrRegC), _p, _p, _p, _sz, _p]),
+    "gsr_reg_backward": (C.c_int, [C.POINTER(GsrRegC), _p, _p, _p, _p, _p, _p, _p]),
+    "gsr_scene_post_step": (C.c_int, [_p, _p, _i64, _f, _f, _f, _p]),
 }
 
 _lib = None
@@ -260,6 +271,9 @@ def load() -> C.CDLL:
       if lib.gsr_color_struct_bytes(which) != C.sizeof(mirror):
         raise GsplatHipError(f"struct layout mismatch: {mirror.__name__} is {C.sizeof(mirror)} bytes in the binding, "
                              f"{lib.gsr_color_struct_bytes(which)} in the library; rebuild")
+    if lib.gsr_reg_struct_bytes() != C.sizeof(GsrRegC):
+      raise GsplatHipError(f"struct layout mismatch: GsrRegC is {C.sizeof(GsrRegC)} bytes in the binding, "
+                           f"{lib.gsr_reg_struct_bytes()} in the library; rebuild")
     _lib = lib
   return _lib
 

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 HOSTMATH_PATH = os.path.join(PKG_DIR, "libgsr_hostmath.so")
 HIP_SOURCES = ["prims.hip", "geometry.hip", "binning.hip", "composite.hip", "frame.hip", "ssim.hip", "optim.hip", "densify.hip",
-               "bilagrid.hip", "neighbours.hip", "color_model.hip"]
+               "bilagrid.hip", "neighbours.hip", "color_model.hip", "reg.hip"]
 HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_wide.inc",
            os.path.join("..", "..", "include", "gsplat_hip.h")]
 
