@@ -88,7 +88,7 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 37) */
+int gsr_abi_version(void);                 /* bumped on any signature change (currently 38) */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */
@@ -634,6 +634,28 @@ int gsr_assign_clusters(const float* x, int64_t N, const float* centroids, int64
 size_t gsr_kmeans_workspace_bytes(int64_t N, int64_t K);
 int gsr_kmeans_iter(const float* x, int64_t N, float* centroids, int64_t K, int32_t iters, int64_t* labels_out,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- frustum point queries and view features (visibility/query_points.py, visibility/cluster.py PointClusters) ------
+ * gsr_frustum_counts: points [N, 3] float32 against V camera records [V, 16] float32 (rows 0..2 of image_t_world =
+ *   expand_proj(K) @ camera_t_world, row-major, then w, h, near, far).  With h_r = fmaf(M[r][2], z, fmaf(M[r][1], y,
+ *   fmaf(M[r][0], x, M[r][3]))) and d = h_2 a point is inside a camera when h_0 >= 0 && h_0 < w d && h_1 >= 0 &&
+ *   h_1 < h d && d > near && d < min(far, depth_below) (depth_below: +inf when unused).  point_counts_out [N] int32 =
+ *   cameras that see point i, camera_counts_out [V] int32 = points camera c sees; either may be NULL, not both.  Exact.
+ *   1 <= N <= GSR_NEIGHBOURS_MAX_N, 1 <= V <= GSR_VISIBILITY_MAX_CAMERAS.
+ * gsr_view_features: features_out [K] float32 = per cluster the sum of vis[j] over the listed points idx[j] of that
+ *   cluster with vis[j] > threshold (strict), in a fixed order: a function of the SET of (idx, vis) pairs, bit-reproducible.
+ *   point_idx [M] int64 holds DISTINCT indices in [0, N) (an index outside the range is skipped; duplicates are not
+ *   supported: the last writer wins); M may be 0.  sorted_labels / sorted_points [N] uint32: the points in stable label
+ *   order (gsr_sort_pairs_u32 of (label, point index)); cluster_range [K, 2] uint32 from gsr_tile_ranges.
+ *   dense_scratch [N] and slot_scratch [N] float32 are the caller's, reused by every call (the call zero-fills the first).
+ *   point_visible [N] int32 (may be NULL) is incremented at every listed index. */
+#define GSR_VISIBILITY_MAX_CAMERAS 65536
+int gsr_frustum_counts(const float* points, int64_t N, const float* records, int64_t V, float depth_below,
+                       int32_t* point_counts_out, int32_t* camera_counts_out, void* stream);
+int gsr_view_features(const int64_t* point_idx, const float* point_vis, int64_t M, float threshold,
+                      const uint32_t* sorted_labels, const uint32_t* sorted_points, const uint32_t* cluster_range,
+                      int64_t N, int64_t K, float* dense_scratch, float* slot_scratch, float* features_out,
+                      int32_t* point_visible, void* stream);
 
 /* ---- neural colour model (scene/color_model.py ColorModel, scene/mlp/torch_mlp.py MLP / AffineMLP) ----------
  * Per row: x = LayerNorm_F([point_features, glo]) (no affine, eps 1e-5); diffuse = lum(base(x), 0); d = normalize(

@@ -15,6 +15,11 @@ from .neighbours import assign_clusters, estimate_scale, kmeans, kmeans_iter, kn
 from .color_model import ColorModel, ColorModelConfig, Colors
 from .reg import reg_loss
 from .mlp_scene import MLPScene, MLPSceneConfig
+from .visibility import (BatchOverlapSampler, BatchOverlapSamplerConfig, CameraBatch, PointClusters, RandomSampler,
+                         RandomSamplerConfig, ViewClustering, balanced_cloud, balanced_points, camera_counts, crop_cloud,
+                         foreground_points, foreground_visibility, frustum_counts, inverse_ndc_depth, point_visibility,
+                         random_cloud, random_ndc, random_points, sample_batch, sample_batch_grouped,
+                         sample_with_temperature, select_batch, sinkhorn)
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -22,4 +27,9 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "GsplatHipError", "GradOut", "fused_ssim", "clamped_mse_loss", "clamped_l1_loss", "reference_loss", "ShFactorCollector", "TaichiQueue", "count_nonfinite",
            "check_finite", "random_camera", "random_3d_gaussians", "BilateralCorrector", "BilateralCorrectorConfig",
            "BilateralGrid", "bilateral_correct", "bilateral_tv_loss", "knn", "estimate_scale", "assign_clusters",
-           "kmeans_iter", "kmeans", "ColorModel", "ColorModelConfig", "Colors", "reg_loss", "MLPScene", "MLPSceneConfig"]
+           "kmeans_iter", "kmeans", "ColorModel", "ColorModelConfig", "Colors", "reg_loss", "MLPScene", "MLPSceneConfig",
+           "CameraBatch", "point_visibility", "camera_counts", "frustum_counts", "crop_cloud", "random_ndc",
+           "inverse_ndc_depth", "random_points", "balanced_points", "random_cloud", "balanced_cloud",
+           "foreground_visibility", "foreground_points", "PointClusters", "ViewClustering", "sample_with_temperature",
+           "select_batch", "sample_batch", "sample_batch_grouped", "sinkhorn", "BatchOverlapSampler",
+           "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig"]

@@ -13,13 +13,14 @@ import torch
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 
-ABI_VERSION = 37
+ABI_VERSION = 38
 PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
 MAX_FEATURES = 16                  # GSR_MAX_FEATURES
 WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
 BILAGRID_MAX_SIDE = 32768          # GSR_BILAGRID_MAX_SIDE
 KNN_MAX_K = 16                     # GSR_KNN_MAX_K
 NEIGHBOURS_MAX_N = 0x7FFFFFFF      # GSR_NEIGHBOURS_MAX_N
+VISIBILITY_MAX_CAMERAS = 65536     # GSR_VISIBILITY_MAX_CAMERAS
 
 
 class GsrRasterParamsC(C.Structure):
@@ -206,6 +207,8 @@ PROTOTYPES = {
     "gsr_assign_clusters": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
     "gsr_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
     "gsr_kmeans_iter": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
+    "gsr_frustum_counts": (C.c_int, [_p, _i64, _p, _i64, _f, _p, _p, _p]),
+    "gsr_view_features": (C.c_int, [_p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "gsr_color_struct_bytes": (_i64, [_i32]),
     "gsr_color_supported": (C.c_int, [C.POINTER(GsrColorModelC)]),
     "gsr_color_forward_workspace_bytes": (_sz, [C.POINTER(GsrColorModelC)]),

@@ -7,6 +7,7 @@
 #include "gsr_math.h"
 #include "gsr_bilagrid.h"
 #include "gsr_neighbours.h"
+#include "gsr_visibility.h"
 #include "gsr_color.h"
 
 extern "C" {
@@ -287,6 +288,69 @@ void hm_cm_normalize(const float* v, const float* dd, int64_t n, float* d, float
     gsr_cm_normalize(v + 3 * i, d + 3 * i, inv, clamped);
     gsr_cm_normalize_bwd(d + 3 * i, inv, clamped, dd + 3 * i, dv + 3 * i);
   }
+}
+
+}  // extern "C"
+
+// frustum point queries and view features (gsr_visibility.h): the device's results bit for bit.
+extern "C" {
+
+// points [N, 3], records [V, 16]; point_counts [N] / camera_counts [V] int32 (either may be NULL).
+void hm_frustum_counts(const float* p, int64_t N, const float* rec, int64_t V, float depth_below, int32_t* point_counts,
+                       int32_t* camera_counts) {
+  if (camera_counts) for (int64_t c = 0; c < V; ++c) camera_counts[c] = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    int32_t seen = 0;
+    for (int64_t c = 0; c < V; ++c) {
+      const bool in = gsr_vis_inside(rec + GSR_VIS_RECORD_FLOATS * c, p[3 * i], p[3 * i + 1], p[3 * i + 2], depth_below);
+      seen += in ? 1 : 0;
+      if (camera_counts && in) camera_counts[c] += 1;
+    }
+    if (point_counts) point_counts[i] = seen;
+  }
+}
+
+// labels [N] int64 in [0, K); idx [M] int64 distinct in [0, N), vis [M]; out [K]; point_visible [N] int32 (may be NULL)
+// is incremented.  Returns -1 for a label or an index out of range.
+int hm_view_features(const int64_t* labels, int64_t N, int64_t K, const int64_t* idx, const float* vis, int64_t M,
+                     float threshold, float* out, int32_t* point_visible) {
+  for (int64_t i = 0; i < N; ++i)
+    if (labels[i] < 0 || labels[i] >= K) return -1;
+  for (int64_t j = 0; j < M; ++j)
+    if (idx[j] < 0 || idx[j] >= N) return -1;
+  float* dense = new float[N]();
+  int64_t* start = new int64_t[K + 1]();
+  int64_t* order = new int64_t[N];
+  for (int64_t j = 0; j < M; ++j) {
+    dense[idx[j]] = gsr_vf_value(vis[j], threshold);
+    if (point_visible) point_visible[idx[j]] += 1;
+  }
+  for (int64_t i = 0; i < N; ++i) start[labels[i] + 1] += 1;
+  for (int64_t c = 0; c < K; ++c) start[c + 1] += start[c];
+  {
+    int64_t* fill = new int64_t[K];
+    for (int64_t c = 0; c < K; ++c) fill[c] = start[c];
+    for (int64_t i = 0; i < N; ++i) order[fill[labels[i]]++] = i;      // stable: ascending point index per cluster
+    delete[] fill;
+  }
+  for (int64_t c = 0; c < K; ++c) {
+    const int64_t s = start[c], e = start[c + 1];
+    float lanes[64];
+    for (int l = 0; l < 64; ++l) lanes[l] = 0.f;
+    int64_t t = 0;
+    for (int64_t a = s; a < e; ++t) {
+      const int64_t b = (a / GSR_VF_CHUNK + 1) * GSR_VF_CHUNK < e ? (a / GSR_VF_CHUNK + 1) * GSR_VF_CHUNK : e;
+      float piece = dense[order[a]];
+      for (int64_t q = a + 1; q < b; ++q) piece += dense[order[q]];
+      lanes[t & 63] += piece;
+      a = b;
+    }
+    out[c] = gsr_vf_tree64(lanes);
+  }
+  delete[] dense;
+  delete[] start;
+  delete[] order;
+  return 0;
 }
 
 }  // extern "C"
