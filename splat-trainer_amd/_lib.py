@@ -227,6 +227,19 @@ _lib = None
 _lock = threading.Lock()
 
 
+def ptr(t):
+  """Device address of a tensor's data as a plain int (the prototypes declare c_void_p: ctypes takes the int, no wrapper
+  object per argument), or None (NULL) for None and for an empty tensor.  A raw address -- an int: buffers of the frame
+  arena that are only ever handed to kernels are kept as addresses, see renderer._run_frame -- passes through, 0 as None."""
+  if t is None:
+    return None
+  if isinstance(t, int):
+    return t or None
+  if t.numel() == 0:
+    return None
+  return t.data_ptr()
+
+
 def current_stream_ptr() -> int:
   """hipStream_t of torch's current stream on the current device.  (torch.cuda.current_stream() costs ~13 us per call
   on this stack -- device-availability probing -- and a step makes a dozen launches; the raw getter costs well under 1 us.)"""

@@ -21,12 +21,9 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 MIN_GRID, MAX_GRID = 2, 64
-
-
-def _ptr(t):
-  return None if t is None or t.numel() == 0 else t.data_ptr()
 
 
 def _grid_shape(grids: torch.Tensor) -> Tuple[int, int, int, int]:

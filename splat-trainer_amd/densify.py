@@ -17,13 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-
-
-_stream = _lib.current_stream_ptr
-
-
-def _p(t: Optional[torch.Tensor]):
-  return None if t is None or t.numel() == 0 else t.data_ptr()     # plain int: the prototypes declare c_void_p
+from ._lib import current_stream_ptr as _stream, ptr as _p
 
 
 def select_n(values: torch.Tensor, n: int, descending: bool = False) -> torch.Tensor:

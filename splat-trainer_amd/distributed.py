@@ -71,8 +71,8 @@ class GradBucket:
       p.grad = v
 
   def zero(self, except_views: Sequence[int] = ()):
-    """Zero-fills the buffer; ``except_views`` lists parameter slots to leave alone (their first backward pass of the
-    batch overwrites every row: ``GradOut.geometry_uninitialized`` / ``feature_uninitialized``).  The alignment padding
+    """Zero-fills the buffer; ``except_views`` lists parameter slots to leave alone (declared uninitialised with
+    ``GradOut.begin_batch``: the first backward node to claim one overwrites every row).  The alignment padding
     between slots is zero from construction and never written, so it is only filled through when that saves a launch."""
     if not except_views:
       self.flat.zero_()
@@ -105,6 +105,20 @@ class GradBucket:
     return work if async_op else None
 
 
+def _rebuild_sh_gradient(blocks: torch.Tensor, width: int, sh_features, positions, d_sh, d_pos, accumulate: bool):
+  """Launches the multi-camera SH rebuild (csrc/geometry.hip: sh_bwd_multi_kernel) over a gathered block table: one row
+  of ``width`` floats per camera slot, its first 3 N floats the colour gradient of the scene rows, the next 3 the camera
+  position.  ``d_sh`` is written (``accumulate``: added to); ``d_pos`` None: the position term of the colour gradient
+  was added by the local backward passes and the coefficient rows are not read."""
+  from . import _lib
+  N, _, K = sh_features.shape
+  base = blocks.data_ptr()
+  _lib.check(_lib.load().gsr_sh_backward_multi(base, width, base + 4 * 3 * N, width, blocks.shape[0],
+                                               sh_features.data_ptr(), positions.data_ptr(), N, K, d_sh.data_ptr(),
+                                               None if d_pos is None else d_pos.data_ptr(), int(accumulate),
+                                               _lib.current_stream_ptr()), "gsr_sh_backward_multi")
+
+
 def exchange_sh_factors(collector, camera_slots: Sequence[int], cameras_per_rank: int, sh_features: torch.Tensor,
                         positions: torch.Tensor, d_sh: torch.Tensor, d_pos: Optional[torch.Tensor], group=None,
                         accumulate: bool = True, after=None, visible_max: Optional[int] = None):
@@ -122,23 +136,14 @@ def exchange_sh_factors(collector, camera_slots: Sequence[int], cameras_per_rank
 
   ``camera_slots[i]``: slot (0..cameras_per_rank-1) of the i-th recorded camera on this rank; every rank contributes
   exactly ``cameras_per_rank`` slots (unused ones stay zero), so the gather is one fixed-size collective."""
-  import ctypes as C
-  from . import _lib
-  lib = _lib.load()
-  N, _, K = sh_features.shape
+  N = sh_features.shape[0]
   if visible_max is not None and 4 * (visible_max + 1) >= 3 * (N + 1):
     visible_max = None               # packed rows would not be smaller than the dense block
   block = gather_sh_factors(collector, camera_slots, cameras_per_rank, N, group=group, device=positions.device,
                             visible_max=visible_max)
   if after is not None:
     after.wait()                     # e.g. the asynchronous all-reduce that delivers d_pos
-  stride = (N + 1) * 3
-  base = block.data_ptr()
-  ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-  _lib.check(lib.gsr_sh_backward_multi(C.c_void_p(base), stride, C.c_void_p(base + 4 * 3 * N), stride, block.shape[0],
-                                       ptr(sh_features.detach()), ptr(positions.detach()), N, K, ptr(d_sh), ptr(d_pos),
-                                       int(accumulate), _lib.current_stream_ptr()),
-             "gsr_sh_backward_multi")
+  _rebuild_sh_gradient(block, (N + 1) * 3, sh_features, positions, d_sh, d_pos, accumulate)
   collector.clear()
 
 
@@ -574,15 +579,23 @@ class CameraShardedStep:
     dist.all_gather_into_tensor(recv, send, group=self.group)
     return recv
 
+  def _rebuild(self, blocks: torch.Tensor, launch: bool = True):
+    """The feature gradient of ALL cameras from the gathered block table (overwritten row for row), and -- unless the
+    local backward passes added it -- their colour gradients' position term on top of the all-reduced position gradient.
+    (Every rank runs the same render path: the flag is the same everywhere; K = 1 has no position term at all.)"""
+    feature = self.params[4]
+    position_done = position_term_done(self.collector, feature.shape[2])
+    if launch:
+      _rebuild_sh_gradient(blocks, blocks.shape[1], feature, self.params[0], self.feature_grad,
+                           None if position_done else self.bucket.views[0], accumulate=False)
+    self.collector.clear()
+
   def _exchange_dense(self, num_cameras: int, local: List[dict], point_state):
     """The default exchange: all-reduce (geometry gradients + visible + in-view count) in flight while the camera blocks
     are packed and all-gathered; then every rank rebuilds the SH gradient of all cameras and replays their controller
     scores in camera order.  Two collectives, no host sync."""
-    import ctypes as C
-    from . import _lib
     from .densify import dp_replay
-    position, feature = self.params[0], self.params[4]
-    N, K = position.shape[0], feature.shape[2]
+    position = self.params[0]
     initialised = dist.is_available() and dist.is_initialized()
     # pack first: it also adds this rank's cameras to the two sum columns the all-reduce carries
     send = self.pack_camera_blocks(num_cameras, local, self.collector.items)
@@ -591,18 +604,9 @@ class CameraShardedStep:
     blocks = self.all_gather_blocks(send)
     if pending is not None:
       pending.wait()                                   # d_pos below adds to the all-reduced position gradient
-    width = blocks.shape[1]
-    base = blocks.data_ptr()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    # (every rank runs the same render path: the flag is the same everywhere; K = 1 has no position term at all)
-    position_done = position_term_done(self.collector, K)
-    _lib.check(_lib.load().gsr_sh_backward_multi(C.c_void_p(base), width, C.c_void_p(base + 4 * 3 * N), width,
-                                                 blocks.shape[0], ptr(feature.detach()), ptr(position.detach()), N, K,
-                                                 ptr(self.feature_grad),
-                                                 None if position_done else ptr(self.bucket.views[0]), 0,
-                                                 _lib.current_stream_ptr()), "gsr_sh_backward_multi")
-    self.collector.clear()
-    dp_replay(point_state, blocks, self.camera_slots(num_cameras, position.device), N, sums=self.bucket.extra)
+    self._rebuild(blocks)
+    dp_replay(point_state, blocks, self.camera_slots(num_cameras, position.device), position.shape[0],
+              sums=self.bucket.extra)
 
   # ---------------------------------------------------------------------------------------- sharded exchange
   def _sharded_begin(self, num_cameras: int):
@@ -668,11 +672,8 @@ class CameraShardedStep:
 
     No host sync.  Against the dense form (one 6 N + 3 block per camera to every rank) a rank receives 3 N + 2 N / G
     floats per camera instead of 6 N, and the replay costs N / G instead of N point-visits per camera."""
-    import ctypes as C
-    from . import _lib
     from .densify import dp_finish, dp_replay_slice
-    position, feature = self.params[0], self.params[4]
-    N, K, dev = position.shape[0], feature.shape[2], position.device
+    N, dev = self.params[0].shape[0], self.params[0].device
     G = self.world
     live = dist.is_available() and dist.is_initialized()
     factors, scores, cpr, L = self._send
@@ -714,16 +715,6 @@ class CameraShardedStep:
       pending.wait()                                   # d_pos below adds to the all-reduced position gradient
     if pending_max is not None:
       pending_max.wait()
-    width = blocks.shape[1]
-    base = blocks.data_ptr()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    position_done = position_term_done(self.collector, K)
-    if blocks.is_cuda:
-      _lib.check(_lib.load().gsr_sh_backward_multi(C.c_void_p(base), width, C.c_void_p(base + 4 * 3 * N), width,
-                                                   blocks.shape[0], ptr(feature.detach()), ptr(position.detach()), N, K,
-                                                   ptr(self.feature_grad),
-                                                   None if position_done else ptr(self.bucket.views[0]), 0,
-                                                   _lib.current_stream_ptr()), "gsr_sh_backward_multi")
-    self.collector.clear()
+    self._rebuild(blocks, launch=blocks.is_cuda)       # (the rebuild kernel is HIP-only: gloo / CPU rehearsals skip it)
     dp_finish(point_state, gathered, N, scale_max=self.scale_max, sums=self.bucket.extra)
     self.last_blocks = blocks                          # (tests look at what was gathered)

@@ -15,13 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-  return None if t is None or t.numel() == 0 else t.data_ptr()     # plain int: the prototypes declare c_void_p
-
-
-_stream = _lib.current_stream_ptr
+from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 
 def _strides(t: torch.Tensor):

@@ -18,7 +18,6 @@ state, so concurrent callers on different streams/threads are safe and no run_sy
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 import threading
 from typing import Optional, Tuple
@@ -26,6 +25,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._lib import current_stream_ptr as _stream, ptr as _ptr
 from .data_types import CameraParams, Gaussians3D, RasterConfig, RenderedPoints, Rendering
 from . import sh as _sh
 from .sh import evaluate_sh_at
@@ -89,21 +89,6 @@ class KernelTimer:
 
 
 KERNEL_TIMER: Optional[KernelTimer] = None
-
-
-def _ptr(t):
-  """ctypes pointer of a tensor's data, or of a raw device address (an int: buffers of the frame arena that are only ever
-  handed to kernels are kept as addresses, see _run_frame), or None."""
-  if t is None:
-    return None
-  if isinstance(t, int):
-    return t or None
-  if t.numel() == 0:
-    return None
-  return t.data_ptr()          # (the prototypes declare c_void_p: ctypes takes the plain int, no wrapper object per argument)
-
-
-_stream = _lib.current_stream_ptr
 
 
 def _require_device(*tensors: torch.Tensor):
@@ -229,7 +214,8 @@ class GradOut:
   ``debug=True`` (or GSPLAT_HIP_DEBUG_GRADOUT=1) records every claim in ``log`` -- (node, action, buffers) in backward
   order -- and raises on a protocol violation: a buffer overwritten after it had been written in the same batch, or a
   buffer consumed (``finish_batch``) that a node had claimed for overwrite but some other node then also overwrote.
-  ``geometry_uninitialized`` / ``feature_uninitialized`` remain as properties over the same state (older callers set them)."""
+  The nodes' claims are all made by ``sh.gradient_destinations``.  ``geometry_uninitialized`` / ``feature_uninitialized``
+  are read-only views of the same state: is a buffer of the group still waiting for its first writer?"""
 
   GEOMETRY = ("position", "log_scaling", "rotation", "alpha_logit")
   NAMES = GEOMETRY + ("feature",)
@@ -296,36 +282,38 @@ class GradOut:
     if self.debug:
       self.log.append((node, action, tuple(names)))
 
-  # ---- the two flags older callers use, over the same state
+  # ---- read-only: is a buffer of the group still waiting for its first writer?
   @property
   def geometry_uninitialized(self) -> bool:
     return any(n in self._fresh for n in self.GEOMETRY)
-
-  @geometry_uninitialized.setter
-  def geometry_uninitialized(self, value: bool):
-    (self._fresh.update if value else self._fresh.difference_update)(self.GEOMETRY)
 
   @property
   def feature_uninitialized(self) -> bool:
     return "feature" in self._fresh
 
-  @feature_uninitialized.setter
-  def feature_uninitialized(self, value: bool):
-    (self._fresh.add if value else self._fresh.discard)("feature")
-
-  def take_geometry_uninitialized(self) -> bool:
-    """= claim_overwrite over the four geometry buffers (kept for callers of the round-3 protocol)."""
-    return self.claim_overwrite("caller", self.GEOMETRY)
-
-  def ensure_geometry_initialized(self):
-    """= claim_accumulate over the four geometry buffers."""
-    self.claim_accumulate("caller", self.GEOMETRY)
 
   def _check(self, name, like):
     t = getattr(self, name)
     if t is None or t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != like.device:
       raise ValueError(f"GradOut.{name} must be a contiguous float32 tensor shaped like the parameter")
     return t
+
+
+def _geometry_targets(go: Optional[GradOut], dest: "_sh.Destination", pos, ls, rot, al):
+  """The four geometry gradient buffers of a backward node: the caller's, or fresh tensors (zero-filled unless the
+  node's kernels write every row)."""
+  if go is not None:
+    return go._check("position", pos), go._check("log_scaling", ls), go._check("rotation", rot), go._check("alpha_logit", al)
+  alloc = torch.zeros_like if dest.zero_fill else torch.empty_like
+  return alloc(pos), alloc(ls), alloc(rot), alloc(al)
+
+
+def _sh_sink(grad_out: Optional[GradOut], sh_collector, feature, position) -> "Optional[_sh.ShSink]":
+  """The SH gradient sink of render_gaussians: the factor collector (data-parallel: colour-gradient factors are
+  exchanged, not d_sh -- sh.py), the caller's own buffers, or None (autograd)."""
+  if sh_collector is None and grad_out is not None:
+    return _sh.ShSink(grad_out._check("feature", feature), grad_out._check("position", position), grad_out, None)
+  return _sh.sh_sink(sh_collector)
 
 
 class _ProjectFn(torch.autograd.Function):
@@ -381,30 +369,27 @@ class _ProjectFn(torch.autograd.Function):
     pos, ls, rot, al, indexes, T, proj = ctx.saved_tensors
     M, N = indexes.shape[0], pos.shape[0]
     go = ctx.grad_out
-    if go is not None:
-      d_pos, d_ls = go._check("position", pos), go._check("log_scaling", ls)
-      d_rot, d_al = go._check("rotation", rot), go._check("alpha_logit", al)
-      go.claim_accumulate("project_to_image.backward", go.GEOMETRY)      # rows of `indexes` are added to; the rest must be defined
-    else:
-      live = M > 0 and (d_g2d is not None or d_depth is not None)
-      alloc = torch.empty_like if (M == N and live) else torch.zeros_like   # every row is written when nothing was culled
-      d_pos, d_ls, d_rot, d_al = alloc(pos), alloc(ls), alloc(rot), alloc(al)
+    live = M > 0 and (d_g2d is not None or d_depth is not None)
+    # rows of `indexes` are added to caller-owned buffers (the rest must be defined), or written into fresh tensors
+    # (every row is written when nothing was culled)
+    dest, _ = _sh.gradient_destinations("project_to_image.backward", N, M if live else 0, 0, go, None)
+    d_pos, d_ls, d_rot, d_al = _geometry_targets(go, dest, pos, ls, rot, al)
     want_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
     d_camera = None
-    if M > 0 and (d_g2d is not None or d_depth is not None):
+    if live:
       dg = _f32c(d_g2d) if d_g2d is not None else torch.zeros(M, 6, dtype=torch.float32, device=pos.device)
       dd = _f32c(d_depth) if d_depth is not None else None
       if want_cam:
         partials, d_camera = _camera_scratch(M, pos.device)
         _lib.check(lib.gsr_project_backward_camera(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
                                                    _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
-                                                   _ptr(d_ls), _ptr(d_rot), _ptr(d_al), 1 if go is not None else 0,
+                                                   _ptr(d_ls), _ptr(d_rot), _ptr(d_al), int(dest.accumulate),
                                                    _ptr(partials), _ptr(d_camera), _stream()),
                    "gsr_project_backward_camera")
       else:
         _lib.check(lib.gsr_project_backward(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
                                             _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
-                                            _ptr(d_ls), _ptr(d_rot), _ptr(d_al), 1 if go is not None else 0,
+                                            _ptr(d_ls), _ptr(d_rot), _ptr(d_al), int(dest.accumulate),
                                             _stream()), "gsr_project_backward")
     d_T, d_proj = _camera_grads(d_camera, pos.device) if want_cam else (None, None)
     if go is not None:
@@ -725,35 +710,27 @@ class _FrameFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, position, log_scaling, rotation, alpha_logit, feature, T, proj, cam_pos, cull_args, st: _RasterState,
-              grad_out, sh_out, want_jac):
-    lib = _lib.load()
+              grad_out, sink, want_jac):
     pos, ls, rot, al = _f32c(position), _f32c(log_scaling), _f32c(rotation), _f32c(alpha_logit)
     sh, cam = _f32c(feature), _f32c(cam_pos)
     N, K, dev = pos.shape[0], sh.shape[2], pos.device
     W, H, near, far, margin = cull_args
-    num_tiles = ((W + 15) // 16) * ((H + 15) // 16)
     if N == 0:
-      indexes = torch.empty(0, dtype=torch.int64, device=dev)
       st.M = 0
       image = _blank_frame(st, dev)
-      rows = st.rows
-      ctx.save_for_backward(pos, ls, rot, al, sh, indexes, T, proj, cam)
-      ctx.set_materialize_grads(False)
-      ctx.st, ctx.jac, ctx.grad_out, ctx.sh_out = st, None, grad_out, sh_out
-      ctx.in_dtypes = (position.dtype, log_scaling.dtype, rotation.dtype, alpha_logit.dtype, feature.dtype)
-      ctx.mark_non_differentiable(indexes)
-      return image, rows[:, 0:6], rows[:, 10:11], indexes
-    frame = _lib.GsrFrameC(pos.data_ptr(), ls.data_ptr(), rot.data_ptr(), al.data_ptr(), sh.data_ptr(), N, K, W, H,
-                           T.data_ptr(), proj.data_ptr(), cam.data_ptr(), near, far, st.params,
-                           int(bool(want_jac and K > 1)), int(st.want_median), int(st.compute_visibility),
-                           int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, None, None, None, 3, None)
-    out, plan, M, image = _run_frame(frame, st, dev, N, projected=False)
-    indexes = _arena_view(out, plan.indexes, (M,), torch.int64)
+      indexes, jac = torch.empty(0, dtype=torch.int64, device=dev), None
+    else:
+      frame = _lib.GsrFrameC(pos.data_ptr(), ls.data_ptr(), rot.data_ptr(), al.data_ptr(), sh.data_ptr(), N, K, W, H,
+                             T.data_ptr(), proj.data_ptr(), cam.data_ptr(), near, far, st.params,
+                             int(bool(want_jac and K > 1)), int(st.want_median), int(st.compute_visibility),
+                             int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, None, None, None, 3, None)
+      out, plan, M, image = _run_frame(frame, st, dev, N, projected=False)
+      indexes = _arena_view(out, plan.indexes, (M,), torch.int64)
+      jac = _arena_view(out, plan.jacobian, (M, 9)) if plan.jacobian >= 0 else None
     rows = st.rows
     ctx.save_for_backward(pos, ls, rot, al, sh, indexes, T, proj, cam)
     ctx.set_materialize_grads(False)       # unused outputs (gaussians2d / depth, usually) arrive as None
-    ctx.st, ctx.jac = st, (_arena_view(out, plan.jacobian, (M, 9)) if plan.jacobian >= 0 else None)
-    ctx.grad_out, ctx.sh_out = grad_out, sh_out
+    ctx.st, ctx.jac, ctx.grad_out, ctx.sink = st, jac, grad_out, sink
     ctx.in_dtypes = (position.dtype, log_scaling.dtype, rotation.dtype, alpha_logit.dtype, feature.dtype)
     ctx.mark_non_differentiable(indexes)
     return image, rows[:, 0:6], rows[:, 10:11], indexes
@@ -764,55 +741,35 @@ class _FrameFn(torch.autograd.Function):
     pos, ls, rot, al, sh, indexes, T, proj, cam = ctx.saved_tensors
     st: _RasterState = ctx.st
     M, N, K, dev = indexes.shape[0], pos.shape[0], sh.shape[2], pos.device
-    go, sh_out = ctx.grad_out, ctx.sh_out
-    collector = sh_out if isinstance(sh_out, _sh.ShFactorCollector) else None
+    go, sink = ctx.grad_out, ctx.sink
+    collector = sink.collector if sink is not None else None
     nothing = (None,) * 13
     # the camera gradient, view-direction term included (folded natively: None is returned for cam_pos)
     want_cam = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
     partials = d_camera = None
+    # the SH coefficient gradient: to the factor collector (data-parallel), into caller-owned buffers, or returned
+    want_sh = sink is not None or ctx.needs_input_grad[4]
+    geometry, feature = _sh.gradient_destinations("render_gaussians.backward", N, M, K, go, sink, want_feature=want_sh)
     # Geometry gradients: added to caller-owned buffers (mode 1), or every scene row written -- zeros where the camera saw
     # nothing -- when the destination holds nothing worth keeping (fresh tensors for autograd, or buffers the caller
     # declared uninitialised): no zero-fill and no read-modify-write (mode 2; mode 0 + zero-fill when the camera saw
     # less than an eighth of the scene)
-    dense = N > 0 and (M == N or 8 * M >= N)
-    if go is not None:
-      d_pos, d_ls = go._check("position", pos), go._check("log_scaling", ls)
-      d_rot, d_al = go._check("rotation", rot), go._check("alpha_logit", al)
-      mode = 1
-      if dense and go.claim_overwrite("render_gaussians.backward", go.GEOMETRY):
-        mode = 2                           # every scene row written: no zero-fill, no read-modify-write
-      elif not dense:
-        go.claim_accumulate("render_gaussians.backward", go.GEOMETRY)
-    else:
-      alloc = torch.empty_like if dense else torch.zeros_like
-      d_pos, d_ls, d_rot, d_al = alloc(pos), alloc(ls), alloc(rot), alloc(al)
-      mode = 2 if dense else 0
-    # the SH coefficient gradient: to the factor collector (data-parallel), into caller-owned buffers, or returned
-    want_sh = collector is not None or sh_out is not None or ctx.needs_input_grad[4]
-    d_sh, owner, sh_mode = None, None, 0
-    if collector is None and want_sh:
-      owner = sh_out[2] if (sh_out is not None and len(sh_out) > 2) else None
-      d_sh = sh_out[0] if sh_out is not None else torch.empty(N, 3, K, dtype=torch.float32, device=dev)
-      if sh_out is None:
-        overwrite = True
-        if not dense:
-          d_sh.zero_()
-      elif owner is None:
-        overwrite = False                  # caller-owned buffer without an owner object: plain accumulation
-      elif dense:
-        overwrite = owner.claim_overwrite("render_gaussians.backward", ("feature",))
-      else:
-        owner.claim_accumulate("render_gaussians.backward", ("feature",))
-        overwrite = False
+    d_pos, d_ls, d_rot, d_al = _geometry_targets(go, geometry, pos, ls, rot, al)
+    mode = 2 if geometry.write_all else int(geometry.accumulate)
+    d_sh, sh_mode = None, 0
+    if feature is not None:
+      d_sh = sink.d_sh if sink is not None else torch.empty(N, 3, K, dtype=torch.float32, device=dev)
+      if feature.zero_fill:
+        d_sh.zero_()
       # 1: every row of d_sh is written (zeros where this camera saw nothing): no zero-fill, no RMW; 2: rows of `indexes` accumulate
-      sh_mode = 1 if (overwrite and dense) else 2
+      sh_mode = 1 if feature.write_all else 2
     if N > 0:
       # the backward half of the frame behind ONE native call (csrc/frame.hip: gsr_frame_backward):
       # K7 -> packed gradient rows -> (scene row -> visible rank map) -> geometry sweep -> SH coefficient gradient
       live = M > 0 and st.O > 0 and d_image is not None
       if live and st.vis_partial is None:
         raise _lib.GsplatHipError("backward called on a rendering made without gradient state")
-      inv = torch.empty(N, dtype=torch.int32, device=dev) if (M < N and dense) else None
+      inv = torch.empty(N, dtype=torch.int32, device=dev) if (M < N and _sh.dense_rows(N, M)) else None
       partial = torch.empty(st.O, PARTIAL_FLOATS, dtype=torch.float32, device=dev) if live else None
       grows = torch.empty(M, ROW_FLOATS, dtype=torch.float32, device=dev) if M > 0 else None
       dcol = torch.empty(M, 3, dtype=torch.float32, device=dev) if want_sh else None
@@ -848,12 +805,11 @@ class _FrameFn(torch.autograd.Function):
       # sweep above, from the Jacobian the forward pass saved; K = 1 has no such term)
       collector.items.append((indexes, dcol, cam, K == 1 or ctx.jac is not None))
     cam = _camera_grads(d_camera, dev) if want_cam else (None, None)
-    if go is not None:
-      return (None, None, None, None, d_sh.to(ctx.in_dtypes[4]) if (d_sh is not None and sh_out is None) else None) + \
-          cam + nothing[7:]
     dt = ctx.in_dtypes
-    return (d_pos.to(dt[0]), d_ls.to(dt[1]), d_rot.to(dt[2]), d_al.to(dt[3]),
-            d_sh.to(dt[4]) if (d_sh is not None and sh_out is None) else None) + cam + nothing[7:]
+    d_feature = d_sh.to(dt[4]) if (d_sh is not None and sink is None) else None
+    if go is not None:
+      return (None, None, None, None, d_feature) + cam + nothing[7:]
+    return (d_pos.to(dt[0]), d_ls.to(dt[1]), d_rot.to(dt[2]), d_al.to(dt[3]), d_feature) + cam + nothing[7:]
 
 
 def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features: torch.Tensor,
@@ -915,13 +871,9 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
     return _render_frame(gaussians, camera_params, config, render_median_depth, grad_out, sh_collector)
   prefetch = {}
   if use_sh:
-    sh_out = None
-    if sh_collector is not None:            # data-parallel: exchange colour-gradient factors, not d_sh (sh.py)
-      sh_out = sh_collector
-    elif grad_out is not None:
-      sh_out = (grad_out._check("feature", feature), grad_out._check("position", gaussians.position), grad_out)
+    sink = _sh_sink(grad_out, sh_collector, feature, gaussians.position)
     g2d, depth, indexes = project_to_image(gaussians, camera_params, config, grad_out=grad_out, prefetch=prefetch)
-    feats = evaluate_sh_at(feature, gaussians.position, indexes, camera_params.camera_position, grad_out=sh_out)
+    feats = evaluate_sh_at(feature, gaussians.position, indexes, camera_params.camera_position, grad_out=sink)
   else:
     if grad_out is not None:
       raise ValueError("grad_out with use_sh=False: gather the features yourself or use plain autograd")
@@ -942,11 +894,7 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   if cam_grad and sh_collector is not None:
     raise ValueError("camera gradients are not supported in data-parallel mode (sh_collector): detach T_camera_world "
                      "and projection, or render on one device")
-  sh_out = None
-  if sh_collector is not None:              # data-parallel: exchange colour-gradient factors, not d_sh (sh.py)
-    sh_out = sh_collector
-  elif grad_out is not None:
-    sh_out = (grad_out._check("feature", feature), grad_out._check("position", position), grad_out)
+  sink = _sh_sink(grad_out, sh_collector, feature, position)
   W, H = camera_params.image_size
   st = _RasterState()
   st.M, st.C, st.W, st.H, st.O = 0, 3, int(W), int(H), 0
@@ -958,7 +906,7 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   # the colour gradient's position term: from the Jacobian the forward pass saves.  Also in data-parallel mode (factor
   # collector): every rank adds the term of its own cameras before the all-reduce, so the multi-camera rebuild does not
   # have to recompute it for all cameras on every rank (it would re-read every coefficient row for that)
-  want_pos_grad = _sh.wants_position_grad(position, sh_out) or (
+  want_pos_grad = _sh.wants_position_grad(position, sink) or (
       sh_collector is not None and sh_collector.position_term_local and torch.is_grad_enabled() and
       (position.requires_grad or grad_out is not None))
   # (the camera gradient's view-direction term is formed natively from the same saved Jacobian and folded into dL/dT:
@@ -971,5 +919,5 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   image, g2d, depth, indexes = _FrameFn.apply(position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit,
                                               feature, _f32c_camera(camera_params.T_camera_world),
                                               _f32c_camera(camera_params.projection), cam_pos, cull_args, st,
-                                              grad_out, sh_out, want_pos_grad or cam_grad)
+                                              grad_out, sink, want_pos_grad or cam_grad)
   return _rendering_of(st, image, indexes, g2d, depth, camera_params)

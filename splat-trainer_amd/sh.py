@@ -5,20 +5,12 @@ Call site in the reference: splat_trainer/scene/transfer_sh.py:49
 """
 from __future__ import annotations
 
-import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-  if t is None or t.numel() == 0:
-    return None
-  return t.data_ptr()          # plain int: the prototypes declare c_void_p
-
-
-_stream = _lib.current_stream_ptr
+from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 
 class ShFactorCollector:
@@ -50,9 +42,88 @@ def as_kernel_inputs(sh_features, positions, camera_pos):
           camera_pos.detach().to(torch.float32).contiguous())
 
 
-def wants_position_grad(positions, grad_out) -> bool:
-  return torch.is_grad_enabled() and not isinstance(grad_out, ShFactorCollector) and \
-      (positions.requires_grad or (grad_out is not None and grad_out[1] is not None))
+class ShSink(NamedTuple):
+  """Where the SH coefficient gradient goes: the one internal form of the public ``grad_out=`` union (``sh_sink``)."""
+  d_sh: Optional[torch.Tensor]        # caller-owned (N,3,K) buffer the coefficient gradient is written / added to
+  d_pos: Optional[torch.Tensor]       # caller-owned (N,3) buffer the colour gradient's position term is added to
+  owner: Optional[object]             # the renderer.GradOut that knows which of its buffers still hold nothing
+  collector: Optional[ShFactorCollector]   # data-parallel: only the colour gradient is recorded (no d_sh, no d_pos)
+
+
+def sh_sink(grad_out) -> Optional[ShSink]:
+  """``None | (d_sh, d_pos) | (d_sh, d_pos, owner) | ShFactorCollector`` -> ``None`` (plain autograd) or a ``ShSink``."""
+  if grad_out is None or isinstance(grad_out, ShSink):
+    return grad_out
+  if isinstance(grad_out, ShFactorCollector):
+    return ShSink(None, None, None, grad_out)
+  return ShSink(grad_out[0], grad_out[1], grad_out[2] if len(grad_out) > 2 else None, None)
+
+
+def wants_position_grad(positions, sink: Optional[ShSink]) -> bool:
+  return torch.is_grad_enabled() and (sink is None or sink.collector is None) and \
+      (positions.requires_grad or (sink is not None and sink.d_pos is not None))
+
+
+class Destination(NamedTuple):
+  """How one backward node's kernels treat one group of gradient buffers (``gradient_destinations``)."""
+  write_all: bool      # every scene row is written (zeros where the camera saw nothing): no zero-fill, no read-modify-write
+  accumulate: bool     # the rows of ``indexes`` are added to what the buffer holds
+  zero_fill: bool      # the node zero-fills the buffer itself before its kernels touch the rows of ``indexes``
+
+
+_WRITE_ALL = Destination(True, False, False)           # fresh tensor or claimed buffer, written whole
+_WRITE_ROWS = Destination(False, False, True)          # fresh tensor, too few rows for the whole-buffer kernels
+_ACCUMULATE = Destination(False, True, False)
+_ZERO_ACCUMULATE = Destination(False, True, True)
+
+# node -> (forms the four geometry gradients?, the SH coefficient gradient?, has kernels that write EVERY scene row?)
+_NODES = {"project_to_image.backward": (True, False, False),
+          "render_gaussians.backward": (True, True, True),
+          "evaluate_sh_at.backward": (False, True, True)}
+
+
+def dense_rows(N: int, M: int) -> bool:
+  """Are M visible rows of N enough for the kernels that write every scene row?  (Below an eighth of the scene the
+  zero-fill + the sweep over the M rows is cheaper.)"""
+  return N > 0 and (M == N or 8 * M >= N)
+
+
+def gradient_destinations(node: str, N: int, M: int, K: int, grad_out, sink: Optional[ShSink], want_feature: bool = True):
+  """THE decision of where a backward node's gradients go: ``(geometry, feature)``, each a ``Destination`` or None (the
+  node does not form that gradient).  ``grad_out``: the renderer.GradOut whose geometry buffers the node writes, None:
+  fresh tensors for autograd.  ``sink``: the SH gradient sink, None: a fresh tensor for autograd.  ``M``: the rows the
+  node's kernels will write.  Every claim on a GradOut is made here, in the order the kernels run."""
+  geometry_node, feature_node, every_row_kernels = _NODES[node]
+  covers = dense_rows(N, M) if every_row_kernels else (N > 0 and M == N)
+  geometry = feature = None
+  if geometry_node:
+    if grad_out is None:
+      geometry = _WRITE_ALL if covers else _WRITE_ROWS
+    elif every_row_kernels and covers:
+      geometry = _WRITE_ALL if grad_out.claim_overwrite(node, grad_out.GEOMETRY) else _ACCUMULATE
+    else:
+      # (project_to_image's kernels touch only the rows of `indexes`, and in the three-call form autograd runs the SH
+      # node, which ADDS its position term, before it: it never claims an overwrite)
+      grad_out.claim_accumulate(node, grad_out.GEOMETRY)
+      geometry = _ACCUMULATE
+  if feature_node and want_feature and (sink is None or sink.collector is None):
+    owner = sink.owner if sink is not None else None
+    if sink is None:
+      feature = _WRITE_ALL if covers else _WRITE_ROWS
+    elif owner is None:
+      feature = _ACCUMULATE                  # caller-owned buffer without an owner object: plain accumulation
+    elif covers:
+      feature = _WRITE_ALL if owner.claim_overwrite(node, ("feature",)) else _ACCUMULATE
+    else:
+      # The claim zero-fills the OWNER's feature buffer when that still held nothing.  A d_sh that is some other buffer is
+      # zero-filled by the node: only evaluate_sh_at's public grad_out=(d_sh, d_pos, owner) can name one (render_gaussians
+      # always hands its node the owner's own buffer, so the test never fires there).
+      fresh = owner.claim_accumulate(node, ("feature",))
+      feature = _ZERO_ACCUMULATE if (fresh and owner.feature is not sink.d_sh) else _ACCUMULATE
+    if not geometry_node and owner is not None and sink.d_pos is not None and K > 1:
+      # the node ADDS the colour gradient's position term to d_pos, and autograd runs it before the projection's node
+      owner.claim_accumulate(node, owner.GEOMETRY)
+  return geometry, feature
 
 
 def launch_forward_counted(sh_features, positions, camera_pos, indexes_full, count_dev, want_pos_grad: bool):
@@ -71,7 +142,7 @@ def launch_forward_counted(sh_features, positions, camera_pos, indexes_full, cou
 
 class _SHFn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, sh_features, positions, indexes, camera_pos, grad_out, want_pos_grad, precomputed):
+  def forward(ctx, sh_features, positions, indexes, camera_pos, sink, want_pos_grad, precomputed):
     lib = _lib.load()
     sh, pos, cam = as_kernel_inputs(sh_features, positions, camera_pos)
     idx = indexes.contiguous()
@@ -88,7 +159,7 @@ class _SHFn(torch.autograd.Function):
                                     _stream()), "gsr_sh_forward")
     ctx.save_for_backward(sh, pos, idx, cam)
     ctx.jac = jac
-    ctx.grad_out = grad_out
+    ctx.sink = sink
     ctx.in_dtypes = (sh_features.dtype, positions.dtype, camera_pos.dtype)
     return out
 
@@ -98,34 +169,20 @@ class _SHFn(torch.autograd.Function):
     sh, pos, idx, cam = ctx.saved_tensors
     N, _, K = sh.shape
     M = idx.shape[0]
-    go = ctx.grad_out
-    if isinstance(go, ShFactorCollector):    # data-parallel factor exchange: keep only the colour gradient
+    sink = ctx.sink
+    if sink is not None and sink.collector is not None:    # data-parallel factor exchange: keep only the colour gradient
       # (4th entry False: this node hands on colour gradients only -- the position term of the colour gradient is left to
       # the multi-camera rebuild, which the exchange then runs WITH the position gradient as a target; K = 1 has no term)
-      go.items.append((idx, d_out.detach().to(torch.float32).contiguous(), cam, K == 1))
+      sink.collector.items.append((idx, d_out.detach().to(torch.float32).contiguous(), cam, K == 1))
       return None, None, None, None, None, None, None
     g = d_out.detach().to(torch.float32).contiguous() if M > 0 else None
-    owner = go[2] if (go is not None and len(go) > 2) else None
-    dense = N > 0 and (M == N or 8 * M >= N)
-    if go is None:
-      overwrite = True
-    elif owner is None:
-      overwrite = False
-    elif dense:
-      overwrite = owner.claim_overwrite("evaluate_sh_at.backward", ("feature",))
-    else:
-      # (too few visible rows for the dense overwrite: zero-fill + accumulate; a d_sh that is not the owner's own buffer
-      # -- grad_out=(d_sh, d_pos, owner) -- is zero-filled below)
-      overwrite = bool(owner.claim_accumulate("evaluate_sh_at.backward", ("feature",))) and owner.feature is not go[0]
-    if go is not None:                       # fused "+=" into caller-owned buffers (see renderer.GradOut)
-      d_sh, d_pos = go[0], go[1]
-      if owner is not None and d_pos is not None and K > 1:
-        # this pass ADDS to d_pos and autograd runs it before the projection's backward pass
-        owner.claim_accumulate("evaluate_sh_at.backward", owner.GEOMETRY)
+    _, dest = gradient_destinations("evaluate_sh_at.backward", N, M, K, None, sink)
+    if sink is not None:                     # fused "+=" into caller-owned buffers (see renderer.GradOut)
+      d_sh, d_pos = sink.d_sh, sink.d_pos
     else:
       d_sh = torch.empty(N, 3, K, dtype=torch.float32, device=pos.device)
       d_pos = torch.zeros_like(pos) if ctx.needs_input_grad[1] else None
-    if overwrite and dense:
+    if dest.write_all:
       # every row of d_sh is written (zeros where this camera saw nothing): no zero-fill, no read-modify-write
       inv = None
       if M < N:
@@ -134,7 +191,7 @@ class _SHFn(torch.autograd.Function):
       _lib.check(lib.gsr_sh_backward_dense(_ptr(g), _ptr(sh), _ptr(pos), _ptr(inv), M, N, K, _ptr(cam), _ptr(ctx.jac),
                                            _ptr(d_sh), _ptr(d_pos), _stream()), "gsr_sh_backward_dense")
     else:
-      if overwrite:
+      if dest.zero_fill:
         d_sh.zero_()
       if M > 0:
         _lib.check(lib.gsr_sh_backward(_ptr(g), _ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(ctx.jac),
@@ -148,7 +205,7 @@ class _SHFn(torch.autograd.Function):
       _lib.check(lib.gsr_sh_camera_position_grad(_ptr(g), _ptr(ctx.jac), M, _ptr(partials), _ptr(d_cam), _stream()),
                  "gsr_sh_camera_position_grad")
       d_cam = d_cam.to(ctx.in_dtypes[2])
-    if go is not None:
+    if sink is not None:
       return None, None, None, d_cam, None, None, None
     return (d_sh.to(ctx.in_dtypes[0]), d_pos.to(ctx.in_dtypes[1]) if d_pos is not None else None,
             None, d_cam, None, None, None)
@@ -161,8 +218,9 @@ def evaluate_sh_at(sh_features: torch.Tensor, positions: torch.Tensor, indexes: 
   colour_c = 0.5 + sum_k sh[idx, c, k] * Y_k(normalize(positions[idx] - camera_pos)), K in {1,4,9,16}
   (degrees 0..3, basis order k = n(n+1)+m as splat_trainer/scene/mlp/rsh.py).  Differentiable wrt
   ``sh_features`` and, through the view direction, ``positions`` and ``camera_pos``; the caller clamps (transfer_sh.py:50).
-  ``grad_out=(d_sh, d_positions[, owner])``: optional fused accumulation, see ``renderer.GradOut`` (when
-  ``owner.feature_uninitialized`` is set, ``d_sh`` is overwritten row for row instead of added to, and the flag is cleared)."""
+  ``grad_out=(d_sh, d_positions[, owner])``: optional fused accumulation, see ``renderer.GradOut`` (with an ``owner``
+  whose ``feature`` buffer still holds nothing this batch, the backward pass claims it and overwrites ``d_sh`` row for row
+  instead of adding to it); a ``ShFactorCollector``: data-parallel, only the colour gradient is recorded."""
   for t in (sh_features, positions, indexes, camera_pos):
     if not t.is_cuda:
       raise _lib.GsplatHipError("evaluate_sh_at runs only on a HIP device; there is no CPU fallback")
@@ -170,12 +228,13 @@ def evaluate_sh_at(sh_features: torch.Tensor, positions: torch.Tensor, indexes: 
     raise ValueError(f"sh_features must be (N,3,K) with K in (1,4,9,16), got {tuple(sh_features.shape)}")
   if indexes.dtype != torch.int64:
     raise TypeError("indexes must be int64")
+  sink = sh_sink(grad_out)
   cam_grad = torch.is_grad_enabled() and camera_pos.requires_grad
-  if cam_grad and isinstance(grad_out, ShFactorCollector):
+  if cam_grad and sink is not None and sink.collector is not None:
     raise ValueError("camera gradients are not supported in data-parallel mode (ShFactorCollector): detach the camera "
                      "position, or evaluate on one device")
   # the saved Jacobian also gives the camera position's gradient
-  want_pos_grad = wants_position_grad(positions, grad_out) or cam_grad
+  want_pos_grad = wants_position_grad(positions, sink) or cam_grad
   if cam_grad and _precomputed is not None and _precomputed[1] is None and sh_features.shape[2] > 1:
     _precomputed = None                      # evaluated without the Jacobian: evaluate again with it
-  return _SHFn.apply(sh_features, positions, indexes, camera_pos, grad_out, want_pos_grad, _precomputed)
+  return _SHFn.apply(sh_features, positions, indexes, camera_pos, sink, want_pos_grad, _precomputed)

@@ -208,7 +208,7 @@ def _stats_worker(rank, world, port, out_path, num_cameras):
     if grad_out.geometry_uninitialized:                 # the first backward pass of a batch writes every row
       for t in (grad_out.position, grad_out.log_scaling, grad_out.rotation, grad_out.alpha_logit):
         t.zero_()
-      grad_out.geometry_uninitialized = False
+      assert grad_out.claim_overwrite("fake_render", grad_out.GEOMETRY) is True
     grad_out.position[d["idx"]] += float(j + 1)
     if collector.on_rows is not None:                   # what the fused node's backward pass does between its two halves:
       rows = torch.zeros(d["idx"].shape[0], 16)         # the packed gradient rows carry the colour gradient in columns 8..10
@@ -324,7 +324,7 @@ def _idle_rank_worker(rank, world, port, out_path):
     assert grad_out.geometry_uninitialized and grad_out.feature_uninitialized
     for k, name in enumerate(("position", "log_scaling", "rotation", "alpha_logit", "feature")):
       getattr(grad_out, name).fill_(float(k + 1))
-    grad_out.geometry_uninitialized = grad_out.feature_uninitialized = False
+    assert grad_out.claim_overwrite("fake_render", grad_out.NAMES) is True
     idx = torch.arange(n)
     z = torch.zeros(n)
     return sta.Rendering(image=None, camera=None, points=sta.RenderedPoints(
