@@ -25,6 +25,12 @@ Specification (one step over the rows ``indexes`` (unique), per-point weight ``w
                         dec      = lr * rho * (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps)
     local_vector        dec      = B dec
                         param[idx] -= dec
+
+``step(..., return_terms=True)`` also returns, per stepped group and for the rows ``indexes``, the sizes of the terms that
+were added to form each output (tests/optim_contract.py normalises errors by them): ``g`` the weighted gradient after the
+basis rotation, ``momentum_in`` (u for LaProp, g for Adam) as it enters the momentum, ``denom``, ``dec`` the decrement
+as it is subtracted from the parameter, and for local_vector groups ``g_abs`` = sum_r |B_rk| |g_r| and ``dec_abs`` =
+sum_k |B_rk| |dec_k|, the sums of magnitudes behind the two rotations.
 """
 from __future__ import annotations
 
@@ -52,8 +58,8 @@ def step(tensors: Dict[str, torch.Tensor], grads: Dict[str, Optional[torch.Tenso
          types: Dict[str, str], indexes: torch.Tensor, visibility: Optional[torch.Tensor] = None,
          basis: Optional[torch.Tensor] = None, algo: str = "laprop", betas=(0.9, 0.999), eps: float = 1e-16,
          vis_beta: float = 0.9, vis_smooth: float = 0.01, bias_correction: bool = True,
-         grad_clip: Optional[float] = None) -> None:
-  """In-place step of ``tensors`` (name -> (N, ...)) on rows ``indexes``."""
+         grad_clip: Optional[float] = None, return_terms: bool = False) -> Optional[dict]:
+  """In-place step of ``tensors`` (name -> (N, ...)) on rows ``indexes``.  ``return_terms``: see the module docstring."""
   beta1, beta2 = betas
   idx = indexes
   t = state["step"][idx] + 1
@@ -68,6 +74,7 @@ def step(tensors: Dict[str, torch.Tensor], grads: Dict[str, Optional[torch.Tenso
   else:
     inv_w = torch.ones_like(t)
     rho = torch.ones_like(t)
+  terms = {} if return_terms else None
   bc1 = 1 - beta1 ** t if bias_correction else torch.ones_like(t)
   bc2 = 1 - beta2 ** t if bias_correction else torch.ones_like(t)
   for name, p in tensors.items():
@@ -78,8 +85,12 @@ def step(tensors: Dict[str, torch.Tensor], grads: Dict[str, Optional[torch.Tenso
     flat = p.reshape(n, -1)
     kind = types.get(name, SCALAR)
     g = grad.reshape(n, -1)[idx] * inv_w[:, None]
+    rec = {}
     if kind == LOCAL_VECTOR:
+      if return_terms:
+        rec["g_abs"] = torch.einsum("mrk,mr->mk", basis.to(g.dtype).abs(), g.abs())
       g = torch.einsum("mrk,mr->mk", basis.to(g.dtype), g)
+    rec["g"] = g
     st = state["groups"][name]
     if kind == SCALAR:
       v = beta2 * st["exp_avg_sq"][idx] + (1 - beta2) * g * g
@@ -95,12 +106,20 @@ def step(tensors: Dict[str, torch.Tensor], grads: Dict[str, Optional[torch.Tenso
       u = g / denom
       if grad_clip is not None and grad_clip > 0:
         u = u.clamp(-grad_clip, grad_clip)
+      rec["momentum_in"] = u
       m = beta1 * m + (1 - beta1) * u
       dec = lrs[name] * (rho / bc1)[:, None] * m
     else:
+      rec["momentum_in"] = g
       m = beta1 * m + (1 - beta1) * g
       dec = lrs[name] * (rho / bc1)[:, None] * m / denom
     st["exp_avg"][idx] = m
     if kind == LOCAL_VECTOR:
+      if return_terms:
+        rec["dec_abs"] = torch.einsum("mrk,mk->mr", basis.to(g.dtype).abs(), dec.abs())
       dec = torch.einsum("mrk,mk->mr", basis.to(g.dtype), dec)
+    rec["denom"], rec["dec"] = denom, dec
+    if terms is not None:
+      terms[name] = rec
     flat[idx] = flat[idx] - dec
+  return terms
