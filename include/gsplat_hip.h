@@ -20,6 +20,11 @@
  *     error, splat_trainer/trainer/trainer.py:507-509, not a boundary error).
  *
  * The maths each entry point implements is specified in oracle/torch_oracle.py (header comment).
+ *
+ * This file is the one place the ABI is written down: the ctypes binding (splat-trainer_amd/_lib.py) reads it at import
+ * and derives its prototypes, struct mirrors and constants from it.  Keep declarations in the forms used below --
+ * `typedef struct X { ... } X;`, plain `T name`, `T a, b` and `T name[n]` fields, `RET gsr_name(ARGS);`, integer
+ * `#define GSR_NAME value`, C comments -- a form the binding cannot read stops its import with the line's number.
  */
 #ifndef GSPLAT_HIP_H
 #define GSPLAT_HIP_H
@@ -88,7 +93,8 @@ typedef struct GsrSegmentsC {
 /* sizeof of the ABI's structs as the library was compiled: 0 GsrRasterParamsC, 1 GsrSegmentsC, 2 GsrFrameC,
  * 3 GsrFramePlanC, 4 GsrFrameResultC, 5 GsrFrameBackwardC (-1 otherwise) -- for a binding to check its own layout. */
 int64_t gsr_struct_bytes(int32_t which);
-int gsr_abi_version(void);                 /* bumped on any signature change (currently 38) */
+#define GSR_ABI_VERSION 38                 /* bumped on any signature change; the one place the number is written */
+int gsr_abi_version(void);                 /* GSR_ABI_VERSION of the library as it was compiled */
 const char* gsr_error_string(int code);
 
 /* ---- device-wide primitives (K5: radix bin + depth sort) ------------------------------------------------ */

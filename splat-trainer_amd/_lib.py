@@ -6,222 +6,151 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 import torch
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
-
-ABI_VERSION = 38
-PREFETCH_MIN_ROWS = 1_000_000      # include/gsplat_hip.h: GSR_PREFETCH_MIN_ROWS
-MAX_FEATURES = 16                  # GSR_MAX_FEATURES
-WIDE_MIN_FEATURES = 4              # GSR_WIDE_MIN_FEATURES
-BILAGRID_MAX_SIDE = 32768          # GSR_BILAGRID_MAX_SIDE
-KNN_MAX_K = 16                     # GSR_KNN_MAX_K
-NEIGHBOURS_MAX_N = 0x7FFFFFFF      # GSR_NEIGHBOURS_MAX_N
-VISIBILITY_MAX_CAMERAS = 65536     # GSR_VISIBILITY_MAX_CAMERAS
+HEADER_PATH = os.path.join(PKG_DIR, "..", "include", "gsplat_hip.h")
 
 
-class GsrRasterParamsC(C.Structure):
-  _fields_ = [("alpha_threshold", C.c_float), ("clamp_max_alpha", C.c_float), ("T_eps", C.c_float),
-              ("q_max", C.c_float), ("blur", C.c_float), ("antialias", C.c_int32), ("tile_size", C.c_int32),
-              ("margin_px", C.c_float)]
+class GsplatHipError(RuntimeError):
+  pass
 
 
-class GsrSegmentsC(C.Structure):
-  _fields_ = [("tile_seg", C.c_void_p), ("seg_desc", C.c_void_p), ("seg_total", C.c_void_p), ("capacity", C.c_int64),
-              ("heavy_capacity", C.c_int64), ("seg_P", C.c_void_p), ("seg_TC", C.c_void_p), ("seg_last", C.c_void_p),
-              ("seg_median", C.c_void_p), ("tile_order", C.c_void_p)]
+# ---- the binding is derived from the header: include/gsplat_hip.h is the one place the ABI is written down ----------
+# C types travel as normalised spellings ("int64_t", "const float*"); the rule that turns one into a ctypes type:
+# scalars map to their ctypes scalar, a struct held by value is its mirror, a function argument pointing to one of the
+# ABI's structs is POINTER(mirror), a `const char*` return is c_char_p and every other pointer -- every pointer field of
+# a struct included -- is c_void_p (ctypes then takes a plain int address, no wrapper object per argument).
+SCALARS = {"float": C.c_float, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
+           "size_t": C.c_size_t}
+
+_TYPE = r"\s*(const\s+)?(\w+)\s*(\*?)\s*"
+_DECLARATOR = r"\w+(?:\[\d+\])?"
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
+_FUNCTION = re.compile(_TYPE + r"(gsr_\w+)\s*\(([^(){};]*)\)\s*;")
+_FIELD = re.compile(_TYPE + rf"({_DECLARATOR}(?:\s*,\s*{_DECLARATOR})*)\s*")      # `T a;`, `T a, b, c;`, `T a[7];`
+_ARGUMENT = re.compile(_TYPE + r"\w*\s*")
+_DEFINE = re.compile(r"#\s*define\s+(\w+)(\([^)]*\))?\s*(.*)")                     # group 2: a function-like macro
+_SPACE = re.compile(r"\s*")
 
 
-class GsrFrameC(C.Structure):
-  _fields_ = [("position", C.c_void_p), ("log_scaling", C.c_void_p), ("rotation_xyzw", C.c_void_p),
-              ("alpha_logit", C.c_void_p), ("sh_features", C.c_void_p), ("N", C.c_int64), ("K", C.c_int32),
-              ("W", C.c_int32), ("H", C.c_int32), ("T_camera_world", C.c_void_p), ("projection", C.c_void_p),
-              ("camera_pos", C.c_void_p), ("near_plane", C.c_float), ("far_plane", C.c_float),
-              ("params", GsrRasterParamsC), ("want_jacobian", C.c_int32), ("want_median", C.c_int32),
-              ("compute_visibility", C.c_int32), ("needs_grad", C.c_int32), ("seg_pairs", C.c_int32),
-              ("seg_min_pairs", C.c_int32), ("pair_capacity", C.c_int64), ("gaussians2d", C.c_void_p),
-              ("depth", C.c_void_p), ("features", C.c_void_p), ("C", C.c_int32), ("depth_order", C.c_void_p),
-              ("feature_table", C.c_int32)]
+def parse_header(text: str):
+  """The ABI a header text declares, in declaration order: (constants, structs, functions) with constants name -> int
+  (the object-like macros that have a value), structs name -> [(field, C type, array length or 0)] and functions
+  name -> (return C type, [argument C types]).  Function-like macros, #include, #ifndef / #endif guards and
+  `extern "C"` carry no ABI; anything else it cannot read -- any other directive (#if, #else, #pragma: they could change
+  what the compiler sees) and a name declared twice included -- raises GsplatHipError naming the line."""
+  constants, structs, functions = {}, {}, {}
+
+  def fail(pos):
+    line = text.count("\n", 0, pos) + 1
+    raise GsplatHipError(f"gsplat_hip.h:{line}: cannot parse {text.splitlines()[line - 1].strip()!r}")
+
+  def ctype(m, pos):
+    const, base, star = m.group(1, 2, 3)
+    if not star and base not in SCALARS and base not in structs:      # held by value: a scalar or an earlier struct
+      fail(pos)
+    return ("const " if const else "") + base + star
+
+  def declare(table, name, value, pos):
+    if name in table:
+      fail(pos)
+    table[name] = value
+
+  def directive(m):
+    d = _DEFINE.fullmatch(m.group().strip())
+    if d is None:
+      re.match(r"#\s*(include|ifndef|endif)\b", m.group().strip()) or fail(m.start())
+    elif not d.group(2) and d.group(3):
+      try:
+        declare(constants, d.group(1), int(d.group(3), 0), m.start())
+      except ValueError:
+        fail(m.start())
+    return ""
+
+  blank = lambda m: "\n" * m.group().count("\n")                      # line numbers survive
+  text = re.sub(r"/\*.*?\*/", blank, text, flags=re.S)
+  text = re.sub(r"^#ifdef __cplusplus$.*?^#endif$", blank, text, flags=re.S | re.M)
+  text = re.sub(r"^[ \t]*#.*$", directive, text, flags=re.M)
+
+  pos = _SPACE.match(text).end()
+  while pos < len(text):
+    m = _STRUCT.match(text, pos)
+    if m:
+      fields, at = [], m.start(2)
+      for decl in m.group(2).split(";"):
+        if decl.strip():
+          at_decl = at + len(decl) - len(decl.lstrip())
+          d = _FIELD.fullmatch(decl) or fail(at_decl)
+          for declarator in d.group(4).split(","):
+            name, _, count = declarator.strip().partition("[")
+            fields.append((name, ctype(d, at_decl), int(count[:-1] or 0)))
+        at += len(decl) + 1
+      declare(structs, m.group(1), fields, pos)
+    else:
+      m = _FUNCTION.match(text, pos) or fail(pos)
+      arguments = [] if m.group(5).strip() == "void" else m.group(5).split(",")
+      declare(functions, m.group(4),
+              (ctype(m, pos), [ctype(_ARGUMENT.fullmatch(a) or fail(pos), pos) for a in arguments]), pos)
+    pos = _SPACE.match(text, m.end()).end()
+  return constants, structs, functions
 
 
-FRAME_PLAN_FIELDS = ("out_bytes", "work_bytes", "zero_begin", "zero_bytes", "prune_cost", "split_score", "counts",
-                     "tile_range", "vis_partial", "indexes", "rows", "screen_scale", "jacobian", "visibility", "image",
-                     "final_T", "last", "median", "count", "offsets", "vals_a", "vals_b", "tvals_a", "tvals_b", "trank_a",
-                     "trank_b", "pair_vis", "seg_tables", "seg_pix", "seg_last", "seg_capacity", "seg_heavy_capacity",
-                     "cull_ws", "sort_ws", "scan_ws", "tsort_ws", "keys_a", "keys_b", "tile_hits", "tkeys_a", "tkeys_b",
-                     "cull_ws_bytes", "sort_ws_bytes", "scan_ws_bytes", "tsort_ws_bytes", "feat_rows")
+def make_mirrors(structs) -> dict:
+  """One ctypes.Structure per parsed struct, under the header's typedef name."""
+  mirrors = {}
+  for name, fields in structs.items():
+    members = []
+    for field, ctype, count in fields:
+      t = C.c_void_p if ctype.endswith("*") else SCALARS.get(ctype) or mirrors[ctype]
+      members.append((field, t * count if count else t))
+    mirrors[name] = type(name, (C.Structure,), {"_fields_": members})
+  return mirrors
 
 
-class GsrFramePlanC(C.Structure):
-  _fields_ = [(name, C.c_int64) for name in FRAME_PLAN_FIELDS]
+def make_prototypes(functions, mirrors) -> dict:
+  """name -> (restype, argtypes) for every parsed function."""
+  def argument(ctype):
+    base = ctype.removeprefix("const ").rstrip("*")
+    if ctype.endswith("*"):
+      return C.POINTER(mirrors[base]) if base in mirrors else C.c_void_p
+    return SCALARS.get(base) or mirrors[base]
+  return {name: (C.c_char_p if ret == "const char*" else argument(ret), [argument(a) for a in args])
+          for name, (ret, args) in functions.items()}
 
 
-class GsrFrameBackwardC(C.Structure):
-  _fields_ = [("position", C.c_void_p), ("log_scaling", C.c_void_p), ("rotation_xyzw", C.c_void_p),
-              ("alpha_logit", C.c_void_p), ("sh_features", C.c_void_p), ("N", C.c_int64), ("K", C.c_int32),
-              ("W", C.c_int32), ("H", C.c_int32), ("C", C.c_int32), ("T_camera_world", C.c_void_p),
-              ("projection", C.c_void_p), ("camera_pos", C.c_void_p), ("params", GsrRasterParamsC), ("M", C.c_int64),
-              ("O", C.c_int64), ("indexes", C.c_void_p), ("rows", C.c_void_p), ("order", C.c_void_p),
-              ("count", C.c_void_p), ("offsets", C.c_void_p), ("sorted_splat", C.c_void_p), ("sorted_inst", C.c_void_p),
-              ("pair_vis", C.c_void_p), ("vis_partial", C.c_void_p), ("tile_range", C.c_void_p), ("final_T", C.c_void_p),
-              ("last", C.c_void_p), ("image", C.c_void_p), ("jacobian", C.c_void_p), ("segments", C.c_void_p),
-              ("d_image", C.c_void_p), ("d_gaussians2d", C.c_void_p), ("d_depth", C.c_void_p), ("partial", C.c_void_p),
-              ("grad_rows", C.c_void_p), ("inverse", C.c_void_p), ("d_colors", C.c_void_p), ("d_position", C.c_void_p),
-              ("d_log_scaling", C.c_void_p), ("d_rotation", C.c_void_p), ("d_alpha_logit", C.c_void_p),
-              ("mode", C.c_int32), ("d_sh", C.c_void_p), ("sh_mode", C.c_int32), ("prune_cost", C.c_void_p),
-              ("split_score", C.c_void_p), ("visibility", C.c_void_p), ("camera_partials", C.c_void_p),
-              ("d_camera", C.c_void_p)]
+with open(HEADER_PATH) as _f:
+  CONSTANTS, STRUCTS, FUNCTIONS = parse_header(_f.read())
+MIRRORS = make_mirrors(STRUCTS)
+# The mirrors are module attributes under the header's typedef names -- GsrRasterParamsC, GsrSegmentsC, GsrFrameC,
+# GsrFramePlanC, GsrFrameResultC, GsrFrameBackwardC, GsrColumnC, GsrColorModel, GsrColorGrads, GsrReg -- injected here:
+# no class statement in this file defines them.
+globals().update(MIRRORS)
+PROTOTYPES = make_prototypes(FUNCTIONS, MIRRORS)
+
+ABI_VERSION = CONSTANTS["GSR_ABI_VERSION"]
+PREFETCH_MIN_ROWS = CONSTANTS["GSR_PREFETCH_MIN_ROWS"]
+MAX_FEATURES = CONSTANTS["GSR_MAX_FEATURES"]
+WIDE_MIN_FEATURES = CONSTANTS["GSR_WIDE_MIN_FEATURES"]
+BILAGRID_MAX_SIDE = CONSTANTS["GSR_BILAGRID_MAX_SIDE"]
+KNN_MAX_K = CONSTANTS["GSR_KNN_MAX_K"]
+NEIGHBOURS_MAX_N = CONSTANTS["GSR_NEIGHBOURS_MAX_N"]
+VISIBILITY_MAX_CAMERAS = CONSTANTS["GSR_VISIBILITY_MAX_CAMERAS"]
+MAX_COLUMNS = CONSTANTS["GSR_MAX_COLUMNS"]
 
 
-class GsrFrameResultC(C.Structure):
-  _fields_ = [("order", C.c_int64), ("sorted_inst", C.c_int64), ("sorted_splat", C.c_int64), ("segments", GsrSegmentsC),
-              ("has_segments", C.c_int32)]
-
-
-class GsrColumnC(C.Structure):
-  _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("tail", C.c_void_p), ("width_dwords", C.c_int32)]
-
-
-MAX_COLUMNS = 32
-
-
-class GsrColorModelC(C.Structure):
-  _fields_ = [("P", C.c_int32), ("G", C.c_int32), ("H", C.c_int32), ("L", C.c_int32), ("S", C.c_int32),
-              ("color_channels", C.c_int32), ("weight", C.c_void_p * 7), ("bias", C.c_void_p * 7)]
-
-
-class GsrColorGradsC(C.Structure):
-  _fields_ = [("d_weight", C.c_void_p * 7), ("d_bias", C.c_void_p * 7), ("d_glo", C.c_void_p),
-              ("d_cam_pos", C.c_void_p)]
-
-
-class GsrRegC(C.Structure):
-  _fields_ = [("idx", C.c_void_p), ("log_scaling", C.c_void_p), ("depths", C.c_void_p), ("opacity", C.c_void_p),
-              ("specular", C.c_void_p), ("visibility", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),
-              ("weight", C.c_float * 4), ("visibility_weighted", C.c_int32)]
-
-
-def raster_params(config) -> GsrRasterParamsC:
+def raster_params(config) -> "GsrRasterParamsC":
   blur = float(config.blur_cov) + (float(config.aa_blur) if config.antialias else 0.0)
-  return GsrRasterParamsC(float(config.alpha_threshold), float(config.clamp_max_alpha),
-                          float(config.transmittance_eps), float(config.gaussian_scale) ** 2, blur,
-                          1 if config.antialias else 0, int(config.tile_size),
-                          float(config.margin_tiles * config.tile_size))
+  return GsrRasterParamsC(                                    # noqa: F821  (injected above)
+      alpha_threshold=float(config.alpha_threshold), clamp_max_alpha=float(config.clamp_max_alpha),
+      T_eps=float(config.transmittance_eps), q_max=float(config.gaussian_scale) ** 2, blur=blur,
+      antialias=1 if config.antialias else 0, tile_size=int(config.tile_size),
+      margin_px=float(config.margin_tiles * config.tile_size))
 
-
-_p = C.c_void_p
-_i64, _i32, _u32, _f, _sz = C.c_int64, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
-_pp = C.POINTER(GsrRasterParamsC)
-_ps = C.POINTER(GsrSegmentsC)
-
-# name -> (restype, argtypes); every symbol declared in include/gsplat_hip.h
-PROTOTYPES = {
-    "gsr_abi_version": (C.c_int, []),
-    "gsr_error_string": (C.c_char_p, [C.c_int]),
-    "gsr_scan_workspace_bytes": (_sz, [_i64]),
-    "gsr_exclusive_scan_u32": (C.c_int, [_p, _p, _i64, _p, _p, _sz, _p]),
-    "gsr_exclusive_scan_u32_checked": (C.c_int, [_p, _p, _i64, _p, _p, _p, _sz, _p]),
-    "gsr_sort_workspace_bytes": (_sz, [_i64]),
-    "gsr_sort_pairs_u32": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.c_int, _p, _sz, _p, _p]),
-    "gsr_sort_pairs2_u32": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, C.c_int, C.c_int, C.c_int, _p, _sz, _p, _p]),
-    "gsr_cull_workspace_bytes": (_sz, [_i64]),
-    "gsr_frustum_cull": (C.c_int, [_p, _i64, _p, _p, _i32, _i32, _f, _f, _f, _p, _p, _p, _sz, _p]),
-    "gsr_project_forward": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _u32, _u32, _p]),
-    "gsr_project_backward": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _i32, _p]),
-    "gsr_camera_grad_partial_rows": (_i64, [_i64]),
-    "gsr_project_backward_camera": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _i32, _p, _p,
-                                              _p]),
-    "gsr_sh_camera_position_grad": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
-    "gsr_camera_grad_finish": (C.c_int, [_p, _i64, _p, _p, _p]),
-    "gsr_sh_forward": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p]),
-    "gsr_sh_backward": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _i32, _p]),
-    "gsr_sh_backward_multi": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i32, _p, _p, _i32, _p]),
-    "gsr_inverse_map": (C.c_int, [_p, _i64, _i64, _p, _p]),
-    "gsr_sh_backward_dense": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p]),
-    "gsr_depth_key_range": (C.c_int, [_f, _f, _p, _p]),
-    "gsr_depth_keys": (C.c_int, [_p, _i64, _u32, _u32, _p, _p]),
-    "gsr_project_sh_forward": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _i64, _p, _p, _p, _pp, _p, _p, _p, _p, _p, _u32,
-                                         _u32, _p]),
-    "gsr_project_backward_rows": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p, _p, _p,
-                                            _p, _p, _i32, _p, _p, _p, _p, _p]),
-    "gsr_project_backward_rows_camera": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _pp, _p, _p, _p, _p, _p,
-                                                   _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_pack_rows": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p]),
-    "gsr_pack_rows_wide": (C.c_int, [_p, _p, _p, _i64, _i32, _pp, _p, _p, _p, _p]),
-    "gsr_tile_count": (C.c_int, [_p, _p, _i64, _i32, _i32, _pp, _p, _p, _p, _p]),
-    "gsr_tile_count_offsets_workspace_bytes": (_sz, [_i64]),
-    "gsr_tile_count_offsets": (C.c_int, [_p, _p, _i64, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "gsr_tile_emit": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _pp, _p, _p, _i64, _p, _p]),
-    "gsr_tile_ranges": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
-    "gsr_segment_thresholds": (C.c_int, [_i32, _i32, _i64, _i32, _i32, _p, _p]),
-    "gsr_segment_capacity": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
-    "gsr_segment_heavy_capacity": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
-    "gsr_segment_plan": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p]),
-    "gsr_composite_forward": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _ps, _i32, _p]),
-    "gsr_composite_backward": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _ps, _p]),
-    "gsr_composite_forward_wide": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_composite_backward_wide": (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _pp, _p, _p, _p, _p, _p]),
-    "gsr_opt_point_weights": (C.c_int, [_p, _p, _i64, _p, _p, _f, _f, _f, _f, _i32, _p, _p]),
-    "gsr_opt_step": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _f, _f, _f, _f, _f, _p]),
-    "gsr_pixel_loss_workspace_bytes": (_sz, [_i64]),
-    "gsr_pixel_loss_forward": (C.c_int, [_p, _p, _i64, _i32, _f, _f, _p, _p, _sz, _p]),
-    "gsr_pixel_loss_backward": (C.c_int, [_p, _p, _i64, _i32, _f, _f, _p, _p, _p]),
-    "gsr_ssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
-    "gsr_ssim_forward": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p]),
-    "gsr_ssim_backward": (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
-    "gsr_msloss_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
-    "gsr_msloss_forward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _f, _p, _p, _sz, _p]),
-    "gsr_msloss_backward": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _f, _p, _p, _sz, _p, _p]),
-    "gsr_select_workspace_bytes": (_sz, [_i64]),
-    "gsr_select_n": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _sz, _p]),
-    "gsr_compact_workspace_bytes": (_sz, [_i64]),
-    "gsr_compact_offsets": (C.c_int, [_p, _i64, _p, _p, _p, _sz, _p]),
-    "gsr_compact_columns": (C.c_int, [_p, _i64, _p, _i64, _i64, C.POINTER(GsrColumnC), _i32, _p]),
-    "gsr_point_basis": (C.c_int, [_p, _p, _p, _i64, _f, _p, _p]),
-    "gsr_dp_pack": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p]),
-    "gsr_dp_replay": (C.c_int, [_p, _i64, _p, _i32, _i64, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_dp_pack_sharded": (C.c_int, [_p, _p, _p, _p, _p, _i32, _p, _i64, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_dp_replay_slice": (C.c_int, [_p, _i32, _i32, _i64, _i32, _i32, _f, _f, _p, _p, _p, _p]),
-    "gsr_dp_finish": (C.c_int, [_p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_point_state_add": (C.c_int, [_p, _p, _i32, _p, _p, _p, _i64, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_frame_plan": (C.c_int, [C.POINTER(GsrFrameC), C.POINTER(GsrFramePlanC)]),
-    "gsr_struct_bytes": (_i64, [_i32]),
-    "gsr_frame_backward": (C.c_int, [C.POINTER(GsrFrameBackwardC), _p, _p, _p]),
-    "gsr_frame_backward_stages": (C.c_int, [C.POINTER(GsrFrameBackwardC), _i32, _p, _p, _p]),
-    "gsr_dp_pack_factors_rows": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p]),
-    "gsr_frame_forward": (C.c_int, [C.POINTER(GsrFrameC), C.POINTER(GsrFramePlanC), _p, _p, C.POINTER(GsrFrameResultC), _p,
-                                    _p, _p, _p, _p]),
-    "gsr_reduce_visibility": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _p, _p]),
-    "gsr_reduce_gradients": (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p]),
-    "gsr_reduce_gradients_wide": (C.c_int, [_p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
-    "gsr_unpack_grad_rows": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
-    "gsr_bilagrid_workspace_bytes": (_sz, [_i32, _i32, _i32]),
-    "gsr_bilagrid_slice_forward": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i64, _p, _i32, _i32, _p, _p]),
-    "gsr_bilagrid_slice_backward": (C.c_int, [_p, _i64, _i32, _i32, _i32, _i64, _p, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
-    "gsr_bilagrid_tv": (C.c_int, [_p, _i64, _i32, _i32, _i32, _f, _p, _p, _i32, _p, _sz, _p]),
-    "gsr_knn_workspace_bytes": (_sz, [_i64, _i32]),
-    "gsr_knn": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
-    "gsr_assign_clusters": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
-    "gsr_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
-    "gsr_kmeans_iter": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
-    "gsr_frustum_counts": (C.c_int, [_p, _i64, _p, _i64, _f, _p, _p, _p]),
-    "gsr_view_features": (C.c_int, [_p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
-    "gsr_color_struct_bytes": (_i64, [_i32]),
-    "gsr_color_supported": (C.c_int, [C.POINTER(GsrColorModelC)]),
-    "gsr_color_forward_workspace_bytes": (_sz, [C.POINTER(GsrColorModelC)]),
-    "gsr_color_backward_workspace_bytes": (_sz, [C.POINTER(GsrColorModelC), _i64]),
-    "gsr_color_forward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
-    "gsr_color_backward": (C.c_int, [C.POINTER(GsrColorModelC), _p, _p, _p, _p, _i64, _p, _p, _p,
-                                     C.POINTER(GsrColorGradsC), _p, _sz, _p]),
-    "gsr_reg_struct_bytes": (_i64, []),
-    "gsr_reg_workspace_bytes": (_sz, [_i64]),
-    "gsr_reg_forward": (C.c_int, [C.POINTER(GsrRegC), _p, _p, _p, _sz, _p]),
-    "gsr_reg_backward": (C.c_int, [C.POINTER(GsrRegC), _p, _p, _p, _p, _p, _p, _p]),
-    "gsr_scene_post_step": (C.c_int, [_p, _p, _i64, _f, _f, _f, _p]),
-}
 
 _lib = None
 _lock = threading.Lock()
@@ -251,10 +180,6 @@ def current_stream() -> "torch.cuda.Stream":
   return torch.cuda.current_stream(torch._C._cuda_getDevice())
 
 
-class GsplatHipError(RuntimeError):
-  pass
-
-
 def load() -> C.CDLL:
   """Loads (once) and returns the HIP library; raises GsplatHipError when it is absent."""
   global _lib
@@ -277,19 +202,16 @@ def load() -> C.CDLL:
       fn.argtypes = argtypes
     if lib.gsr_abi_version() != ABI_VERSION:
       raise GsplatHipError(f"ABI mismatch: library {lib.gsr_abi_version()} != binding {ABI_VERSION}; rebuild")
-    # the ctypes mirrors of the ABI's structs must have the layout the library was compiled with (gsr_struct_bytes)
-    for which, mirror in enumerate((GsrRasterParamsC, GsrSegmentsC, GsrFrameC, GsrFramePlanC, GsrFrameResultC,
-                                    GsrFrameBackwardC)):
-      if lib.gsr_struct_bytes(which) != C.sizeof(mirror):
-        raise GsplatHipError(f"struct layout mismatch: {mirror.__name__} is {C.sizeof(mirror)} bytes in the binding, "
-                             f"{lib.gsr_struct_bytes(which)} in the library; rebuild")
-    for which, mirror in enumerate((GsrColorModelC, GsrColorGradsC)):
-      if lib.gsr_color_struct_bytes(which) != C.sizeof(mirror):
-        raise GsplatHipError(f"struct layout mismatch: {mirror.__name__} is {C.sizeof(mirror)} bytes in the binding, "
-                             f"{lib.gsr_color_struct_bytes(which)} in the library; rebuild")
-    if lib.gsr_reg_struct_bytes() != C.sizeof(GsrRegC):
-      raise GsplatHipError(f"struct layout mismatch: GsrRegC is {C.sizeof(GsrRegC)} bytes in the binding, "
-                           f"{lib.gsr_reg_struct_bytes()} in the library; rebuild")
+    # the mirrors must have the layout the library was compiled with: a stale .so fails here, not in a kernel
+    frame_structs = ("GsrRasterParamsC", "GsrSegmentsC", "GsrFrameC", "GsrFramePlanC", "GsrFrameResultC",
+                     "GsrFrameBackwardC")
+    sized = [(lib.gsr_struct_bytes(i), n) for i, n in enumerate(frame_structs)]
+    sized += [(lib.gsr_color_struct_bytes(i), n) for i, n in enumerate(("GsrColorModel", "GsrColorGrads"))]
+    sized += [(lib.gsr_reg_struct_bytes(), "GsrReg")]
+    for library_bytes, name in sized:
+      if library_bytes != C.sizeof(MIRRORS[name]):
+        raise GsplatHipError(f"struct layout mismatch: {name} is {C.sizeof(MIRRORS[name])} bytes in the binding, "
+                             f"{library_bytes} in the library; rebuild")
     _lib = lib
   return _lib
 

@@ -148,7 +148,7 @@ class _ColorFn(torch.autograd.Function):
       d_glo = torch.empty_like(glo)
       want_cam = ctx.needs_input_grad[4]
       d_cam = torch.empty_like(cam) if want_cam else None
-      grads = _lib.GsrColorGradsC()
+      grads = _lib.GsrColorGrads()
       for i, layer in enumerate(_layer_slots(ctx.L)):
         grads.d_weight[layer] = d_params[2 * i].data_ptr()
         grads.d_bias[layer] = d_params[2 * i + 1].data_ptr()
@@ -221,7 +221,7 @@ class ColorModel(nn.Module):
     params = []
     for lin in self._linears():
       params += [lin.weight, lin.bias]
-    model_c = _lib.GsrColorModelC()
+    model_c = _lib.GsrColorModel()
     model_c.P, model_c.G = self.point_features, self.glo_features
     model_c.H, model_c.L, model_c.S = self.config.hidden_features, self.config.hidden_layers, self.config.sh_degree
     model_c.color_channels = self.config.color_channels

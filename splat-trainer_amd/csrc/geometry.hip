@@ -908,7 +908,7 @@ inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 
 
 extern "C" {
 
-int gsr_abi_version(void) { return 38; }
+int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
 const char* gsr_error_string(int code) {
   switch (code) {

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "gsr_device.h"
+#include "../../include/gsplat_hip.h"
 
 namespace {
 

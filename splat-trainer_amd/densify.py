@@ -85,8 +85,9 @@ def compact_rows(keep_mask: torch.Tensor, columns: Sequence[Tuple[torch.Tensor, 
     width = 1
     for d in col.shape[1:]:
       width *= int(d)
-    arr[i] = _lib.GsrColumnC(col.data_ptr() if N else None, out.data_ptr(),
-                             tail.data_ptr() if (tail is not None and n_tail) else None, max(width, 1))
+    arr[i] = _lib.GsrColumnC(src=col.data_ptr() if N else None, dst=out.data_ptr(),
+                             tail=tail.data_ptr() if (tail is not None and n_tail) else None,
+                             width_dwords=max(width, 1))
   _lib.check(lib.gsr_compact_columns(_p(keep), N, _p(offsets), kept, n_tail, arr, len(cols), stream),
              "gsr_compact_columns")
   return outs

@@ -24,8 +24,8 @@ def _ptr(t: Optional[torch.Tensor]):
   return None if t is None else t.data_ptr()
 
 
-def _args(idx, log_scaling, depths, opacity, specular, visibility, weights, visibility_weighted) -> "_lib.GsrRegC":
-  a = _lib.GsrRegC(idx=_ptr(idx), log_scaling=_ptr(log_scaling), depths=_ptr(depths), opacity=_ptr(opacity),
+def _args(idx, log_scaling, depths, opacity, specular, visibility, weights, visibility_weighted) -> "_lib.GsrReg":
+  a = _lib.GsrReg(idx=_ptr(idx), log_scaling=_ptr(log_scaling), depths=_ptr(depths), opacity=_ptr(opacity),
                    specular=_ptr(specular), visibility=_ptr(visibility), M=int(idx.shape[0]),
                    N=int(log_scaling.shape[0]), visibility_weighted=1 if visibility_weighted else 0)
   for k in range(4):

@@ -30,8 +30,8 @@ from .data_types import CameraParams, Gaussians3D, RasterConfig, RenderedPoints,
 from . import sh as _sh
 from .sh import evaluate_sh_at
 
-ROW_FLOATS = 16          # packed per-splat row (64 bytes; include/gsplat_hip.h GSR_ROW_FLOATS)
-PARTIAL_FLOATS = 12
+ROW_FLOATS = _lib.CONSTANTS["GSR_ROW_FLOATS"]            # packed per-splat row (64 bytes)
+PARTIAL_FLOATS = _lib.CONSTANTS["GSR_PARTIAL_FLOATS"]
 CAMERA_GRAD_FLOATS = 20   # dL/dT_camera_world (4x4) + dL/dprojection (include/gsplat_hip.h: gsr_project_backward_camera)
 
 
@@ -580,11 +580,13 @@ class _RasterFn(torch.autograd.Function):
     else:
       # the native frame driver in projected mode: pack -> depth sort -> K4 -> K5 -> K6 behind one call
       st.order = order
-      frame = _lib.GsrFrameC(None, None, None, None, None, st.M, 1, st.W, st.H, None, None, None, st.near_far[0],
-                             st.near_far[1], st.params, 0, int(st.want_median), int(st.compute_visibility),
-                             int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, g.data_ptr(), d.data_ptr(),
-                             f.data_ptr(), st.C, order.data_ptr() if order is not None else None)
-      frame.feature_table = int(st.C >= _lib.WIDE_MIN_FEATURES)
+      frame = _lib.GsrFrameC(
+          N=st.M, K=1, W=st.W, H=st.H, near_plane=st.near_far[0], far_plane=st.near_far[1], params=st.params,
+          want_median=int(st.want_median), compute_visibility=int(st.compute_visibility),
+          needs_grad=int(bool(st.needs_grad)), seg_pairs=st.seg_pairs, seg_min_pairs=st.seg_min,
+          gaussians2d=g.data_ptr(), depth=d.data_ptr(), features=f.data_ptr(), C=st.C,
+          depth_order=order.data_ptr() if order is not None else None,
+          feature_table=int(st.C >= _lib.WIDE_MIN_FEATURES))
       _, _, _, image = _run_frame(frame, st, g.device, st.M, projected=True)
     ctx.st = st
     ctx.in_dtypes = (g2d.dtype, feats.dtype)      # e.g. fp16 colours from an autocast MLP (mlp_scene.py:362)
@@ -609,17 +611,16 @@ class _RasterFn(torch.autograd.Function):
     return d_g2d.to(ctx.in_dtypes[0]), d_feat.to(ctx.in_dtypes[1]), None, None, None
 
 
-def _arena_view(arena: torch.Tensor, offset: int, shape, dtype=torch.float32) -> torch.Tensor:
-  """A contiguous tensor of ``shape`` at byte ``offset`` of the uint8 arena (one as_strided call on a typed alias)."""
-  typed = arena.view(dtype)
-  size = typed.element_size()
+def _arena_view(typed: torch.Tensor, offset: int, shape) -> torch.Tensor:
+  """A contiguous tensor of ``shape`` at byte ``offset`` of an arena, given the arena's alias of the wanted dtype (one
+  as_strided call; the caller makes the alias once for all its views)."""
   if len(shape) == 1:
     strides = (1,)
   elif len(shape) == 2:
-    strides = (int(shape[1]), 1)
+    strides = (shape[1], 1)
   else:
-    strides = (int(shape[1]) * int(shape[2]), int(shape[2]), 1)
-  return torch.as_strided(typed, shape, strides, offset // size)
+    strides = (shape[1] * shape[2], shape[2], 1)
+  return torch.as_strided(typed, shape, strides, offset // typed.element_size())
 
 
 def _pair_capacity(dev_index, N: int):
@@ -672,10 +673,9 @@ def _run_frame(frame: "_lib.GsrFrameC", st: _RasterState, dev, rows_bound: int, 
   # than the small frames' kernels take); the arena itself stays alive through st.segment_buffers.
   base = out.data_ptr()
   out_f = out.view(torch.float32)
-  V = lambda off, shape, strides: torch.as_strided(out_f, shape, strides, off >> 2)
   st.M, st.O = M, O
-  st.rows = V(plan.rows, (M, ROW_FLOATS), (ROW_FLOATS, 1))
-  st.screen_scale = V(plan.screen_scale, (M, 2), (2, 1))
+  st.rows = _arena_view(out_f, plan.rows, (M, ROW_FLOATS))
+  st.screen_scale = _arena_view(out_f, plan.screen_scale, (M, 2))
   if res.order >= 0:
     st.order = base + res.order
   st.count, st.offsets = base + plan.count, base + plan.offsets
@@ -684,10 +684,10 @@ def _run_frame(frame: "_lib.GsrFrameC", st: _RasterState, dev, rows_bound: int, 
   keep = st.compute_visibility or st.needs_grad
   st.vis_partial = base + plan.vis_partial if keep else None
   st.pair_vis = base + plan.pair_vis if keep else None
-  st.final_T, st.last = V(plan.final_T, (H, W), (W, 1)), base + plan.last
-  st.median = V(plan.median, (H, W), (W, 1)) if st.want_median else None
-  st.visibility = V(plan.visibility, (M,), (1,))
-  st.prune_cost, st.split_score = V(plan.prune_cost, (M,), (1,)), V(plan.split_score, (M,), (1,))
+  st.final_T, st.last = _arena_view(out_f, plan.final_T, (H, W)), base + plan.last
+  st.median = _arena_view(out_f, plan.median, (H, W)) if st.want_median else None
+  st.visibility = _arena_view(out_f, plan.visibility, (M,))
+  st.prune_cost, st.split_score = _arena_view(out_f, plan.prune_cost, (M,)), _arena_view(out_f, plan.split_score, (M,))
   st.vis_capacity = capacity
   st.feat_rows = base + plan.feat_rows if plan.feat_rows >= 0 else None
   if not st.compute_visibility:
@@ -695,7 +695,7 @@ def _run_frame(frame: "_lib.GsrFrameC", st: _RasterState, dev, rows_bound: int, 
   st.vis_ready = not (st.compute_visibility and st.needs_grad)    # without gradients the driver reduced it already
   st.segments = _lib.GsrSegmentsC.from_buffer_copy(res.segments) if res.has_segments else None
   st.segment_buffers = (out,)
-  image = V(plan.image, (H, W, C_), (W * C_, C_, 1))
+  image = _arena_view(out_f, plan.image, (H, W, C_))
   st.image = base + plan.image if st.needs_grad else None
   return out, plan, M, image
 
@@ -720,13 +720,16 @@ class _FrameFn(torch.autograd.Function):
       image = _blank_frame(st, dev)
       indexes, jac = torch.empty(0, dtype=torch.int64, device=dev), None
     else:
-      frame = _lib.GsrFrameC(pos.data_ptr(), ls.data_ptr(), rot.data_ptr(), al.data_ptr(), sh.data_ptr(), N, K, W, H,
-                             T.data_ptr(), proj.data_ptr(), cam.data_ptr(), near, far, st.params,
-                             int(bool(want_jac and K > 1)), int(st.want_median), int(st.compute_visibility),
-                             int(bool(st.needs_grad)), st.seg_pairs, st.seg_min, 0, None, None, None, 3, None)
+      frame = _lib.GsrFrameC(
+          position=pos.data_ptr(), log_scaling=ls.data_ptr(), rotation_xyzw=rot.data_ptr(), alpha_logit=al.data_ptr(),
+          sh_features=sh.data_ptr(), N=N, K=K, W=W, H=H, T_camera_world=T.data_ptr(), projection=proj.data_ptr(),
+          camera_pos=cam.data_ptr(), near_plane=near, far_plane=far, params=st.params,
+          want_jacobian=int(bool(want_jac and K > 1)), want_median=int(st.want_median),
+          compute_visibility=int(st.compute_visibility), needs_grad=int(bool(st.needs_grad)), seg_pairs=st.seg_pairs,
+          seg_min_pairs=st.seg_min, C=3)
       out, plan, M, image = _run_frame(frame, st, dev, N, projected=False)
-      indexes = _arena_view(out, plan.indexes, (M,), torch.int64)
-      jac = _arena_view(out, plan.jacobian, (M, 9)) if plan.jacobian >= 0 else None
+      indexes = _arena_view(out.view(torch.int64), plan.indexes, (M,))
+      jac = _arena_view(out.view(torch.float32), plan.jacobian, (M, 9)) if plan.jacobian >= 0 else None
     rows = st.rows
     ctx.save_for_backward(pos, ls, rot, al, sh, indexes, T, proj, cam)
     ctx.set_materialize_grads(False)       # unused outputs (gaussians2d / depth, usually) arrive as None
@@ -782,13 +785,17 @@ class _FrameFn(torch.autograd.Function):
       if want_cam:
         partials, d_camera = _camera_scratch(M, dev)
       args = _lib.GsrFrameBackwardC(
-          _ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(sh), N, K, st.W, st.H, st.C, _ptr(T), _ptr(proj), _ptr(cam),
-          st.params, M, st.O, _ptr(indexes), _ptr(st.rows), _ptr(st.order), _ptr(st.count), _ptr(st.offsets),
-          _ptr(st.sorted_splat), _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.vis_partial), _ptr(st.tile_range),
-          _ptr(st.final_T), _ptr(st.last), _ptr(st.image), _ptr(ctx.jac), seg, _ptr(dimg), _ptr(dg), _ptr(dd),
-          _ptr(partial), _ptr(grows), _ptr(inv), _ptr(dcol), _ptr(d_pos), _ptr(d_ls), _ptr(d_rot), _ptr(d_al), mode,
-          _ptr(d_sh), sh_mode, _ptr(st.prune_cost), _ptr(st.split_score), _ptr(_vis_out(st, live)), _ptr(partials),
-          _ptr(d_camera))
+          position=_ptr(pos), log_scaling=_ptr(ls), rotation_xyzw=_ptr(rot), alpha_logit=_ptr(al), sh_features=_ptr(sh),
+          N=N, K=K, W=st.W, H=st.H, C=st.C, T_camera_world=_ptr(T), projection=_ptr(proj), camera_pos=_ptr(cam),
+          params=st.params, M=M, O=st.O, indexes=_ptr(indexes), rows=_ptr(st.rows), order=_ptr(st.order),
+          count=_ptr(st.count), offsets=_ptr(st.offsets), sorted_splat=_ptr(st.sorted_splat),
+          sorted_inst=_ptr(st.sorted_inst), pair_vis=_ptr(st.pair_vis), vis_partial=_ptr(st.vis_partial),
+          tile_range=_ptr(st.tile_range), final_T=_ptr(st.final_T), last=_ptr(st.last), image=_ptr(st.image),
+          jacobian=_ptr(ctx.jac), segments=seg, d_image=_ptr(dimg), d_gaussians2d=_ptr(dg), d_depth=_ptr(dd),
+          partial=_ptr(partial), grad_rows=_ptr(grows), inverse=_ptr(inv), d_colors=_ptr(dcol), d_position=_ptr(d_pos),
+          d_log_scaling=_ptr(d_ls), d_rotation=_ptr(d_rot), d_alpha_logit=_ptr(d_al), mode=mode, d_sh=_ptr(d_sh),
+          sh_mode=sh_mode, prune_cost=_ptr(st.prune_cost), split_score=_ptr(st.split_score),
+          visibility=_ptr(_vis_out(st, live)), camera_partials=_ptr(partials), d_camera=_ptr(d_camera))
       early = getattr(collector, "on_rows", None) if collector is not None else None
       if early is not None and M > 0:
         # data-parallel: K7 + reduction first; the caller packs the colour-gradient factors straight from the packed rows

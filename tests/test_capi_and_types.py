@@ -1,9 +1,12 @@
 """The C-ABI library loads and exports every symbol include/gsplat_hip.h declares (no compute calls: there
-is no GPU here), the ctypes binding covers exactly that set, the product path refuses CPU tensors and a
-missing library (no fallback), and the boundary types behave as the reference's consumers expect."""
+is no GPU here), the ctypes binding derived from that header covers exactly that set with the signatures and struct
+layouts the C++ compiler reads from it, the product path refuses CPU tensors and a missing library (no fallback), and
+the boundary types behave as the reference's consumers expect."""
+import copy
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -29,9 +32,102 @@ def test_library_exports_every_declared_symbol(built_libs):
   assert sorted(_lib.PROTOTYPES) == syms, "ctypes binding and header disagree"
 
 
+def _abi_translation_unit(constants, structs, functions) -> str:
+  """C++ that compiles exactly when the parsed constants, field types and signatures, and the layouts of the mirrors made
+  from them, are the ones the compiler reads from the header."""
+  mirrors = _lib.make_mirrors(structs)
+  tu = ["#include <cstddef>", "#include <type_traits>", f'#include "{_lib.HEADER_PATH}"']
+  for ctype, scalar in _lib.SCALARS.items():            # the scalar half of the type rule
+    tu.append(f"static_assert(sizeof({ctype}) == {C.sizeof(scalar)} && std::is_floating_point<{ctype}>::value == "
+              f"{int(scalar is C.c_float)} && std::is_signed<{ctype}>::value == {int(scalar(-1).value < 0)}, "
+              f"\"{ctype}\");")
+  for name, value in constants.items():
+    tu.append(f"static_assert({name} == {value}, \"{name}\");")
+  for name, (ret, args) in functions.items():
+    tu.append(f"static_assert(std::is_same<decltype(&{name}), {ret} (*)({', '.join(args)})>::value, \"{name}\");")
+  for name, fields in structs.items():
+    tu.append(f"static_assert(sizeof({name}) == {C.sizeof(mirrors[name])}, \"sizeof {name}\");")
+    for field, ctype, count in fields:
+      member, declared = getattr(mirrors[name], field), ctype + (f"[{count}]" if count else "")
+      tu.append(f"static_assert(std::is_same<decltype({name}::{field}), {declared}>::value && offsetof({name}, {field})"
+                f" == {member.offset} && sizeof({name}::{field}) == {member.size}, \"{name}.{field}\");")
+  return "\n".join(tu) + "\n"
+
+
+def _compile_abi(tmp_path, tag, constants=_lib.CONSTANTS, structs=_lib.STRUCTS, functions=_lib.FUNCTIONS):
+  src = tmp_path / f"abi_{tag}.cpp"
+  src.write_text(_abi_translation_unit(constants, structs, functions))
+  return subprocess.run(["g++", "-std=c++17", "-fsyntax-only", str(src)], capture_output=True, text=True)
+
+
+def test_compiler_agrees_with_the_derived_binding(tmp_path):
+  """The C++ compiler referees the header parser against the real header: one static_assert per constant on its value,
+  per entry point on its whole signature, per struct on its size and per field on its declared type, offset and size.
+  A misread must not compile: shown on copies of the derived data with one argument type altered, one pair of
+  same-typed fields swapped, one float field read as int32_t (same size, same offset) and one constant misread."""
+  assert sorted(_lib.FUNCTIONS) == _header_symbols()
+  declared = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S).count("typedef struct")
+  assert len(_lib.STRUCTS) == declared >= 10
+  ok = _compile_abi(tmp_path, "derived")
+  assert ok.returncode == 0, ok.stderr
+
+  def failed_asserts(run):
+    assert run.returncode != 0
+    return sorted(re.findall(r"static assertion failed: (\S+)", run.stderr))
+
+  functions = copy.deepcopy(_lib.FUNCTIONS)
+  args = functions["gsr_segment_capacity"][1]
+  assert args[:2] == ["int64_t", "int32_t"]
+  args[1] = "int64_t"                                   # a swapped _i32 / _i64: corrupts the call silently at run time
+  assert failed_asserts(_compile_abi(tmp_path, "argtype", functions=functions)) == ["gsr_segment_capacity"]
+
+  structs = copy.deepcopy(_lib.STRUCTS)
+  fields = structs["GsrFrameBackwardC"]
+  i = [f[0] for f in fields].index("d_image")
+  assert fields[i + 1][0] == "d_gaussians2d" and fields[i][1:] == fields[i + 1][1:]     # two interchangeable pointers
+  fields[i], fields[i + 1] = fields[i + 1], fields[i]
+  assert failed_asserts(_compile_abi(tmp_path, "order", structs=structs)) == ["GsrFrameBackwardC.d_gaussians2d",
+                                                                              "GsrFrameBackwardC.d_image"]
+
+  structs = copy.deepcopy(_lib.STRUCTS)
+  fields = structs["GsrFrameC"]
+  i = [f[0] for f in fields].index("near_plane")
+  assert fields[i] == ("near_plane", "float", 0)
+  fields[i] = ("near_plane", "int32_t", 0)              # same size and offset: the mirror would truncate without notice
+  assert failed_asserts(_compile_abi(tmp_path, "fieldtype", structs=structs)) == ["GsrFrameC.near_plane"]
+
+  constants = dict(_lib.CONSTANTS, GSR_NEIGHBOURS_MAX_N=7)
+  assert failed_asserts(_compile_abi(tmp_path, "constant", constants=constants)) == ["GSR_NEIGHBOURS_MAX_N"]
+
+
+@pytest.mark.parametrize("malformed", ["int gsr_bad(float (*callback)(int), void* stream);",
+                                       "int gsr_bad(double x);",
+                                       "typedef struct GsrBad { float* a, *b; } GsrBad;",
+                                       "typedef struct GsrBad { int32_t n; GsrUnknown inner; } GsrBad;",
+                                       "#define GSR_BAD (1 << 4)",
+                                       "#define GSR_OK 1",                       # a name declared twice
+                                       "int gsr_abi_version(void);",
+                                       "typedef struct GsrSegmentsC { int32_t n; } GsrSegmentsC;",
+                                       "#pragma pack(1)",                        # directives that change what is compiled
+                                       "#if 0",
+                                       "#else",
+                                       "static const int gsr_bad = 3;"])
+def test_unparsable_declaration_raises_with_its_line(malformed):
+  """Nothing in the header is skipped silently: a declaration the parser cannot read, a repeated name and a directive
+  that could change what the compiler sees stop the import, naming the line."""
+  lines = open(_lib.HEADER_PATH).read().split("\n")
+  at = next(i for i, line in enumerate(lines) if line.startswith("size_t gsr_scan_workspace_bytes"))
+  lines.insert(at, malformed)
+  with pytest.raises(_lib.GsplatHipError, match=rf"gsplat_hip\.h:{at + 1}: "):
+    _lib.parse_header("\n".join(lines))
+  del lines[at]
+  assert _lib.parse_header("\n".join(lines)) == (_lib.CONSTANTS, _lib.STRUCTS, _lib.FUNCTIONS)
+
+
 def test_host_only_entry_points(built_libs):
   lib = _lib.load()
   assert lib.gsr_abi_version() == _lib.ABI_VERSION
+  assert _lib.ABI_VERSION == _lib.CONSTANTS["GSR_ABI_VERSION"] == 38
   assert lib.gsr_error_string(-2).decode() == "workspace too small"
   assert lib.gsr_sort_workspace_bytes(0) > 0
   assert lib.gsr_sort_workspace_bytes(10_000_000) >= (10_000_000 // 4096) * 256 * 4
@@ -45,6 +141,10 @@ def test_host_only_entry_points(built_libs):
                                   _lib.GsrFrameResultC, _lib.GsrFrameBackwardC)):
     assert lib.gsr_struct_bytes(which) == C.sizeof(mirror), mirror.__name__
   assert lib.gsr_struct_bytes(6) == -1
+  for which, mirror in enumerate((_lib.GsrColorModel, _lib.GsrColorGrads)):
+    assert lib.gsr_color_struct_bytes(which) == C.sizeof(mirror), mirror.__name__
+  assert lib.gsr_color_struct_bytes(2) == -1
+  assert lib.gsr_reg_struct_bytes() == C.sizeof(_lib.GsrReg)
 
 
 def test_frame_plan_lays_out_disjoint_aligned_buffers_by_field_name(built_libs):

@@ -227,7 +227,8 @@ def test_tile_count_with_offsets_equals_count_then_scan(m, visible):
   rows[:, 5] = 0.05 + 0.9 * torch.rand(m, generator=gen)
   rows = rows.cuda()
   order = torch.randperm(m, generator=gen).to(torch.int32).cuda()
-  params = _lib.GsrRasterParamsC(1.0 / 255.0, 0.99, 1e-4, 9.0, 0.3, 0, 16, 48.0)
+  params = _lib.GsrRasterParamsC(alpha_threshold=1.0 / 255.0, clamp_max_alpha=0.99, T_eps=1e-4, q_max=9.0, blur=0.3,
+                                 antialias=0, tile_size=16, margin_px=48.0)
   m_dev = torch.tensor([visible], dtype=torch.int32, device="cuda") if visible is not None else None
   mp = _ptr(m_dev) if m_dev is not None else None
   outs = []
