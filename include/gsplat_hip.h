@@ -81,11 +81,14 @@ typedef struct GsrSegmentsC {
   int64_t capacity;           /* from gsr_segment_capacity */
   int64_t heavy_capacity;     /* from gsr_segment_heavy_capacity (<= capacity) */
   float* seg_P;               /* [capacity,256] */
-  float* seg_TC;              /* [capacity,256,4], 16-byte aligned: (T, c0, c1, c2) per pixel slot */
+  float* seg_TC;              /* [capacity,256,4], 16-byte aligned: (T, c0, c1, c2) per pixel slot; a wide frame keeps
+                                 only T here, [capacity,256], and its colours in seg_col */
   int32_t* seg_last;          /* [capacity,256] */
   float* seg_median;          /* [capacity,256]; NULL unless a median depth image is requested */
   const uint32_t* tile_order; /* [GSR_TILE_ORDER_WORDS(num_tiles)]: the forward pass's launch order (tiles by XCD band and
                                  length class, filled by gsr_segment_plan), or NULL: tiles in image order */
+  float* seg_col;             /* wide frames only (NULL otherwise): [capacity, CW/4, 256, 4], 16-byte aligned: channels
+                                 4q .. 4q+3 of the colour composited up to the segment's end, per pixel slot */
 } GsrSegmentsC;
 #define GSR_SEG_TOTAL_WORDS 272
 #define GSR_TILE_ORDER_WORDS(num_tiles) (8 * 32 * ((((num_tiles) + 127) / 128) * 16))
@@ -317,6 +320,20 @@ int gsr_segment_plan(const uint32_t* tile_range, int32_t num_tiles, int32_t seg_
                      int32_t needs_grad, int64_t O, const uint32_t* O_dev, int64_t capacity, int64_t heavy_capacity,
                      uint32_t* tile_seg_out, uint32_t* seg_desc_out, uint32_t* seg_total_out, uint32_t* tile_order_out,
                      void* stream);
+/* The same four with the frame's kind: wide = 1 for a frame of GSR_WIDE_MIN_FEATURES or more channels (0: the entry
+ * points above).  Explicit thresholds mean the same for both kinds; only the automatic segment length with gradients
+ * differs (256 pairs for a wide frame, whose checkpoints are 1 + CW floats per pixel), and it does not depend on the
+ * channel count. */
+int gsr_segment_thresholds_wide(int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int64_t O, int32_t num_tiles,
+                                int32_t needs_grad, int32_t wide, int32_t* seg_pairs_out, int32_t* heavy_min_out);
+int64_t gsr_segment_capacity_wide(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                                  int32_t num_tiles, int32_t needs_grad, int32_t wide);
+int64_t gsr_segment_heavy_capacity_wide(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                                        int32_t num_tiles, int32_t needs_grad, int32_t wide);
+int gsr_segment_plan_wide(const uint32_t* tile_range, int32_t num_tiles, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                          int32_t needs_grad, int32_t wide, int64_t O, const uint32_t* O_dev, int64_t capacity,
+                          int64_t heavy_capacity, uint32_t* tile_seg_out, uint32_t* seg_desc_out, uint32_t* seg_total_out,
+                          uint32_t* tile_order_out, void* stream);
 
 /* ---- K6 alpha-composite forward ------------------------------------------------------------------------- */
 /* image [H,W,C]; final_T [H,W]; last [H,W] int32 = 1 + list position of the last contributing splat;
@@ -334,9 +351,15 @@ int gsr_composite_forward(const float* rows /* [M,16] */, const uint32_t* sorted
                                                    readable that far (gsr_frame_plan sizes it so) */,
                           void* stream);
 /* Wide frames (GSR_WIDE_MIN_FEATURES <= C <= GSR_MAX_FEATURES): the features come from feat_rows [M,CW]
- * (gsr_pack_rows_wide), every tile is composited by one wave (no segments); image [H,W,C], the other outputs as
- * gsr_composite_forward.  Channels, final_T, last, median and the visibility partials are bit-identical to
- * gsr_composite_forward without segments for the same splats. */
+ * (gsr_pack_rows_wide); image [H,W,C], the other outputs as gsr_composite_forward.  Channels, final_T, last, median and
+ * the visibility partials are bit-identical to gsr_composite_forward for the same splats and the same segments.
+ * gsr_composite_forward_wide composites every tile with one wave (no segments); the _seg form takes the segment tables
+ * of gsr_segment_plan with the wide pixel slots (GsrSegmentsC: seg_TC holds T only, seg_col the colours), or NULL. */
+int gsr_composite_forward_wide_seg(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
+                                   const uint32_t* sorted_splat, const uint32_t* sorted_inst, const uint32_t* tile_range,
+                                   int32_t W, int32_t H, int32_t C, const GsrRasterParamsC* params_host, float* image_out,
+                                   float* final_T_out, int32_t* last_out, float* median_depth_out, float* vis_partial_out,
+                                   float* pair_vis_out, const GsrSegmentsC* segments_host /* or NULL */, void* stream);
 int gsr_composite_forward_wide(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
                                const uint32_t* sorted_splat, const uint32_t* sorted_inst, const uint32_t* tile_range,
                                int32_t W, int32_t H, int32_t C, const GsrRasterParamsC* params_host, float* image_out,
@@ -354,7 +377,16 @@ int gsr_composite_backward(const float* rows /* [M,16] */, const uint32_t* sorte
                            const float* dL_dimage, const float* image /* the forward output; needed with segments */,
                            float* partial_out, const GsrSegmentsC* segments_host /* the forward pass's, or NULL */,
                            void* stream);
-/* Wide frames: partial_out [O, 8 + CW] (see GSR_WIDE_MIN_FEATURES), written only for pairs with pair_vis > 0. */
+/* Wide frames: partial_out [O, 8 + CW] (see GSR_WIDE_MIN_FEATURES), written only for pairs with pair_vis > 0.  The _seg
+ * form takes the forward pass's segments (or NULL) and, with them, the forward image: every segment gets a wave of its
+ * own, entered from its checkpoint. */
+int gsr_composite_backward_wide_seg(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
+                                    const uint32_t* sorted_splat, const uint32_t* sorted_inst, const float* pair_vis,
+                                    const uint32_t* tile_range, int32_t W, int32_t H, int32_t C,
+                                    const GsrRasterParamsC* params_host, const float* final_T, const int32_t* last,
+                                    const float* dL_dimage, const float* image /* the forward output; needed with segments */,
+                                    float* partial_out, const GsrSegmentsC* segments_host /* the forward pass's, or NULL */,
+                                    void* stream);
 int gsr_composite_backward_wide(const float* rows /* [M,16] */, const float* feat_rows /* [M,CW] */,
                                 const uint32_t* sorted_splat, const uint32_t* sorted_inst, const float* pair_vis,
                                 const uint32_t* tile_range, int32_t W, int32_t H, int32_t C,
@@ -421,7 +453,7 @@ typedef struct GsrFrameC {
   int32_t C;                    /* 1..3, or up to GSR_MAX_FEATURES with feature_table (3 in the one-call form) */
   const uint32_t* depth_order;  /* [N] or NULL: the depth order when the caller has it already (skips the depth sort) */
   /* Projected mode: 1 = the caller takes C >= GSR_WIDE_MIN_FEATURES through the wide path (the plan lays out the
-   * feature table feat_rows, K6 wide composites every tile with one wave: seg_pairs is ignored); 0 = C <= 3 only. */
+   * feature table feat_rows and, with seg_pairs != 0, the wide segment slots); 0 = C <= 3 only. */
   int32_t feature_table;
 } GsrFrameC;
 /* Byte offsets of the frame's buffers inside the two caller-owned arenas (-1: not present in this frame).  `out`:
@@ -439,6 +471,8 @@ typedef struct GsrFramePlanC {
   int64_t cull_ws, sort_ws, scan_ws, tsort_ws, keys_a, keys_b, tile_hits, tkeys_a, tkeys_b;
   int64_t cull_ws_bytes, sort_ws_bytes, scan_ws_bytes, tsort_ws_bytes;
   int64_t feat_rows;            /* out arena: [N,CW] feature table of a wide frame, -1 otherwise */
+  int64_t seg_col;              /* out arena: [seg_capacity, CW/4, 256, 4] colour checkpoints of a segmented wide frame (its
+                                   seg_pix holds T, the alpha products and the median: one plane each), -1 otherwise */
 } GsrFramePlanC;
 /* Where the ping-pong sorts left their results (byte offsets into `out`) and the segment tables of the frame. */
 typedef struct GsrFrameResultC {

@@ -784,8 +784,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
 // segment end -- and gains from finer work units (measured: K7 -5 % on c2 at 64-pair segments, -13..20 % on c3 at
 // 256..128), so with gradients a tile is cut into about six segments (mean list length / 6 within [64, 256], multiple
 // of 4); without gradients only heavy tiles are cut, into segments half a threshold long.
+// Wide frames (4..16 channels, composite_wide.inc) share everything but the automatic segment length with gradients: a
+// checkpoint there is (1 + CW) KB per segment end instead of 4 KB, and on a frame of evenly short lists writing and
+// reading them back costs more than the finer backward units gain (c2 geometry, step of C = 4 / 8 / 16: 64-pair
+// segments +3 / +13 / +30 % over no segments, 256-pair segments +2 / +2 / 0 %, profiles/r15_wide_segments.txt), so they
+// take the top of the range above, 256 pairs, whatever the mean -- and whatever the channel count: renders of the same
+// splats with different channel counts are cut alike, so splitting channels over two renders gives the same bits.
 __host__ __device__ inline void segment_thresholds(int32_t seg_cfg, int32_t heavy_cfg, int64_t O, int32_t num_tiles,
-                                                   int32_t needs_grad, uint32_t* seg_out, uint32_t* heavy_out) {
+                                                   int32_t needs_grad, int32_t wide, uint32_t* seg_out,
+                                                   uint32_t* heavy_out) {
   if (O < 0) O = 0;
   int64_t heavy = heavy_cfg > 0 ? (int64_t)heavy_cfg : 120 + O / 2900;
   if (heavy_cfg <= 0 && heavy < 512) heavy = 512;
@@ -793,7 +800,9 @@ __host__ __device__ inline void segment_thresholds(int32_t seg_cfg, int32_t heav
   if (seg_cfg > 0) {
     seg = seg_cfg;
   } else {
-    if (needs_grad) {
+    if (needs_grad && wide) {
+      seg = 256;
+    } else if (needs_grad) {
       const int64_t per = 6 * (int64_t)(num_tiles > 0 ? num_tiles : 1);
       seg = (O / per + 3) & ~(int64_t)3;
       seg = seg < 64 ? 64 : (seg > 256 ? 256 : seg);
@@ -810,7 +819,8 @@ __host__ __device__ inline void segment_thresholds(int32_t seg_cfg, int32_t heav
 
 __global__ __launch_bounds__(256) void segment_plan_kernel(const uint32_t* __restrict__ tile_range, int num_tiles,
                                                            int32_t seg_cfg, int32_t heavy_cfg, int32_t needs_grad,
-                                                           int64_t O, const uint32_t* __restrict__ O_dev,
+                                                           int32_t wide, int64_t O,
+                                                           const uint32_t* __restrict__ O_dev,
                                                            uint32_t capacity, uint32_t heavy_capacity,
                                                            uint32_t* __restrict__ tile_seg,
                                                            uint32_t* __restrict__ seg_desc,
@@ -828,7 +838,7 @@ __global__ __launch_bounds__(256) void segment_plan_kernel(const uint32_t* __res
   if (t < num_tiles) {
     uint32_t seg_pairs, heavy_min;
     const int64_t O_now = O_dev ? (int64_t)*O_dev : O;
-    segment_thresholds(seg_cfg, heavy_cfg, O_now, num_tiles, needs_grad, &seg_pairs, &heavy_min);
+    segment_thresholds(seg_cfg, heavy_cfg, O_now, num_tiles, needs_grad, wide, &seg_pairs, &heavy_min);
     const uint32_t a = tile_range[2 * t], len = tile_range[2 * t + 1] - a;
     // a heavy tile's segments are also FORWARD work units (alpha-product pass + a prologue over the preceding segments):
     // about 256 pairs each and at most ~128 per tile; a long tile's segments are only checkpoints: seg_pairs each
@@ -909,24 +919,31 @@ inline bool seg_ok(const GsrSegmentsC* sg, bool median) {
 
 extern "C" {
 
-int gsr_segment_thresholds(int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int64_t O, int32_t num_tiles, int32_t needs_grad,
-                           int32_t* seg_pairs_out, int32_t* heavy_min_out) {
+int gsr_segment_thresholds_wide(int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int64_t O, int32_t num_tiles,
+                                int32_t needs_grad, int32_t wide, int32_t* seg_pairs_out, int32_t* heavy_min_out) {
   if (!seg_pairs_out || !heavy_min_out || num_tiles <= 0) return GSR_ERR_INVALID_ARGUMENT;
   uint32_t seg, heavy;
-  segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, &seg, &heavy);
+  segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, wide, &seg, &heavy);
   *seg_pairs_out = (int32_t)seg;
   *heavy_min_out = (int32_t)heavy;
   return GSR_OK;
 }
 
-int64_t gsr_segment_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int32_t num_tiles,
-                             int32_t needs_grad) {
+int gsr_segment_thresholds(int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int64_t O, int32_t num_tiles, int32_t needs_grad,
+                           int32_t* seg_pairs_out, int32_t* heavy_min_out) {
+  return gsr_segment_thresholds_wide(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, 0, seg_pairs_out,
+                                     heavy_min_out);
+}
+
+int64_t gsr_segment_capacity_wide(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                                  int32_t num_tiles, int32_t needs_grad, int32_t wide) {
   if (O <= 0 || num_tiles <= 0) return 0;
   // a tile of len pairs (len > seg) yields at most ceil(len / seg) <= len / seg + 1 segments, and at most
   // min(tiles, O / (seg + 1)) tiles are that long
-  if (!O_is_bound || seg_pairs_cfg > 0) {
+  // (a wide frame's automatic length with gradients does not depend on the count: the exact formula holds for a bound too)
+  if (!O_is_bound || seg_pairs_cfg > 0 || (wide && needs_grad)) {
     uint32_t seg, heavy;
-    segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, &seg, &heavy);
+    segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, wide, &seg, &heavy);
     return O / seg + O / ((int64_t)seg + 1) + 1;
   }
   // only a bound on the pair count is known and the segment length follows the true count: for any count <= O the
@@ -939,14 +956,19 @@ int64_t gsr_segment_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cf
   return by_min < by_rule ? by_min : by_rule;
 }
 
-int64_t gsr_segment_heavy_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
-                                   int32_t num_tiles, int32_t needs_grad) {
+int64_t gsr_segment_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg, int32_t num_tiles,
+                             int32_t needs_grad) {
+  return gsr_segment_capacity_wide(O, O_is_bound, seg_pairs_cfg, heavy_min_cfg, num_tiles, needs_grad, 0);
+}
+
+int64_t gsr_segment_heavy_capacity_wide(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                                        int32_t num_tiles, int32_t needs_grad, int32_t wide) {
   if (O <= 0 || num_tiles <= 0) return 0;
   // a heavy tile (len > heavy) is cut into pieces of at least seg_heavy = max(seg, min(256, heavy / 2)) pairs
   uint32_t seg, heavy;
-  segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, &seg, &heavy);
+  segment_thresholds(seg_pairs_cfg, heavy_min_cfg, O, num_tiles, needs_grad, wide, &seg, &heavy);
   if (O_is_bound && heavy_min_cfg <= 0) heavy = 512;                 // the automatic threshold of any smaller count
-  if (O_is_bound && seg_pairs_cfg <= 0) seg = needs_grad ? 64 : 256;
+  if (O_is_bound && seg_pairs_cfg <= 0) seg = (needs_grad && !wide) ? 64 : 256;
   uint32_t piece = (heavy / 2u) & ~3u;
   if (piece > 256u) piece = 256u;
   if (piece < seg) piece = seg;
@@ -954,17 +976,30 @@ int64_t gsr_segment_heavy_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pa
   return O / piece + O / ((int64_t)heavy + 1) + 1;
 }
 
+int64_t gsr_segment_heavy_capacity(int64_t O, int32_t O_is_bound, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                                   int32_t num_tiles, int32_t needs_grad) {
+  return gsr_segment_heavy_capacity_wide(O, O_is_bound, seg_pairs_cfg, heavy_min_cfg, num_tiles, needs_grad, 0);
+}
+
 int gsr_segment_plan(const uint32_t* tile_range, int32_t num_tiles, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
                      int32_t needs_grad, int64_t O, const uint32_t* O_dev, int64_t capacity, int64_t heavy_capacity,
                      uint32_t* tile_seg_out, uint32_t* seg_desc_out, uint32_t* seg_total_out, uint32_t* tile_order_out,
                      void* stream_) {
+  return gsr_segment_plan_wide(tile_range, num_tiles, seg_pairs_cfg, heavy_min_cfg, needs_grad, 0, O, O_dev, capacity,
+                               heavy_capacity, tile_seg_out, seg_desc_out, seg_total_out, tile_order_out, stream_);
+}
+
+int gsr_segment_plan_wide(const uint32_t* tile_range, int32_t num_tiles, int32_t seg_pairs_cfg, int32_t heavy_min_cfg,
+                          int32_t needs_grad, int32_t wide, int64_t O, const uint32_t* O_dev, int64_t capacity,
+                          int64_t heavy_capacity, uint32_t* tile_seg_out, uint32_t* seg_desc_out, uint32_t* seg_total_out,
+                          uint32_t* tile_order_out, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (num_tiles <= 0 || capacity <= 0 || capacity > 0x7fffffffll || (O < 0 && !O_dev)) return GSR_ERR_INVALID_ARGUMENT;
   if (heavy_capacity < 0 || heavy_capacity > capacity) return GSR_ERR_INVALID_ARGUMENT;
   if (seg_pairs_cfg > 0 && heavy_min_cfg > 0 && heavy_min_cfg < seg_pairs_cfg) return GSR_ERR_INVALID_ARGUMENT;
   if (!tile_range || !tile_seg_out || !seg_desc_out || !seg_total_out) return GSR_ERR_INVALID_ARGUMENT;
   segment_plan_kernel<<<(num_tiles + 255) / 256, 256, 0, stream>>>(tile_range, num_tiles, seg_pairs_cfg, heavy_min_cfg,
-                                                                  needs_grad, O, O_dev, (uint32_t)capacity,
+                                                                  needs_grad, wide, O, O_dev, (uint32_t)capacity,
                                                                   (uint32_t)heavy_capacity, tile_seg_out, seg_desc_out,
                                                                   seg_total_out, tile_order_out);
   GSR_CHECK_LAUNCH();

@@ -59,7 +59,7 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
   const bool projected = f->position == nullptr;
   if (!projected && f->K != 1 && f->K != 4 && f->K != 9 && f->K != 16) return GSR_ERR_UNSUPPORTED;
   if (f->C < 1 || f->C > GSR_MAX_FEATURES || (!projected && f->C != 3)) return GSR_ERR_UNSUPPORTED;
-  const bool wide = f->C >= GSR_WIDE_MIN_FEATURES;         // features in their own table, unsegmented composite
+  const bool wide = f->C >= GSR_WIDE_MIN_FEATURES;         // features in their own table
   if (wide && !f->feature_table) return GSR_ERR_UNSUPPORTED;
   if (f->params.tile_size != 16) return GSR_ERR_UNSUPPORTED;
   memset(p, 0, sizeof(*p));
@@ -95,22 +95,28 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
   p->trank_a = out.take(4 * cap + 16);         // (+ 3 words: K6's large-frame walk fetches list words four at a time)
   p->trank_b = out.take(4 * cap + 16);
   p->pair_vis = vis_partial ? out.take(4 * cap) : -1;
-  p->feat_rows = wide ? out.take(4 * (f->C <= 4 ? 4 : f->C <= 8 ? 8 : 16) * N) : -1;
+  const int64_t CW = f->C <= 4 ? 4 : f->C <= 8 ? 8 : 16;
+  p->feat_rows = wide ? out.take(4 * CW * N) : -1;
   // segment tables and pixel slots (forward checkpoints read by the backward pass)
   p->seg_capacity = 0;
   p->seg_heavy_capacity = 0;
-  p->seg_tables = p->seg_pix = p->seg_last = -1;
-  if (f->seg_pairs != 0 && cap > 0 && !wide) {
-    const int64_t sc = gsr_segment_capacity(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T, f->needs_grad ? 1 : 0);
+  p->seg_tables = p->seg_pix = p->seg_last = p->seg_col = -1;
+  if (f->seg_pairs != 0 && cap > 0) {
+    const int64_t sc = gsr_segment_capacity_wide(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T, f->needs_grad ? 1 : 0,
+                                                 wide ? 1 : 0);
     if (sc > 0) {
-      int64_t hc = gsr_segment_heavy_capacity(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T, f->needs_grad ? 1 : 0);
+      int64_t hc = gsr_segment_heavy_capacity_wide(cap, 1, f->seg_pairs, f->seg_min_pairs, (int32_t)T,
+                                                   f->needs_grad ? 1 : 0, wide ? 1 : 0);
       if (hc > sc) hc = sc;
       p->seg_capacity = sc;
       p->seg_heavy_capacity = hc;
       p->seg_tables = out.take(4 * (2 * T + hc + 4 * sc + GSR_TILE_ORDER_WORDS(T)));
-      const int64_t planes = 5 + (f->want_median ? 1 : 0);
+      // pixel planes: (T, c0, c1, c2) + alpha products (+ median); a wide frame keeps T alone next to them and its
+      // colours, CW per pixel slot, in a buffer of their own
+      const int64_t planes = (wide ? 2 : 5) + (f->want_median ? 1 : 0);
       p->seg_pix = out.take(4 * planes * sc * 256);
       p->seg_last = out.take(4 * sc * 256);
+      if (wide) p->seg_col = out.take(4 * CW * sc * 256);
     }
   }
   p->out_bytes = out.at;
@@ -244,8 +250,9 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
       uint32_t* seg_desc = tables + 2 * (int64_t)T + p->seg_heavy_capacity;
       uint32_t* seg_total = counts + 3;
       uint32_t* tile_order = seg_desc + 4 * p->seg_capacity;
-      GSR_TRY(gsr_segment_plan(tile_range, T, f->seg_pairs, f->seg_min_pairs, f->needs_grad ? 1 : 0, cap, O_dev,
-                               p->seg_capacity, p->seg_heavy_capacity, tile_seg, seg_desc, seg_total, tile_order, stream_));
+      GSR_TRY(gsr_segment_plan_wide(tile_range, T, f->seg_pairs, f->seg_min_pairs, f->needs_grad ? 1 : 0,
+                                    p->feat_rows >= 0 ? 1 : 0, cap, O_dev, p->seg_capacity, p->seg_heavy_capacity,
+                                    tile_seg, seg_desc, seg_total, tile_order, stream_));
       float* pix = at<float>(out, p->seg_pix);
       res->segments.tile_seg = tile_seg;
       res->segments.seg_desc = seg_desc;
@@ -254,8 +261,10 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
       res->segments.capacity = p->seg_capacity;
       res->segments.heavy_capacity = p->seg_heavy_capacity;
       res->segments.seg_TC = pix;
-      res->segments.seg_P = pix + 4 * p->seg_capacity * 256;
-      res->segments.seg_median = f->want_median ? pix + 5 * p->seg_capacity * 256 : nullptr;
+      const int64_t tc_planes = p->seg_col >= 0 ? 1 : 4;
+      res->segments.seg_P = pix + tc_planes * p->seg_capacity * 256;
+      res->segments.seg_median = f->want_median ? pix + (tc_planes + 1) * p->seg_capacity * 256 : nullptr;
+      res->segments.seg_col = at<float>(out, p->seg_col);
       res->segments.seg_last = at<int32_t>(out, p->seg_last);
       res->has_segments = 1;
       seg = &res->segments;
@@ -263,10 +272,10 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
     if (event_k6_begin && hipEventRecord(reinterpret_cast<hipEvent_t>(event_k6_begin), stream) != hipSuccess)
       return GSR_ERR_LAUNCH_FAILED;
     if (p->feat_rows >= 0)
-      GSR_TRY(gsr_composite_forward_wide(rows, at<float>(out, p->feat_rows), sorted_splat, sorted_inst, tile_range, f->W,
-                                         f->H, f->C, &f->params, image, at<float>(out, p->final_T),
-                                         at<int32_t>(out, p->last), at<float>(out, p->median),
-                                         at<float>(out, p->vis_partial), at<float>(out, p->pair_vis), stream_));
+      GSR_TRY(gsr_composite_forward_wide_seg(rows, at<float>(out, p->feat_rows), sorted_splat, sorted_inst, tile_range,
+                                             f->W, f->H, f->C, &f->params, image, at<float>(out, p->final_T),
+                                             at<int32_t>(out, p->last), at<float>(out, p->median),
+                                             at<float>(out, p->vis_partial), at<float>(out, p->pair_vis), seg, stream_));
     else
       GSR_TRY(gsr_composite_forward(rows, sorted_splat, sorted_inst, tile_range, f->W, f->H, f->C, &f->params, image,
                                     at<float>(out, p->final_T), at<int32_t>(out, p->last), at<float>(out, p->median),

@@ -509,7 +509,7 @@ def _wide_width(C_: int) -> int:
 
 def _composite_backward_wide(st: _RasterState, d_image: torch.Tensor, d_feat: torch.Tensor, dev) -> torch.Tensor:
   """K7 wide + its per-splat reduction (C >= 4): the packed (M,16) gradient rows with df0..df2 = 0; the feature gradient
-  is written straight into ``d_feat`` (M, C)."""
+  is written straight into ``d_feat`` (M, C).  The forward pass's segments (if any) give every segment its own wave."""
   lib = _lib.load()
   if st.vis_partial is None:
     raise _lib.GsplatHipError("backward called on a rendering made without gradient state")
@@ -519,10 +519,11 @@ def _composite_backward_wide(st: _RasterState, d_image: torch.Tensor, d_feat: to
   timer = KERNEL_TIMER
   if timer is not None:
     timer.begin("composite_backward")
-  _lib.check(lib.gsr_composite_backward_wide(_ptr(st.rows), _ptr(st.feat_rows), _ptr(st.sorted_splat),
-                                             _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.tile_range), st.W, st.H,
-                                             st.C, C.byref(st.params), _ptr(st.final_T), _ptr(st.last), _ptr(dimg),
-                                             _ptr(partial), stream), "gsr_composite_backward_wide")
+  _lib.check(lib.gsr_composite_backward_wide_seg(_ptr(st.rows), _ptr(st.feat_rows), _ptr(st.sorted_splat),
+                                                 _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.tile_range), st.W,
+                                                 st.H, st.C, C.byref(st.params), _ptr(st.final_T), _ptr(st.last),
+                                                 _ptr(dimg), _ptr(st.image), _ptr(partial), _seg_ref(st), stream),
+             "gsr_composite_backward_wide_seg")
   if timer is not None:
     timer.end("composite_backward")
   grows = torch.empty(st.M, ROW_FLOATS, dtype=torch.float32, device=dev)
@@ -824,8 +825,8 @@ def render_projected(indexes: torch.Tensor, gaussians2d: torch.Tensor, features:
                      render_median_depth: bool = False, _depth_order=None, **_unused) -> Rendering:
   """K4 tile binning -> K5 radix sort -> K6 composite; autograd backward = K7 (+ per-point heuristics).
 
-  ``features`` is (M, C) with 1 <= C <= 16 (C >= 4: the wide path -- a feature table next to the packed rows, every tile
-  composited by one wave; C <= 3 keeps the packed rows' three colour slots).  ``points.prune_cost`` / ``points.split_score`` of the
+  ``features`` is (M, C) with 1 <= C <= 16 (C >= 4: the wide path -- a feature table next to the packed rows, tile lists
+  segmented by the same rule as for C <= 3, which keeps the packed rows' three colour slots).  ``points.prune_cost`` / ``points.split_score`` of the
   returned Rendering are filled in place when ``loss.backward()`` runs (trainer.py:512-514 reads them
   afterwards); ``points.visibility`` is available right after the forward pass (reg_loss,
   mlp_scene.py:268-288, needs ``points.visible`` before backward)."""
