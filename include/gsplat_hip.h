@@ -768,6 +768,25 @@ int gsr_reg_backward(const GsrReg* args, const float* terms, const float* d_loss
                      float* d_specular, float* d_log_scaling, void* stream);
 int gsr_scene_post_step(float* rotation_xyzw, float* log_scaling, int64_t N, float eps, float lo, float hi, void* stream);
 
+/* ---- evaluation pass (trainer/evaluation.py Evaluation, util/colors.py fit_colors_batch) --------------------------
+ * gsr_color_fit: out [P, 3] = the iterative affine-quadratic colour fit of image [P, 3] to ref [P, 3] (float32,
+ * contiguous, out distinct from both).  Design row a = [r^2, rg, rb, g^2, gb, b^2, r, g, b, 1]; iteration k solves, per
+ * channel c, min_w sum_p m_c (a . w - ref_c)^2 over the pixels with image_c, iterate_c and ref_c all in [eps, 1 - eps]
+ * (compared in float32), from 45 fp64 sums (the normal equations), and the next iterate is clip(a . W, 0, 1) rounded to
+ * float32.  The solve scales to unit diagonal, takes the symmetric eigendecomposition and drops eigenvalues <= 1e-9 of
+ * the largest: a rank-deficient system (a grey image, a constant channel) gets its minimum-norm solution, no unmasked
+ * pixel gives w = 0.  num_iters in 0..64 (0 copies), eps in [0, 0.5).  num_iters + 1 passes and num_iters one-block
+ * solves, all on the device; fixed-order sums, no atomics: bit-reproducible.
+ * gsr_image_metrics: metrics_out[0..2] (device floats, e.g. a row of a table) = mean squared error, mean absolute error
+ * (no clamp) and mean SSIM with valid padding of image against source, both [H, W, 3] float32 contiguous and 16-byte
+ * aligned, H and W > 10. */
+size_t gsr_color_fit_workspace_bytes(int64_t P);
+int gsr_color_fit(const float* image, const float* ref, int64_t P, int32_t num_iters, float eps, float* out,
+                  void* workspace, size_t workspace_bytes, void* stream);
+size_t gsr_image_metrics_workspace_bytes(int32_t H, int32_t W);
+int gsr_image_metrics(const float* image, const float* source, int32_t H, int32_t W, float* metrics_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -20,6 +20,8 @@ from .visibility import (BatchOverlapSampler, BatchOverlapSamplerConfig, CameraB
                          foreground_points, foreground_visibility, frustum_counts, inverse_ndc_depth, point_visibility,
                          random_cloud, random_ndc, random_points, sample_batch, sample_batch_grouped,
                          sample_with_temperature, select_batch, sinkhorn)
+from .evaluation import (Evaluation, compute_psnr, evaluate_scene, fit_colors, fit_colors_batch, image_metrics,
+                         mse_to_psnr)
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -32,4 +34,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "inverse_ndc_depth", "random_points", "balanced_points", "random_cloud", "balanced_cloud",
            "foreground_visibility", "foreground_points", "PointClusters", "ViewClustering", "sample_with_temperature",
            "select_batch", "sample_batch", "sample_batch_grouped", "sinkhorn", "BatchOverlapSampler",
-           "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig"]
+           "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig", "Evaluation", "compute_psnr",
+           "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene"]

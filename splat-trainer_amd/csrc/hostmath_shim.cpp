@@ -9,6 +9,7 @@
 #include "gsr_neighbours.h"
 #include "gsr_visibility.h"
 #include "gsr_color.h"
+#include "gsr_eval.h"
 
 extern "C" {
 
@@ -151,6 +152,85 @@ void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float*
     }
   for (int e = 0; e < n_grid; ++e) d_grid[e] = (float)acc[e];
   delete[] acc;
+}
+
+// ---- colour fit of the evaluation pass (gsr_eval.h) -----------------------------------------------------------------
+// sums [3][45]: the moments of iterate x [P, 3] against ref over the pixels unclipped in x0, x and ref, in pixel order
+void hm_color_fit_moments(const float* x0, const float* x, const float* ref, int64_t P, float eps, double* sums) {
+  const float lo = eps, hi = (float)(1.0 - (double)eps);
+  for (int k = 0; k < 3 * GSR_EV_SUMS; ++k) sums[k] = 0.0;
+  for (int64_t p = 0; p < P; ++p) {
+    double a[GSR_EV_COLS];
+    gsr_ev_row(x[3 * p], x[3 * p + 1], x[3 * p + 2], a);
+    for (int c = 0; c < 3; ++c) {
+      const int64_t o = 3 * p + c;
+      if (gsr_ev_unclipped(x0[o], lo, hi) && gsr_ev_unclipped(x[o], lo, hi) && gsr_ev_unclipped(ref[o], lo, hi))
+        gsr_ev_accumulate(a, (double)ref[o], sums + GSR_EV_SUMS * c);
+    }
+  }
+}
+
+// w [10]: the weights of one channel from its 45 sums
+void hm_color_fit_solve(const double* sums, double* w) {
+  double work[GSR_EV_WORK];
+  gsr_ev_solve(sums, work, w);
+}
+
+// The whole fit in the device's order of operations (eval.hip): min(ceil(P / 256), 1024) blocks of 256 threads, a thread
+// takes the pixels block * 256 + thread + i * blocks * 256 in ascending order, 64 lanes are added in the shuffle tree
+// v[l] += v[l + off] (off = 32 .. 1), the 4 waves in order, then the blocks' slots in order.  out [P, 3].
+void hm_color_fit(const float* x0, const float* ref, int64_t P, int num_iters, float eps, float* out) {
+  const float lo = eps, hi = (float)(1.0 - (double)eps);
+  const int64_t want = (P + 255) / 256;
+  const int blocks = (int)(want < 1024 ? want : 1024);
+  float* cur = new float[3 * P];
+  float* nxt = new float[3 * P];
+  double* lanes = new double[64 * GSR_EV_SUMS];
+  double weights[3 * GSR_EV_COLS];
+  for (int k = 0; k <= num_iters; ++k) {
+    for (int64_t p = 0; p < P; ++p) {
+      const float* src = k ? cur : x0;
+      if (k) {
+        double a[GSR_EV_COLS];
+        gsr_ev_row(src[3 * p], src[3 * p + 1], src[3 * p + 2], a);
+        for (int c = 0; c < 3; ++c) nxt[3 * p + c] = gsr_ev_warp(a, weights + GSR_EV_COLS * c);
+      } else {
+        for (int c = 0; c < 3; ++c) nxt[3 * p + c] = src[3 * p + c];
+      }
+    }
+    float* t = cur; cur = nxt; nxt = t;
+    if (k == num_iters) break;
+    for (int c = 0; c < 3; ++c) {
+      double sums[GSR_EV_SUMS];
+      for (int s = 0; s < GSR_EV_SUMS; ++s) sums[s] = 0.0;
+      for (int b = 0; b < blocks; ++b) {
+        double part[4][GSR_EV_SUMS];
+        for (int wv = 0; wv < 4; ++wv) {
+          for (int i = 0; i < 64 * GSR_EV_SUMS; ++i) lanes[i] = 0.0;
+          for (int lane = 0; lane < 64; ++lane)
+            for (int64_t p = (int64_t)b * 256 + wv * 64 + lane; p < P; p += (int64_t)blocks * 256) {
+              const int64_t o = 3 * p + c;
+              if (!(gsr_ev_unclipped(x0[o], lo, hi) && gsr_ev_unclipped(cur[o], lo, hi) && gsr_ev_unclipped(ref[o], lo, hi)))
+                continue;
+              double a[GSR_EV_COLS];
+              gsr_ev_row(cur[3 * p], cur[3 * p + 1], cur[3 * p + 2], a);
+              gsr_ev_accumulate(a, (double)ref[o], lanes + GSR_EV_SUMS * lane);
+            }
+          for (int off = 32; off > 0; off >>= 1)
+            for (int lane = 0; lane < off; ++lane)
+              for (int s = 0; s < GSR_EV_SUMS; ++s) lanes[GSR_EV_SUMS * lane + s] += lanes[GSR_EV_SUMS * (lane + off) + s];
+          for (int s = 0; s < GSR_EV_SUMS; ++s) part[wv][s] = lanes[s];
+        }
+        for (int s = 0; s < GSR_EV_SUMS; ++s) sums[s] += ((part[0][s] + part[1][s]) + part[2][s]) + part[3][s];
+      }
+      double work[GSR_EV_WORK];
+      gsr_ev_solve(sums, work, weights + GSR_EV_COLS * c);
+    }
+  }
+  for (int64_t i = 0; i < 3 * P; ++i) out[i] = cur[i];
+  delete[] cur;
+  delete[] nxt;
+  delete[] lanes;
 }
 
 
