@@ -697,6 +697,29 @@ int gsr_view_features(const int64_t* point_idx, const float* point_vis, int64_t 
                       int64_t N, int64_t K, float* dense_scratch, float* slot_scratch, float* features_out,
                       int32_t* point_visible, void* stream);
 
+/* ---- 3-D smoothing filter (Mip-Splatting, Yu et al. CVPR 2024, section 5.1; no reference counterpart) ---------------
+ * gsr_sampling_rate: rate_out [N] float32 = max over the cameras that sample point i of focal[c] / d, 0 when none does.
+ *   points [N, 3], records [V, 16] and h_r, d as for gsr_frustum_counts; focal [V] float32, the camera's max(fx, fy) in
+ *   pixels; margin >= 0 a fraction of the image: camera c samples a point when h_0 >= (-margin w) d && h_0 < (w + margin w) d
+ *   && h_1 >= (-margin h) d && h_1 < (h + margin h) d && d > near && d < far.  One lane owns its points and walks the
+ *   cameras in ascending order, no atomics: a function of the inputs alone.  1 <= N <= GSR_NEIGHBOURS_MAX_N,
+ *   1 <= V <= GSR_VISIBILITY_MAX_CAMERAS.
+ * gsr_filter3d_forward: per row, c = strength / rate^2 (0 when rate is not > 0, strength >= 0) is added to the variance of
+ *   every axis and the opacity is scaled by prod_j sigma_j / sigma'_j: u_j = c exp(-2 ls_j), ls'_j = ls_j + log1p(u_j) / 2,
+ *   lc = -sum_j log1p(u_j) / 2, a' = log sigmoid(a) + lc - log(sigmoid(-a) + sigmoid(a) (-expm1(lc))).  A row with c == 0
+ *   is copied: its output bits are its input bits.  log_scaling / out_log_scaling [N, 3], alpha_logit / out_alpha_logit
+ *   and rate [N], float32 contiguous and 16-byte aligned (rows travel four at a time); outputs distinct from inputs.
+ * gsr_filter3d_backward recomputes the forward's terms (nothing is saved) and writes d_log_scaling [N, 3] and
+ *   d_alpha_logit [N] from the gradients of the two outputs (overwritten, not added); a row with c == 0 passes its
+ *   incoming gradients through bit for bit.  The rate receives no gradient.  Same layout and alignment. */
+int gsr_sampling_rate(const float* points, int64_t N, const float* records, const float* focal, int64_t V, float margin,
+                      float* rate_out, void* stream);
+int gsr_filter3d_forward(const float* log_scaling, const float* alpha_logit, const float* rate, int64_t N, float strength,
+                         float* out_log_scaling, float* out_alpha_logit, void* stream);
+int gsr_filter3d_backward(const float* log_scaling, const float* alpha_logit, const float* rate, int64_t N, float strength,
+                          const float* d_out_log_scaling, const float* d_out_alpha_logit, float* d_log_scaling,
+                          float* d_alpha_logit, void* stream);
+
 /* ---- neural colour model (scene/color_model.py ColorModel, scene/mlp/torch_mlp.py MLP / AffineMLP) ----------
  * Per row: x = LayerNorm_F([point_features, glo]) (no affine, eps 1e-5); diffuse = lum(base(x), 0); d = normalize(
  * position - cam_pos) (eps 1e-12); [a, b] = encode(rsh_S(d)); specular = lum(dir(x a + b), -2), lum(o, c)_k =

@@ -22,6 +22,7 @@ from .visibility import (BatchOverlapSampler, BatchOverlapSamplerConfig, CameraB
                          sample_with_temperature, select_batch, sinkhorn)
 from .evaluation import (Evaluation, compute_psnr, evaluate_scene, fit_colors, fit_colors_batch, image_metrics,
                          mse_to_psnr)
+from .filter3d import sampling_rate, smooth_gaussians
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -35,4 +36,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "foreground_visibility", "foreground_points", "PointClusters", "ViewClustering", "sample_with_temperature",
            "select_batch", "sample_batch", "sample_batch_grouped", "sinkhorn", "BatchOverlapSampler",
            "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig", "Evaluation", "compute_psnr",
-           "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene"]
+           "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene", "sampling_rate",
+           "smooth_gaussians"]

@@ -8,6 +8,7 @@
 #include "gsr_bilagrid.h"
 #include "gsr_neighbours.h"
 #include "gsr_visibility.h"
+#include "gsr_filter3d.h"
 #include "gsr_color.h"
 #include "gsr_eval.h"
 
@@ -431,6 +432,49 @@ int hm_view_features(const int64_t* labels, int64_t N, int64_t K, const int64_t*
   delete[] start;
   delete[] order;
   return 0;
+}
+
+}  // extern "C"
+
+// sampling rate and 3-D smoothing filter (gsr_filter3d.h) on the host's libm: the device's order of operations.
+extern "C" {
+
+// points [N, 3], records [V, 16], focal [V]; rate [N]
+void hm_sampling_rate(const float* p, int64_t N, const float* rec, const float* focal, int64_t V, float margin,
+                      float* rate) {
+  for (int64_t i = 0; i < N; ++i) {
+    float bf = 0.f, bd = 1.f;
+    for (int64_t c = 0; c < V; ++c)
+      gsr_f3d_pair(rec + GSR_VIS_RECORD_FLOATS * c, focal[c], margin, p[3 * i], p[3 * i + 1], p[3 * i + 2], &bf, &bd);
+    rate[i] = gsr_f3d_rate(bf, bd);
+  }
+}
+
+// ls / out_ls [N, 3], a / rate / out_a [N]
+void hm_filter3d_forward(const float* ls, const float* a, const float* rate, int64_t N, float strength, float* out_ls,
+                         float* out_a) {
+  for (int64_t i = 0; i < N; ++i) {
+    const float c = gsr_f3d_variance(rate[i], strength);
+    if (c != 0.f) {
+      gsr_f3d_forward_row(ls + 3 * i, a[i], c, out_ls + 3 * i, out_a + i);
+    } else {
+      for (int j = 0; j < 3; ++j) out_ls[3 * i + j] = ls[3 * i + j];
+      out_a[i] = a[i];
+    }
+  }
+}
+
+void hm_filter3d_backward(const float* ls, const float* a, const float* rate, int64_t N, float strength, const float* g_ls,
+                          const float* g_a, float* d_ls, float* d_a) {
+  for (int64_t i = 0; i < N; ++i) {
+    const float c = gsr_f3d_variance(rate[i], strength);
+    if (c != 0.f) {
+      gsr_f3d_backward_row(ls + 3 * i, a[i], c, g_ls + 3 * i, g_a[i], d_ls + 3 * i, d_a + i);
+    } else {
+      for (int j = 0; j < 3; ++j) d_ls[3 * i + j] = g_ls[3 * i + j];
+      d_a[i] = g_a[i];
+    }
+  }
 }
 
 }  // extern "C"

@@ -8,6 +8,11 @@ logger; a scene is told the number of images instead of being handed a camera ta
 the learning rates are plain floats -- the caller evaluates its schedules and passes the values to
 ``update_learning_rate``; ``to_sh_gaussians`` takes the cameras to fit against.  There is no autocast in ``render``: the
 native colour model is fp32 outside and f16 MFMA inside.
+
+Beyond the reference: ``MLPSceneConfig.filter_3d`` > 0 switches on Mip-Splatting's 3-D smoothing filter (filter3d.py).
+``update_filter(cameras)`` stores every point's sampling rate as the unoptimised column ``filter_rate`` of ``points``
+(as ``visible`` rides along), and ``render``, ``query_visibility`` and ``to_sh_gaussians`` then work on the smoothed
+scales and opacities; ``gaussians`` and ``reg_loss`` stay on the raw parameters.  At 0, the default, none of it runs.
 """
 from __future__ import annotations
 
@@ -19,6 +24,7 @@ import torch.nn as nn
 
 from . import reg
 from .color_model import ColorModel, ColorModelConfig, Colors
+from .filter3d import sampling_rate, smooth_gaussians
 from .data_types import CameraParams, Gaussians3D, RasterConfig, Rendering, pop_raster_config
 from .harness import split_gaussians_uniform
 from .optim import ParameterClass, VisibilityAwareLaProp, VisibilityOptimizer, point_basis_rows
@@ -63,7 +69,8 @@ def _clone_tree(obj):
 @dataclass(frozen=True)
 class MLPSceneConfig:
   """mlp_scene.py:34-93; defaults :40-52.  ``parameters``: {name: dict(lr=, type=)} for position, log_scaling, rotation,
-  alpha_logit and feature (config/scene/mlp.yaml:6-14); ``reg_weight``: {scale, opacity, aspect, specular} (:16-20)."""
+  alpha_logit and feature (config/scene/mlp.yaml:6-14); ``reg_weight``: {scale, opacity, aspect, specular} (:16-20).
+  ``filter_3d``: strength of the 3-D smoothing filter (Mip-Splatting uses 0.2); 0 = off."""
   parameters: Dict[str, dict]
   reg_weight: Dict[str, float]
   color_model: ColorModelConfig = field(default_factory=ColorModelConfig)
@@ -76,6 +83,7 @@ class MLPSceneConfig:
   vis_smooth: float = 0.001
   per_image: bool = True
   grad_clip: Optional[float] = 2.0
+  filter_3d: float = 0.0
 
   def optim_options(self) -> dict:
     """mlp_scene.py:58-60."""
@@ -238,13 +246,33 @@ class MLPScene:
     return Gaussians3D(position=p.position, rotation=p.rotation, log_scaling=p.log_scaling, alpha_logit=p.alpha_logit,
                        feature=p.feature)
 
+  @torch.no_grad()
+  def update_filter(self, cameras, margin: float = 0.15):
+    """Recomputes every point's sampling rate over ``cameras`` (anything ``CameraBatch.of`` accepts; the training views)
+    and stores it as the column ``filter_rate`` of ``points``.  Call it when the cameras or the points have changed,
+    e.g. after a densify round: until then ``split_and_prune`` keeps the rate of the rows it keeps and gives children
+    their parent's.  Points that no camera samples get the smallest rate among the others (the strongest filter)."""
+    if not self.config.filter_3d > 0:
+      raise ValueError("update_filter needs MLPSceneConfig.filter_3d > 0 (the filter's strength; 0 = off)")
+    self.points.tensors["filter_rate"] = sampling_rate(cameras, self.points.position.detach(), margin=margin)
+
+  def _filtered_gaussians(self) -> Gaussians3D:
+    """What ``render`` projects: ``gaussians``, through the 3-D smoothing filter when ``config.filter_3d`` > 0."""
+    if not self.config.filter_3d > 0:
+      return self.gaussians
+    if "filter_rate" not in self.points.tensors:
+      raise RuntimeError("MLPSceneConfig.filter_3d > 0 but the scene has no sampling rates yet: call "
+                         "update_filter(cameras) with the training cameras first")
+    return smooth_gaussians(self.gaussians, self.points.tensors["filter_rate"], self.config.filter_3d)
+
   def render(self, camera_params: CameraParams, image_idx: Optional[int] = None, specular_weight: float = 1.0,
              **options) -> Rendering:
     """mlp_scene.py:410-427: project, colour the culled points, rasterise ``colors.total(specular_weight)``; the
-    rendering's ``points.attributes`` are the ``Colors`` and its image has gone through ``post_activation``."""
+    rendering's ``points.attributes`` are the ``Colors`` and its image has gone through ``post_activation``.  With
+    ``config.filter_3d`` > 0 the smoothed Gaussians are projected (one autograd node in front of the projection)."""
     config = pop_raster_config(options)
     prefetch = {}
-    gaussians2d, depth, indexes = project_to_image(self.gaussians, camera_params, config, prefetch=prefetch)
+    gaussians2d, depth, indexes = project_to_image(self._filtered_gaussians(), camera_params, config, prefetch=prefetch)
     colors = self.eval_colors(indexes, camera_params, image_idx)
     rendering = render_projected(indexes, gaussians2d, colors.total(specular_weight), depth, camera_params, config,
                                  _depth_order=prefetch.get("depth_order"), **options)
@@ -255,7 +283,7 @@ class MLPScene:
   def query_visibility(self, camera_params: CameraParams) -> Tuple[torch.Tensor, torch.Tensor]:
     """mlp_scene.py:372-381: indexes and visibility of the points that reach a pixel (one zero feature channel)."""
     config = RasterConfig(compute_visibility=True)
-    gaussians2d, depth, indexes = project_to_image(self.gaussians, camera_params, config)
+    gaussians2d, depth, indexes = project_to_image(self._filtered_gaussians(), camera_params, config)
     feature = torch.zeros((indexes.shape[0], 1), device=self.device)
     rendering = render_projected(indexes, gaussians2d, feature, depth, camera_params, config)
     visible = rendering.points.visible
@@ -277,11 +305,14 @@ class MLPScene:
 
   def to_sh_gaussians(self, cameras: Sequence[CameraParams], image_indexes: Sequence[Optional[int]], epochs: int = 1,
                       sh_degree: int = 2, generator: Optional[torch.Generator] = None) -> Gaussians3D:
-    """mlp_scene.py:394-398: the scene's geometry with fitted SH colours, as ``ply_io.write_gaussians`` takes it."""
-    p = self.points
+    """mlp_scene.py:394-398: the scene's geometry with fitted SH colours, as ``ply_io.write_gaussians`` takes it.  With
+    ``config.filter_3d`` > 0 the scales and opacities are the smoothed ones: the export bakes the filter in, so a
+    standard 3DGS viewer shows what was trained."""
     feature = self.evaluate_sh_features(cameras, image_indexes, epochs, sh_degree, generator)
-    return Gaussians3D(position=p.position.detach(), rotation=p.rotation.detach(), log_scaling=p.log_scaling.detach(),
-                       alpha_logit=p.alpha_logit.detach(), feature=feature)
+    with torch.no_grad():
+      g = self._filtered_gaussians()
+    return Gaussians3D(position=g.position.detach(), rotation=g.rotation.detach(), log_scaling=g.log_scaling.detach(),
+                       alpha_logit=g.alpha_logit.detach(), feature=feature)
 
 
 def resized_camera(camera: CameraParams, scale: float) -> CameraParams:

@@ -872,7 +872,10 @@ def render_gaussians(gaussians: Gaussians3D, camera_params: CameraParams, config
                      sh_collector=None, **options) -> Rendering:
   """One-call form (splat_trainer/scripts/test_split.py:30): project -> colour -> rasterize.
   ``use_sh``: ``gaussians.feature`` is (N, 3, K) SH coefficients evaluated towards the camera (one fused autograd node,
-  ``_FrameFn``); otherwise it is an (N, C) per-point colour and the three calls are chained."""
+  ``_FrameFn``); otherwise it is an (N, C) per-point colour and the three calls are chained.
+  ``grad_out`` (the fused accumulation of ``MiniTrainer``) is not combined with the 3-D smoothing filter: it writes the
+  gradients of the tensors it is handed straight into its buffers, so the output of ``smooth_gaussians`` would receive
+  them and the filter's backward would never run.  Render ``smooth_gaussians(...)`` with plain autograd instead."""
   config = config or RasterConfig()
   feature = gaussians.feature
   if use_sh and feature.is_cuda and feature.dim() == 3 and feature.shape[1] == 3 and feature.shape[2] in (1, 4, 9, 16):
