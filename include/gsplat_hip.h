@@ -720,6 +720,21 @@ int gsr_filter3d_backward(const float* log_scaling, const float* alpha_logit, co
                           const float* d_out_log_scaling, const float* d_out_alpha_logit, float* d_log_scaling,
                           float* d_alpha_logit, void* stream);
 
+/* ---- SH export fit: per-point least squares of SH coefficients to view-dependent colours (no reference counterpart) ----
+ * One row of gsr_sh_fit_row_doubles(K) = K (K + 1) / 2 + 3 K + 1 doubles per point (0 for a K outside {1, 4, 9, 16}): the
+ * lower triangle of G = sum w Y Y^T, b_c = sum w Y (y_c - 0.5) channel-major, W = sum w, with Y the basis of gsr_sh_forward
+ * at normalize(position - camera_pos) in float32 and every product and sum after it fp64 (csrc/gsr_sh_fit.h).
+ * gsr_sh_fit_accumulate adds one view: positions [N, 3], indexes [M] int64 DISTINCT indices in [0, N) (an index outside
+ *   the range is skipped; duplicates are not detected and lose updates), colors [M, 3] and weights [M] >= 0 float32,
+ *   camera_pos [3] float32 on the device, acc [N, row doubles] fp64.  Only the listed rows are read and written, without
+ *   atomics: calls on one stream add their views in order, bit-reproducibly.  1 <= M <= N <= GSR_NEIGHBOURS_MAX_N.
+ * gsr_sh_fit_solve: (G + ridge W Y0^2 diag(0, 1, ..., 1)) s_c = b_c per point by fp64 Cholesky, Y0 the constant basis
+ *   term; sh_out [N, 3, K] and weight_out [N] = W, float32.  A row with W == 0 gives zeros.  ridge >= 1e-6, finite. */
+int gsr_sh_fit_row_doubles(int32_t K);
+int gsr_sh_fit_accumulate(const float* positions, int64_t N, const int64_t* indexes, int64_t M, const float* colors,
+                          const float* weights, const float* camera_pos, int32_t K, double* acc, void* stream);
+int gsr_sh_fit_solve(const double* acc, int64_t N, int32_t K, float ridge, float* sh_out, float* weight_out, void* stream);
+
 /* ---- neural colour model (scene/color_model.py ColorModel, scene/mlp/torch_mlp.py MLP / AffineMLP) ----------
  * Per row: x = LayerNorm_F([point_features, glo]) (no affine, eps 1e-5); diffuse = lum(base(x), 0); d = normalize(
  * position - cam_pos) (eps 1e-12); [a, b] = encode(rsh_S(d)); specular = lum(dir(x a + b), -2), lum(o, c)_k =

@@ -23,6 +23,7 @@ from .visibility import (BatchOverlapSampler, BatchOverlapSamplerConfig, CameraB
 from .evaluation import (Evaluation, compute_psnr, evaluate_scene, fit_colors, fit_colors_batch, image_metrics,
                          mse_to_psnr)
 from .filter3d import sampling_rate, smooth_gaussians
+from .sh_fit import ShFit, fit_sh
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -37,4 +38,4 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "select_batch", "sample_batch", "sample_batch_grouped", "sinkhorn", "BatchOverlapSampler",
            "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig", "Evaluation", "compute_psnr",
            "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene", "sampling_rate",
-           "smooth_gaussians"]
+           "smooth_gaussians", "ShFit", "fit_sh"]

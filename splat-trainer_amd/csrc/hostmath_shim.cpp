@@ -9,6 +9,7 @@
 #include "gsr_neighbours.h"
 #include "gsr_visibility.h"
 #include "gsr_filter3d.h"
+#include "gsr_sh_fit.h"
 #include "gsr_color.h"
 #include "gsr_eval.h"
 
@@ -474,6 +475,60 @@ void hm_filter3d_backward(const float* ls, const float* a, const float* rate, in
       for (int j = 0; j < 3; ++j) d_ls[3 * i + j] = g_ls[3 * i + j];
       d_a[i] = g_a[i];
     }
+  }
+}
+
+}  // extern "C"
+
+// SH export fit (gsr_sh_fit.h): the device's updates and its solve, in its order, one point at a time.
+namespace {
+
+template <int K>
+void shf_accumulate(const float* pos, int64_t N, const int64_t* idx, int64_t M, const float* col, const float* wts,
+                    const float* cam, double* acc) {
+  constexpr GsrShfTable<K> tab{};
+  constexpr int R = GsrShfTable<K>::R;
+  for (int64_t m = 0; m < M; ++m) {
+    const int64_t i = idx[m];
+    if (i < 0 || i >= N) continue;
+    double e[GsrShfTable<K>::E];
+    gsr_shf_operands<K>(pos + 3 * i, cam, col + 3 * m, e);
+    double* row = acc + i * R;
+    for (int j = 0; j < R; ++j) row[j] = gsr_shf_update(row[j], wts[m], e[tab.a[j]], e[tab.b[j]]);
+  }
+}
+
+template <int K>
+void shf_solve(const double* acc, int64_t N, float ridge, float* sh, float* weight) {
+  constexpr int R = GsrShfTable<K>::R;
+  double work[R];
+  for (int64_t n = 0; n < N; ++n) gsr_shf_solve_row<K>(acc + n * R, ridge, work, sh + n * 3 * K, weight + n);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hm_sh_fit_row_doubles(int K) { return gsr_shf_row_doubles(K); }
+
+// pos [N, 3], idx / wts [M], col [M, 3], cam [3]; acc [N, R(K)] is added to
+void hm_sh_fit_accumulate(const float* pos, int64_t N, const int64_t* idx, int64_t M, const float* col, const float* wts,
+                          const float* cam, int K, double* acc) {
+  switch (K) {
+    case 1: shf_accumulate<1>(pos, N, idx, M, col, wts, cam, acc); break;
+    case 4: shf_accumulate<4>(pos, N, idx, M, col, wts, cam, acc); break;
+    case 9: shf_accumulate<9>(pos, N, idx, M, col, wts, cam, acc); break;
+    case 16: shf_accumulate<16>(pos, N, idx, M, col, wts, cam, acc); break;
+  }
+}
+
+// acc [N, R(K)]; sh [N, 3, K], weight [N]
+void hm_sh_fit_solve(const double* acc, int64_t N, int K, float ridge, float* sh, float* weight) {
+  switch (K) {
+    case 1: shf_solve<1>(acc, N, ridge, sh, weight); break;
+    case 4: shf_solve<4>(acc, N, ridge, sh, weight); break;
+    case 9: shf_solve<9>(acc, N, ridge, sh, weight); break;
+    case 16: shf_solve<16>(acc, N, ridge, sh, weight); break;
   }
 }
 

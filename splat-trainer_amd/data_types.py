@@ -8,6 +8,7 @@ plain dataclasses over torch tensors exposing the attributes/methods the referen
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field, fields, replace as _dc_replace
 from typing import Any, Optional, Tuple
 
@@ -133,6 +134,21 @@ class Gaussians3D:
 
   def detach(self) -> "Gaussians3D":
     return self.apply(torch.detach)
+
+  def translated(self, translation) -> "Gaussians3D":
+    """New instance with ``translation`` (3,) added to every position (dataset/normalization.py:28-31)."""
+    t = torch.as_tensor(translation, dtype=self.position.dtype, device=self.position.device)
+    return Gaussians3D(position=self.position + t, rotation=self.rotation, log_scaling=self.log_scaling,
+                       alpha_logit=self.alpha_logit, feature=self.feature)
+
+  def scaled(self, scale: float) -> "Gaussians3D":
+    """New instance ``scale`` (> 0) times the size about the origin: positions times ``scale``, ``log scale`` added to
+    ``log_scaling`` (dataset/normalization.py:28-31)."""
+    scale = float(scale)
+    if not scale > 0.0:
+      raise ValueError(f"scale must be > 0, got {scale}")
+    return Gaussians3D(position=self.position * scale, rotation=self.rotation,
+                       log_scaling=self.log_scaling + math.log(scale), alpha_logit=self.alpha_logit, feature=self.feature)
 
   def to_dict(self) -> dict:
     return {name: getattr(self, name) for name in self.FIELDS}

@@ -30,6 +30,7 @@ from .harness import split_gaussians_uniform
 from .optim import ParameterClass, VisibilityAwareLaProp, VisibilityOptimizer, point_basis_rows
 from .renderer import project_to_image, render_projected
 from .sh import evaluate_sh_at
+from .sh_fit import DEFAULT_RIDGE, fit_sh
 
 SH_C0 = 0.282094791773878
 
@@ -290,25 +291,37 @@ class MLPScene:
     return visible.idx, visible.visibility
 
   def evaluate_sh_features(self, cameras: Sequence[CameraParams], image_indexes: Sequence[Optional[int]], epochs: int = 1,
-                           sh_degree: int = 2, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                           sh_degree: int = 2, generator: Optional[torch.Generator] = None, method: str = "adam",
+                           ridge: float = DEFAULT_RIDGE) -> torch.Tensor:
     """mlp_scene.py:384-391 + scene/transfer_sh.py:54-113: per-point SH coefficients (N, 3, (sh_degree + 1)^2) fitted to
     the scene's view-dependent colours.  Cameras at half resolution in a random order per epoch; Adam, base band lr 0.1,
     higher bands lr 0.01 with weight decay 1e-4; visibility-weighted MSE + 0.1 L1 of the base colour.  ``generator``: a
-    CPU generator for the initial coefficients and the camera order."""
+    CPU generator for the initial coefficients and the camera order.
+
+    ``method="lstsq"`` solves the weighted fit over the same half-resolution cameras directly instead (sh_fit.fit_sh:
+    one pass in the given order, ``ridge`` on the higher bands; no ``epochs``, no ``generator``; a point no camera sees
+    gets zero coefficients, not random ones)."""
+    if method not in ("adam", "lstsq"):
+      raise ValueError(f"method must be 'adam' or 'lstsq', got {method!r}")
+
     def eval_colors(idx, cam, image_idx):
       with torch.no_grad():
         return self.color_model.post_activation(self.eval_colors(idx, cam, image_idx).total())
 
     half = [resized_camera(c, 0.5) for c in cameras]
+    if method == "lstsq":
+      return fit_sh(eval_colors, self.query_visibility, half, list(image_indexes), self.points.position.detach(),
+                    sh_degree=sh_degree, ridge=ridge)[0]
     return transfer_sh(eval_colors, self.query_visibility, half, list(image_indexes), self.points.position.detach(),
                        epochs=epochs, sh_degree=sh_degree, generator=generator)
 
   def to_sh_gaussians(self, cameras: Sequence[CameraParams], image_indexes: Sequence[Optional[int]], epochs: int = 1,
-                      sh_degree: int = 2, generator: Optional[torch.Generator] = None) -> Gaussians3D:
+                      sh_degree: int = 2, generator: Optional[torch.Generator] = None, method: str = "adam",
+                      ridge: float = DEFAULT_RIDGE) -> Gaussians3D:
     """mlp_scene.py:394-398: the scene's geometry with fitted SH colours, as ``ply_io.write_gaussians`` takes it.  With
     ``config.filter_3d`` > 0 the scales and opacities are the smoothed ones: the export bakes the filter in, so a
-    standard 3DGS viewer shows what was trained."""
-    feature = self.evaluate_sh_features(cameras, image_indexes, epochs, sh_degree, generator)
+    standard 3DGS viewer shows what was trained.  ``method`` and ``ridge`` as for ``evaluate_sh_features``."""
+    feature = self.evaluate_sh_features(cameras, image_indexes, epochs, sh_degree, generator, method=method, ridge=ridge)
     with torch.no_grad():
       g = self._filtered_gaussians()
     return Gaussians3D(position=g.position.detach(), rotation=g.rotation.detach(), log_scaling=g.log_scaling.detach(),
