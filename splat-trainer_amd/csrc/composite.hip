@@ -41,6 +41,16 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // four consecutive list words at an address that is only 4-byte aligned (a wave-uniform address: one s_load_dwordx4)
 struct __attribute__((packed, aligned(4))) Rank4 { uint32_t x, y, z, w; };
 #define GSR_V2(x) ((v2f){(x), (x)})
+typedef float v3f __attribute__((ext_vector_type(3)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+// the C channel values of one pixel as one register tuple
+template <int C> struct ChanVec;
+template <> struct ChanVec<1> { typedef float type; };
+template <> struct ChanVec<2> { typedef v2f type; };
+template <> struct ChanVec<3> { typedef v3f type; };
+__device__ __forceinline__ float chan(float v, int) { return v; }
+__device__ __forceinline__ float chan(v2f v, int c) { return v[c]; }
+__device__ __forceinline__ float chan(v3f v, int c) { return v[c]; }
 
 // The VALU is the binding unit of both kernels (a wave64 fp32 op holds its SIMD for 4 cycles; only the packed
 // v_pk_{mul,add,fma}_f32 forms reach the 64 FLOP/clk/SIMD peak), so each lane evaluates its two pixels of one
@@ -120,6 +130,13 @@ __device__ __forceinline__ Splat load_splat(const float* __restrict__ rec, const
 // Device view of the segment tables (all NULL / 0 when the caller does not segment).
 #define GSR_SEG_HEAVY 0x80000000u   // tile_seg count word: the tile's FORWARD pass is segmented too (passes A, C, D)
 
+// A word of a table that an earlier launch wrote and no kernel reading it here modifies (segment plan, launch order),
+// read through the constant address space: at a wave-uniform address that is a scalar-cache load, which neither waits
+// for nor is counted with the wave's vector loads and stores.
+__device__ __forceinline__ uint32_t load_table_word(const uint32_t* p) {
+  return *(const __attribute__((address_space(4))) uint32_t*)p;
+}
+
 struct SegDev {
   const uint32_t* tile_seg;    // [num_tiles, 2]: first segment, number of segments (0: short tile) | GSR_SEG_HEAVY
   const uint32_t* seg_desc;    // [capacity, 4]: tile, list start, list end, index within the tile
@@ -173,8 +190,8 @@ __device__ __forceinline__ int ordered_tile(const SegDev& seg, int num_tiles, ui
   if (longer == 0ull) return -1;
   const int l = __builtin_ctzll(longer);
   const uint32_t before = l ? (uint32_t)__builtin_amdgcn_readlane((int)upto, l - 1) : 0u;
-  return (int)seg.tile_order[((size_t)band * GSR_TILE_CLASSES + (size_t)(GSR_TILE_CLASSES - 1 - l)) *
-                                 (size_t)gsr_tile_band_stride(num_tiles) + (t - before)];
+  return (int)load_table_word(seg.tile_order + ((size_t)band * GSR_TILE_CLASSES + (size_t)(GSR_TILE_CLASSES - 1 - l)) *
+                                                   (size_t)gsr_tile_band_stride(num_tiles) + (t - before));
 }
 
 // per-lane pixel state of the forward walk: pixel p = 2h + i, half h (rows py0 + 8h), side i (cols px0 + 8i)
@@ -223,10 +240,14 @@ __device__ __forceinline__ void fwd_walk(FwdPix<C>& px, const float* __restrict_
                                          const uint32_t* __restrict__ sorted_inst, uint32_t tile_start, uint32_t begin,
                                          uint32_t end, float fx0, float fy0, const GsrRasterParams& rp, int lane,
                                          float* __restrict__ vis_partial, float* __restrict__ pair_vis,
-                                         uint32_t pf_end) {
+                                         uint32_t pf_end, float* vis_park) {
   // lane 16r+15 ends up with the visibility total of pair (i + {0,2,1,3}[r]) of each group of four
   const uint32_t vis_slot = (uint32_t)(((lane >> 4) & 1) * 2 + (lane >> 5));
   if (begin >= end) return;
+  // Visibility handover: the totals are parked in the wave's 64 LDS cells, by list position counted from `begin`, and
+  // handed over once per 64 positions (and wherever the walk ends) with one coalesced store; the block's instance ids
+  // come by one coalesced load issued when the block starts, so the four-pair loop holds no memory wait at all.
+  float* const park = vis_park + vis_slot;
   // PF instantiation (frames whose row table has outgrown the caches): the packed splat ids of the NEXT iteration's four
   // pairs arrive by one scalar load issued at the top of this iteration, so the row fetch of a pair no longer waits for
   // an index load issued just in front of it (one exposed scalar-load latency per pair; K6 653 -> 602 us at 3M splats;
@@ -242,79 +263,96 @@ __device__ __forceinline__ void fwd_walk(FwdPix<C>& px, const float* __restrict_
   } else {
     nxt = load_splat<C, MEDIAN>(rec, sorted_rank, begin);
   }
-  for (uint32_t i = begin; i < end; i += 4) {
-    if (PF && ((i - tile_start) & (GSR_K6_PREFETCH - 1)) == 0u) fwd_prefetch_step<C>(px, rec, sorted_rank, i, pf_end, lane);
-    if constexpr (PF) {
-      if (i + 4 < end) {
-        const Rank4 q4 = *reinterpret_cast<const Rank4*>(sorted_rank + i + 4);
-        rk_next[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.x); rk_next[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.y);
-        rk_next[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.z); rk_next[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.w);
-      }
-    }
-    float wq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      if (i + m < end) {                                               // wave-uniform
-        const Splat s = nxt;
-        if constexpr (PF) {
-          if (i + m + 1 < end) nxt = load_splat_packed<C, MEDIAN>(rec, m < 3 ? rk[m + 1] : rk_next[0]);
-        } else {
-          // prefetch of the next pair's row (scalar loads), UNCONDITIONAL -- the last pair of the list re-reads its own
-          // row -- so that `nxt` is always a fresh value and the compiler alternates register sets instead of copying
-          // the row from "next" to "current" once per pair (-16 scalar instructions per pair; K6 -2 % at 500k splats;
-          // at 3M the re-reads cost more than the copies: +2 %, so the large-frame instantiation keeps the condition)
-          nxt = load_splat<C, MEDIAN>(rec, sorted_rank, min(i + m + 1, end - 1u));
+  for (uint32_t blk = begin; blk < end; blk += 64) {
+    const uint32_t blk_end = min(blk + 64u, end);
+    uint32_t blk_inst = 0u;
+    if (VIS) blk_inst = sorted_inst[min(blk + (uint32_t)lane, blk_end - 1u)];   // (clamped: always a valid address)
+    bool dead = false;
+    uint32_t i = blk;
+    for (; i < blk_end; i += 4) {
+      if (PF && ((i - tile_start) & (GSR_K6_PREFETCH - 1)) == 0u) fwd_prefetch_step<C>(px, rec, sorted_rank, i, pf_end, lane);
+      if constexpr (PF) {
+        if (i + 4 < end) {
+          const Rank4 q4 = *reinterpret_cast<const Rank4*>(sorted_rank + i + 4);
+          rk_next[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.x); rk_next[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.y);
+          rk_next[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.z); rk_next[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)q4.w);
         }
-        // offsets from the mean: ONE rounding per pixel (centre - mean, the centre exact), whichever half / side it is in
-        const v2f dx2 = (v2f){fx0, fx0 + 8.f} - GSR_V2(s.u);
-        const int idx = (int)(i - tile_start) + m + 1;
-        v2f wsum2 = GSR_V2(0.f);
+      }
+      float wq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          if (!(s.halves & (1u << h))) continue;                        // scalar test: support misses this half
-          const float dy = (h ? fy0 + 8.f : fy0) - s.v;
-          const v2f q = eval_q2(dx2, dy, s.A, s.B, s.C);
-          // q <= qlim = min(q_max, 2 ln(opacity / alpha_threshold)) says both "inside the support" and "alpha reaches
-          // the threshold" (alpha = opacity exp(-q/2); the clamp at 0.99 lies above the threshold)
-          const bool hit0 = px.T2[h].x >= rp.T_eps && q.x <= s.qlim;
-          const bool hit1 = px.T2[h].y >= rp.T_eps && q.y <= s.qlim;
-          if (__ballot(hit0 || hit1) != 0ull) {
-            const v2f G = eval_G2(q);
-            const v2f a_raw = G * s.op;
-            v2f alpha = clamp_alpha2(a_raw, rp.clamp_max_alpha);
-            alpha = (v2f){hit0 ? alpha.x : 0.f, hit1 ? alpha.y : 0.f};
-            const v2f w = alpha * px.T2[h];
-            px.col2[h][0] = __builtin_elementwise_fma(w, GSR_V2(s.f0), px.col2[h][0]);
-            if (C > 1) px.col2[h][1] = __builtin_elementwise_fma(w, GSR_V2(s.f1), px.col2[h][1]);
-            if (C > 2) px.col2[h][2] = __builtin_elementwise_fma(w, GSR_V2(s.f2), px.col2[h][2]);
-            wsum2 += w;
-            px.T2[h] = px.T2[h] - w;                           // T (1 - alpha), with w = alpha T already formed
-            if (hit0) px.lastc[2 * h] = idx;
-            if (hit1) px.lastc[2 * h + 1] = idx;
-            if (MEDIAN) {
-              if (hit0 && px.med2[h].x == 0.f && px.T2[h].x < 0.5f) px.med2[h].x = s.depth;
-              if (hit1 && px.med2[h].y == 0.f && px.T2[h].y < 0.5f) px.med2[h].y = s.depth;
+      for (int m = 0; m < 4; ++m) {
+        if (i + m < end) {                                               // wave-uniform
+          const Splat s = nxt;
+          if constexpr (PF) {
+            if (i + m + 1 < end) nxt = load_splat_packed<C, MEDIAN>(rec, m < 3 ? rk[m + 1] : rk_next[0]);
+          } else {
+            // prefetch of the next pair's row (scalar loads), UNCONDITIONAL -- the last pair of the list re-reads its own
+            // row -- so that `nxt` is always a fresh value and the compiler alternates register sets instead of copying
+            // the row from "next" to "current" once per pair (-16 scalar instructions per pair; K6 -2 % at 500k splats;
+            // at 3M the re-reads cost more than the copies: +2 %, so the large-frame instantiation keeps the condition)
+            nxt = load_splat<C, MEDIAN>(rec, sorted_rank, min(i + m + 1, end - 1u));
+          }
+          // offsets from the mean: ONE rounding per pixel (centre - mean, the centre exact), whichever half / side it is in
+          const v2f dx2 = (v2f){fx0, fx0 + 8.f} - GSR_V2(s.u);
+          const int idx = (int)(i - tile_start) + m + 1;
+          v2f wsum2 = GSR_V2(0.f);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (!(s.halves & (1u << h))) continue;                        // scalar test: support misses this half
+            const float dy = (h ? fy0 + 8.f : fy0) - s.v;
+            const v2f q = eval_q2(dx2, dy, s.A, s.B, s.C);
+            // q <= qlim = min(q_max, 2 ln(opacity / alpha_threshold)) says both "inside the support" and "alpha reaches
+            // the threshold" (alpha = opacity exp(-q/2); the clamp at 0.99 lies above the threshold)
+            const bool hit0 = px.T2[h].x >= rp.T_eps && q.x <= s.qlim;
+            const bool hit1 = px.T2[h].y >= rp.T_eps && q.y <= s.qlim;
+            if (__ballot(hit0 || hit1) != 0ull) {
+              const v2f G = eval_G2(q);
+              const v2f a_raw = G * s.op;
+              v2f alpha = clamp_alpha2(a_raw, rp.clamp_max_alpha);
+              alpha = (v2f){hit0 ? alpha.x : 0.f, hit1 ? alpha.y : 0.f};
+              const v2f w = alpha * px.T2[h];
+              px.col2[h][0] = __builtin_elementwise_fma(w, GSR_V2(s.f0), px.col2[h][0]);
+              if (C > 1) px.col2[h][1] = __builtin_elementwise_fma(w, GSR_V2(s.f1), px.col2[h][1]);
+              if (C > 2) px.col2[h][2] = __builtin_elementwise_fma(w, GSR_V2(s.f2), px.col2[h][2]);
+              wsum2 += w;
+              px.T2[h] = px.T2[h] - w;                           // T (1 - alpha), with w = alpha T already formed
+              if (hit0) px.lastc[2 * h] = idx;
+              if (hit1) px.lastc[2 * h + 1] = idx;
+              if (MEDIAN) {
+                if (hit0 && px.med2[h].x == 0.f && px.T2[h].x < 0.5f) px.med2[h].x = s.depth;
+                if (hit1 && px.med2[h].y == 0.f && px.T2[h].y < 0.5f) px.med2[h].y = s.depth;
+              }
             }
           }
+          wq[m] = wsum2.x + wsum2.y;
         }
-        wq[m] = wsum2.x + wsum2.y;
       }
+      if (VIS) {
+        // four pairs reduced at once, transposing: swap32 (4 -> 2 registers), swap16 (2 -> 1), then 4 row steps
+        float r = gsr_swap16_add(gsr_swap32_add(wq[0], wq[1]), gsr_swap32_add(wq[2], wq[3]));
+        r = gsr_row_sum_to_lane15(r);
+        if ((lane & 15) == 15) park[i - blk] = r;      // (cells past `end` are parked too and never handed over)
+      }
+      const bool live = px.T2[0].x >= rp.T_eps || px.T2[0].y >= rp.T_eps || px.T2[1].x >= rp.T_eps ||
+                        px.T2[1].y >= rp.T_eps;
+      if (__ballot(live) == 0ull) { dead = true; i += 4; break; }
+      if constexpr (PF) { rk[0] = rk_next[0]; rk[1] = rk_next[1]; rk[2] = rk_next[2]; rk[3] = rk_next[3]; }
     }
     if (VIS) {
-      // four pairs reduced at once, transposing: swap32 (4 -> 2 registers), swap16 (2 -> 1), then 4 row steps
-      float r = gsr_swap16_add(gsr_swap32_add(wq[0], wq[1]), gsr_swap32_add(wq[2], wq[3]));
-      r = gsr_row_sum_to_lane15(r);
-      const uint32_t pos = i + vis_slot;
-      if ((lane & 15) == 15 && pos < end) {
-        // sorted-position copy (read back coalesced by the backward pass) + per-instance copy (per-splat sums)
-        pair_vis[pos] = r;
-        if (r > 0.f) vis_partial[sorted_inst[pos]] = r;
+      // hand over the positions the walk reached, [blk, min(i, blk_end)): sorted-position copy (read back coalesced by
+      // the backward pass) + per-instance copy (per-splat sums); positions it never reached stay unwritten
+      gsr_wave_lds_fence();
+      const float r = vis_park[lane];
+      gsr_wave_lds_fence();                            // read before the next block parks into the same cells
+      // the ids, requested a block ago, are taken here, in front of the stores below: left to the scatter's branch, a wave
+      // that skips it would carry the pending load -- and with it a wait for these very stores -- to the register's next use
+      asm volatile("" : "+v"(blk_inst));
+      if (blk + (uint32_t)lane < min(i, blk_end)) {
+        if (r > 0.f) vis_partial[blk_inst] = r;
+        pair_vis[blk + (uint32_t)lane] = r;
       }
     }
-    const bool live = px.T2[0].x >= rp.T_eps || px.T2[0].y >= rp.T_eps || px.T2[1].x >= rp.T_eps ||
-                      px.T2[1].y >= rp.T_eps;
-    if (__ballot(live) == 0ull) break;
-    if constexpr (PF) { rk[0] = rk_next[0]; rk[1] = rk_next[1]; rk[2] = rk_next[2]; rk[3] = rk_next[3]; }
+    if (dead) break;
   }
 }
 
@@ -402,22 +440,29 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(const float* __restri
   const float fx0 = (float)px0 + 0.5f, fy0 = (float)py0 + 0.5f;
   const uint32_t start = tile_range[2 * tile], end = tile_range[2 * tile + 1];
 
+  __shared__ float vis_park[64];                  // fwd_walk's visibility handover (the wave owns the block's LDS)
   FwdPix<C> px;
   fwd_init<C>(px, px0, py0, W, H);
   fwd_prefetch_init<C, PF>(px, sorted_rank, start, start, end, lane);
   if (tseg == 0u) {
     fwd_walk<C, VIS, MEDIAN, PF>(px, rec, sorted_rank, sorted_inst, start, start, end, fx0, fy0, rp, lane, vis_partial,
-                             pair_vis, end);
+                             pair_vis, end, vis_park);
   } else {
     // A long (but not heavy) tile is still walked by this one wave, but the walk pauses at the segment ends and leaves
     // a checkpoint -- (T, colour composited so far) per pixel, one 16-byte store each -- so that the backward pass can
     // give every segment a wave of its own (finer work units: its tail and its latency-bound last waves shrink).
     // (Kept as a second copy of the walk: the one-segment form of this loop costs the short-tile path 10-20 %.)
-    const uint32_t first = seg.tile_seg[2 * tile];
-    for (uint32_t j = 0; j < tseg; ++j) {
-      const uint32_t* d = seg.seg_desc + 4 * (size_t)(first + j);
-      fwd_walk<C, VIS, MEDIAN, PF>(px, rec, sorted_rank, sorted_inst, start, d[1], d[2], fx0, fy0, rp, lane, vis_partial,
-                               pair_vis, end);
+    // The next segment's bounds are fetched (scalar loads) before the current one is walked, so the wave never waits
+    // for a descriptor behind its own checkpoint stores.
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg.tile_seg[2 * tile]);
+    const uint32_t* d = seg.seg_desc + 4 * (size_t)first;
+    uint32_t seg_begin = load_table_word(d + 1), seg_end = load_table_word(d + 2);
+    for (uint32_t j = 0; j < tseg; ++j, d += 4) {
+      uint32_t next_begin = seg_begin, next_end = seg_end;
+      if (j + 1 < tseg) { next_begin = load_table_word(d + 5); next_end = load_table_word(d + 6); }
+      fwd_walk<C, VIS, MEDIAN, PF>(px, rec, sorted_rank, sorted_inst, start, seg_begin, seg_end, fx0, fy0, rp, lane,
+                                   vis_partial, pair_vis, end, vis_park);
+      seg_begin = next_begin; seg_end = next_end;
       float4* out = seg.seg_TC + 256 * (size_t)(first + j) + lane;
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
@@ -469,6 +514,7 @@ __global__ __launch_bounds__(64) void seg_composite_kernel(const float* __restri
   const int px0 = tx * 16 + (lane & 7), py0 = ty * 16 + (lane >> 3);
   const float fx0 = (float)px0 + 0.5f, fy0 = (float)py0 + 0.5f;
 
+  __shared__ float vis_park[64];
   FwdPix<C> px;
   fwd_init<C>(px, px0, py0, W, H);
   fwd_prefetch_init<C, PF>(px, sorted_rank, tile_range[2 * tile], begin, end, lane);
@@ -480,7 +526,7 @@ __global__ __launch_bounds__(64) void seg_composite_kernel(const float* __restri
   const bool alive[4] = {px.T2[0].x >= rp.T_eps, px.T2[0].y >= rp.T_eps, px.T2[1].x >= rp.T_eps, px.T2[1].y >= rp.T_eps};
   if (__ballot(alive[0] || alive[1] || alive[2] || alive[3]) != 0ull)
     fwd_walk<C, VIS, MEDIAN, PF>(px, rec, sorted_rank, sorted_inst, tile_range[2 * tile], begin, end, fx0, fy0, rp, lane,
-                             vis_partial, pair_vis, end);
+                             vis_partial, pair_vis, end, vis_park);
   const size_t o = 256 * (size_t)sidx + lane;
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
@@ -571,12 +617,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
   const bool is_seg = blockIdx.x < seg_blocks;
   if (is_seg) {
     sidx = gsr_xcd_group_remap(blockIdx.x, GSR_K7_SEG_GROUP_LOG2);     // a tile's segments share an XCD (and its L2)
-    if (sidx >= min(seg.seg_total[0], seg_capacity)) return;     // (the grid is rounded up past the tables' capacity)
+    if (sidx >= min(load_table_word(seg.seg_total), seg_capacity)) return;     // (the grid is rounded up past the tables' capacity)
     const uint32_t* d = seg.seg_desc + 4 * (size_t)sidx;
-    tile = (int)d[0];
+    tile = (int)load_table_word(d);
     const uint32_t tstart = tile_range[2 * tile];
-    lo = (int)(d[1] - tstart);
-    seg_hi = (int)(d[2] - tstart);
+    lo = (int)(load_table_word(d + 1) - tstart);
+    seg_hi = (int)(load_table_word(d + 2) - tstart);
   } else {
     const uint32_t b = blockIdx.x - seg_blocks;                       // (seg_blocks is a multiple of 8: same XCD)
     if (seg.tile_order) {
@@ -586,7 +632,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
       if ((int)b >= num_tiles) return;
       tile = gsr_xcd_remap((int)b, num_tiles);
     }
-    if (seg.tile_seg && seg.tile_seg[2 * tile + 1] != 0u) return;     // segmented tile: its segment blocks handle it
+    if (seg.tile_seg && load_table_word(seg.tile_seg + 2 * tile + 1) != 0u) return;     // segmented tile: its segment blocks handle it
   }
   const int lane = (int)threadIdx.x;
   const int tx = tile % tiles_x, ty = tile / tiles_x;
@@ -604,32 +650,58 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
     T2[h] = GSR_V2(1.f); ga2[h] = GSR_V2(0.f);
     g2[h][0] = g2[h][1] = g2[h][2] = GSR_V2(0.f);
   }
+  // Entry state.  Every address is known here, so all loads are issued back to back -- a pixel outside the image reads
+  // the clamped pixel (always a valid address) and is set to its out-of-image values afterwards -- and waited for ONCE:
+  // the empty asm below takes every loaded register, which keeps the compiler from sinking a load behind the early
+  // return or folding arithmetic (and with it a wait) into the segment branch.
+  v4f tc[4];
+  typename ChanVec<C>::type img[4], g_in[4];
+  float t_in[4];
+  int last_in[4];
+  size_t pixc[4];
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
-    const int px = px0 + 8 * (p & 1), py = py0 + 8 * (p >> 1);
-    const int h = p >> 1;
-    lastc[p] = 0;
-    if (px < W && py < H) {
-      const size_t pix = (size_t)py * W + px;
-      float t = final_T[pix];
-      float4 tc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (is_seg) {                                   // T after this segment (dead-at-entry pixels never contribute)
-        tc = seg.seg_TC[256 * (size_t)sidx + 64 * p + lane];
-        t = tc.x < 0.f ? 1.f : tc.x;
-      }
-      const float upto[3] = {tc.y, tc.z, tc.w};
-      if (p & 1) T2[h].y = t; else T2[h].x = t;
-      lastc[p] = last[pix];
-      float gb = 0.f;
+    const int px = min(px0 + 8 * (p & 1), W - 1), py = min(py0 + 8 * (p >> 1), H - 1);
+    pixc[p] = (size_t)py * W + px;
+    tc[p] = (v4f){0.f, 0.f, 0.f, 0.f};
+    img[p] = 0.f;
+  }
+  if (is_seg) {                                       // (wave-uniform; only issues loads)
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float gv = dL_dimage[pix * C + c];
-        if (p & 1) g2[h][c].y = gv; else g2[h][c].x = gv;
-        // colour behind the segment = final colour - colour composited up to the segment's end
-        if (is_seg) gb = fmaf(gv, image[pix * C + c] - upto[c], gb);
-      }
-      if (p & 1) ga2[h].y = gb; else ga2[h].x = gb;   // g . (colour behind the segment); 0 for a whole tile
+    for (int p = 0; p < 4; ++p) {
+      tc[p] = reinterpret_cast<const v4f*>(seg.seg_TC)[256 * (size_t)sidx + 64 * p + lane];
+      __builtin_memcpy(&img[p], image + pixc[p] * C, sizeof(float) * C);
     }
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    t_in[p] = final_T[pixc[p]];
+    last_in[p] = last[pixc[p]];
+    __builtin_memcpy(&g_in[p], dL_dimage + pixc[p] * C, sizeof(float) * C);
+  }
+  asm volatile("" : "+v"(tc[0]), "+v"(tc[1]), "+v"(tc[2]), "+v"(tc[3]), "+v"(img[0]), "+v"(img[1]), "+v"(img[2]),
+                    "+v"(img[3]), "+v"(g_in[0]), "+v"(g_in[1]), "+v"(g_in[2]), "+v"(g_in[3]), "+v"(t_in[0]),
+                    "+v"(t_in[1]), "+v"(t_in[2]), "+v"(t_in[3]), "+v"(last_in[0]), "+v"(last_in[1]), "+v"(last_in[2]),
+                    "+v"(last_in[3]));
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const bool inside = (px0 + 8 * (p & 1)) < W && (py0 + 8 * (p >> 1)) < H;
+    const int h = p >> 1;
+    float t = t_in[p];
+    if (is_seg) t = tc[p].x < 0.f ? 1.f : tc[p].x;    // T after this segment (dead-at-entry pixels never contribute)
+    const float upto[3] = {tc[p].y, tc[p].z, tc[p].w};
+    t = inside ? t : 1.f;
+    if (p & 1) T2[h].y = t; else T2[h].x = t;
+    lastc[p] = inside ? last_in[p] : 0;
+    float gb = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float gv = inside ? chan(g_in[p], c) : 0.f;
+      if (p & 1) g2[h][c].y = gv; else g2[h][c].x = gv;
+      // colour behind the segment = final colour - colour composited up to the segment's end
+      if (is_seg) gb = fmaf(gv, chan(img[p], c) - upto[c], gb);
+    }
+    if (p & 1) ga2[h].y = gb; else ga2[h].x = gb;     // g . (colour behind the segment); 0 for a whole tile
     tile_last = max(tile_last, lastc[p]);
   }
 #pragma unroll
@@ -637,7 +709,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
   tile_last = __builtin_amdgcn_readfirstlane(tile_last);
   const int hi = min(tile_last, seg_hi);
   if (hi <= lo) return;
-  __shared__ float red[12 * 80];
+  __shared__ float red[11 * 68];
   const int rslot = lane < 44 ? (lane >> 2) * 68 + (lane & 3) * 16 : 0;   // reader 4k+p: quarter p of value k (68-word rows)
 
   for (int cbase = lo + (((hi - lo - 1) >> 6) << 6); cbase >= lo; cbase -= 64) {
@@ -645,11 +717,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
     // pairs that touched no pixel in the forward pass are skipped without evaluating anything
     // one coalesced vector load per 64 pairs for the skip flags, the packed ranks and the slot ids; a pair's
     // values are then broadcast with v_readlane (no dependent index load in front of the record fetch)
-    const uint32_t li = start + (uint32_t)cbase + (uint32_t)lane;
-    const float pv = (lane < n) ? pair_vis[li] : 0.f;
-    const int my_rank = (lane < n) ? (int)sorted_rank[li] : 0;
-    const int my_inst = (lane < n) ? (int)sorted_inst[li] : 0;
-    uint64_t flags = __ballot(pv > 0.f);
+    // (the three loads go out together, at an address clamped to the chunk's last pair: under `lane < n` they would sit
+    // in branches of their own, the flags waited for before the other two are even requested)
+    const uint32_t li = start + (uint32_t)cbase + (uint32_t)min(lane, n - 1);
+    float pv = pair_vis[li];
+    int my_rank = (int)sorted_rank[li];
+    int my_inst = (int)sorted_inst[li];
+    asm volatile("" : "+v"(pv), "+v"(my_rank), "+v"(my_inst));       // one wait for the three (see the entry state)
+    uint64_t flags = __ballot(lane < n && pv > 0.f);
     if (flags == 0ull) continue;
     int j = 63 - __builtin_clzll(flags);
     Splat nxt = load_splat_packed<C, true>(rec, (uint32_t)__builtin_amdgcn_readlane(my_rank, j));
@@ -730,9 +805,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
       // swaps + 9 adds + 12 DPP steps of the register-only transposing tree (the VALU is the binding unit here, the LDS
       // pipe is idle otherwise).  Each value has a row of 68 words: its 64 lanes' cells, parked by lane id with
       // ds_write_addtid_b32 (no per-lane address register, the rows at 16-bit immediate offsets), plus 4 words of padding
-      // so that the 16-byte reads are conflict-free.  (`red` still has the size of an earlier 80-word row layout.)
+      // so that the 16-byte reads are conflict-free (`red`: 11 rows of 68 words).
       // Fixed association order => bit-reproducible.
       {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"       // (m0 is a reserved register; the block does overwrite it)
         asm volatile("s_mov_b32 m0, %11\n"
                      "s_nop 0\n"                                  /* hazard: SALU write of M0 -> LDS add-TID needs a wait state */
                      "ds_write_addtid_b32 %0 offset:0\n"
@@ -747,7 +824,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_K7_WAVES
                      "ds_write_addtid_b32 %9 offset:2448\n"
                      "ds_write_addtid_b32 %10 offset:2720\n"
                      :: "v"(du), "v"(dv), "v"(dA), "v"(dB), "v"(dC), "v"(dop), "v"(prune), "v"(split), "v"(df[0]), "v"(df[1]),
-                        "v"(df[2]), "s"((uint32_t)(uintptr_t)red) : "memory");
+                        "v"(df[2]), "s"((uint32_t)(uintptr_t)red) : "memory", "m0");
+#pragma clang diagnostic pop
         gsr_wave_lds_fence();                                  // parks above are visible to the reader lanes below
         const float4* rd = reinterpret_cast<const float4*>(red + rslot);
         const float4 a = rd[0], b = rd[1], c = rd[2], d = rd[3];

@@ -2,7 +2,8 @@
 // (u32 key, u32 value) pairs over an arbitrary bit range.  Hand-written for wave64; no rocPRIM.
 //
 // K5 of SURVEY.md §2a ("radix sort by (tile, depth) + tile ranges").  The path sorts twice:
-//   (1) the M visible splats by depth bits (32-bit keys, 4 passes)  -> depth order, ties by index (stable)
+//   (1) the M visible splats by depth bits (only the bit range between bits(near) and bits(far) of the 32-bit keys:
+//       27 bits for near 0.1 / far 100, three 9-bit passes)         -> depth order, ties by index (stable)
 //   (2) the O tile instances, emitted in depth order, by tile id (ceil(log2 tiles) bits, 2 passes)
 // so the big array moves through 2 passes instead of the 6 a fused 48-bit (tile|depth) key would need.
 #include "gsr_device.h"

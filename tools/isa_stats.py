@@ -91,6 +91,59 @@ def loop_mix(body, depth: int = 2) -> dict:
   return mix
 
 
+def blocks(body) -> list:
+  """The kernel's basic blocks in layout order: dict(label, loop, header, lines) -- `loop` is the label of the header of
+  the innermost loop the block belongs to (None outside every loop), from the compiler's block comments."""
+  out = [dict(label="entry", loop=None, header=False, lines=[])]
+  for ln in body:
+    s = ln.strip()
+    start = re.match(r"\.(LBB\d+_\d+):", s) or re.match(r"; %bb\.(\d+):", s)
+    if start:
+      out.append(dict(label=start.group(1).replace("LBB", "BB"), loop=None, header=False, lines=[]))
+    if start or (s.startswith(";") and not out[-1]["lines"]):        # the block's own comment lines
+      m = re.search(r"in Loop: Header=(BB\d+_\d+)", s)
+      if m:
+        out[-1]["loop"] = m.group(1)
+      elif re.search(r"This (Inner )?Loop Header", s):
+        out[-1]["loop"], out[-1]["header"] = out[-1]["label"], True
+      continue
+    if s and not s.startswith((";", ".")):
+      out[-1]["lines"].append(s)
+  return out
+
+
+def is_vmcnt_wait(line: str) -> bool:
+  return line.startswith("s_waitcnt") and "vmcnt" in line
+
+
+def four_pair_loops(body) -> list:
+  """K6: the innermost loops that hold the four-pair visibility reduction (v_permlane32_swap marks it), one per copy of
+  the walk: dict(header, blocks, vmcnt_waits, vmem) -- waits on the vector-memory counter and vector-memory instructions
+  inside the loop's own blocks."""
+  bl = blocks(body)
+  loops = []
+  for b in bl:
+    if b["loop"] and b["loop"] not in loops and any(l.startswith("v_permlane32_swap") for l in b["lines"]):
+      loops.append(b["loop"])
+  out = []
+  for h in loops:
+    mine = [b for b in bl if b["loop"] == h]
+    out.append(dict(header=h, blocks=len(mine),
+                    vmcnt_waits=sum(1 for b in mine for l in b["lines"] if is_vmcnt_wait(l)),
+                    vmem=sum(1 for b in mine for l in b["lines"] if classify(l.split()[0]) == "vmem")))
+  return out
+
+
+def prologue_vmcnt_waits(body) -> int:
+  """K7: waits on the vector-memory counter from the kernel's entry to its first loop (the chunk loop)."""
+  n = 0
+  for b in blocks(body):
+    if b["header"]:
+      return n
+    n += sum(1 for l in b["lines"] if is_vmcnt_wait(l))
+  raise ValueError("no loop in the kernel")
+
+
 def find(meta: dict, *needles: str) -> str:
   for name in meta:
     if all(n in name for n in needles):
@@ -112,6 +165,11 @@ def audit() -> dict:
                       s_barrier=sum(1 for ln in body if ln.strip().startswith("s_barrier")),
                       mfma=sum(1 for ln in body if "mfma" in ln), static_loop_mix=loop_mix(body, depth),
                       instructions=sum(1 for ln in body if ln.strip() and not ln.strip().startswith((";", "."))))
+  # where the composite walks wait for memory (tests/test_isa_budget_composite_waits.py)
+  out["composite_waits"] = {
+      "K6_fwd_C3_vis": dict(four_pair_loops=four_pair_loops(meta[find(meta, *picks["K6_fwd_C3_vis"])]["body"])),
+      "K6_segC_C3_vis": dict(four_pair_loops=four_pair_loops(meta[find(meta, *picks["K6_segC_C3_vis"])]["body"])),
+      "K7_bwd_C3": dict(prologue_vmcnt_waits=prologue_vmcnt_waits(meta[find(meta, *picks["K7_bwd_C3"])]["body"]))}
   out["all_kernels"] = {n: dict(vgpr=k["vgpr"], scratch_bytes=k["scratch"]) for n, k in meta.items()}
   return out
 
@@ -122,9 +180,11 @@ if __name__ == "__main__":
     print(json.dumps(a))
   else:
     for label, k in a.items():
-      if label == "all_kernels":
+      if label in ("all_kernels", "composite_waits"):
         continue
       print(f"{label:18s} vgpr {k['vgpr']:3d}  sgpr {k['sgpr']:3d}  scratch {k['scratch_bytes']} B  lds {k['lds_bytes']} B  "
             f"s_barrier {k['s_barrier']}  mfma {k['mfma']}  loop mix {k['static_loop_mix']}")
+    for label, w in a["composite_waits"].items():
+      print(f"{label:18s} waits {w}")
     worst = max(a["all_kernels"].values(), key=lambda k: k["scratch_bytes"])
     print(f"{len(a['all_kernels'])} kernels in composite.hip; max scratch {worst['scratch_bytes']} B")
