@@ -720,6 +720,24 @@ int gsr_filter3d_backward(const float* log_scaling, const float* alpha_logit, co
                           const float* d_out_log_scaling, const float* d_out_alpha_logit, float* d_log_scaling,
                           float* d_alpha_logit, void* stream);
 
+/* ---- MCMC controller: position noise (controller/mcmc_controller.py:93-100, made to reach the scene) --------------------
+ * gsr_mcmc_noise, in place on position [N, 3]; log_scaling [N, 3], rotation_xyzw [N, 4], alpha_logit [N] float32 and
+ *   points_in_view [N] int16, contiguous.  Row i with points_in_view[i] > min_views:  o = sigmoid(alpha_logit[i]), h = opacity_threshold / 2,
+ *   level = sigmoid(-(o - h) margin / h) noise_level (soft_lt(o, h, margin) of util/misc.py), sigma_j =
+ *   max(exp(log_scaling[i][j]), scale_eps);  position[i] += R(q / max(|q|, 1e-12)) (sigma * (xi level)) with xi the first
+ *   three of the four normals that Box-Muller makes of the Philox4x32-10 words at key (seed lo, seed hi), counter
+ *   (i lo, i hi, step lo, step hi): u = ((w >> 8) + 0.5) 2^-24 per word, sqrt(-2 ln u_a) (cos, sin)(2 pi u_b) on the pairs
+ *   (0, 1) and (2, 3).  A row with too few views, or whose level max_j sigma_j is 0 in float32, is neither read beyond
+ *   points_in_view and alpha_logit nor written.  No atomics, no generator state: row i depends on its own inputs, seed,
+ *   step and i alone.  0 <= N <= GSR_NEIGHBOURS_MAX_N (0: nothing is launched), opacity_threshold > 0, margin,
+ *   noise_level and scale_eps >= 0.
+ * gsr_mcmc_draws: the words [N, 4] uint32 (16-byte aligned) and the three normals [N, 3] float32 of rows 0..N-1 from the
+ *   same device functions; either may be NULL. */
+int gsr_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
+                   const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
+                   float noise_level, float scale_eps, uint64_t seed, uint64_t step, void* stream);
+int gsr_mcmc_draws(int64_t N, uint64_t seed, uint64_t step, uint32_t* words_out, float* normals_out, void* stream);
+
 /* ---- SH export fit: per-point least squares of SH coefficients to view-dependent colours (no reference counterpart) ----
  * One row of gsr_sh_fit_row_doubles(K) = K (K + 1) / 2 + 3 K + 1 doubles per point (0 for a K outside {1, 4, 9, 16}): the
  * lower triangle of G = sum w Y Y^T, b_c = sum w Y (y_c - 0.5) channel-major, W = sum w, with Y the basis of gsr_sh_forward

@@ -24,6 +24,8 @@ from .evaluation import (Evaluation, compute_psnr, evaluate_scene, fit_colors, f
                          mse_to_psnr)
 from .filter3d import sampling_rate, smooth_gaussians
 from .sh_fit import ShFit, fit_sh
+from .controller import (Controller, ControllerConfig, DisabledConfig, DisabledController, MCMCConfig, MCMCController,
+                         Progress, TargetConfig, TargetController, densify_and_prune, mcmc_noise)
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -38,4 +40,6 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "select_batch", "sample_batch", "sample_batch_grouped", "sinkhorn", "BatchOverlapSampler",
            "BatchOverlapSamplerConfig", "RandomSampler", "RandomSamplerConfig", "Evaluation", "compute_psnr",
            "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene", "sampling_rate",
-           "smooth_gaussians", "ShFit", "fit_sh"]
+           "smooth_gaussians", "ShFit", "fit_sh", "Progress", "ControllerConfig", "Controller", "DisabledConfig",
+           "DisabledController", "TargetConfig", "TargetController", "MCMCConfig", "MCMCController", "densify_and_prune",
+           "mcmc_noise"]

@@ -26,7 +26,7 @@ class GsplatHipError(RuntimeError):
 # ABI's structs is POINTER(mirror), a `const char*` return is c_char_p and every other pointer -- every pointer field of
 # a struct included -- is c_void_p (ctypes then takes a plain int address, no wrapper object per argument).
 SCALARS = {"float": C.c_float, "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
-           "size_t": C.c_size_t}
+           "uint64_t": C.c_uint64, "size_t": C.c_size_t}
 
 _TYPE = r"\s*(const\s+)?(\w+)\s*(\*?)\s*"
 _DECLARATOR = r"\w+(?:\[\d+\])?"

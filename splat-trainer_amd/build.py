@@ -18,8 +18,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 HOSTMATH_PATH = os.path.join(PKG_DIR, "libgsr_hostmath.so")
 HIP_SOURCES = ["prims.hip", "geometry.hip", "binning.hip", "composite.hip", "frame.hip", "ssim.hip", "optim.hip", "densify.hip",
-               "bilagrid.hip", "neighbours.hip", "color_model.hip", "reg.hip", "visibility.hip", "eval.hip", "filter3d.hip", "sh_fit.hip"]
-HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_visibility.h", "gsr_eval.h", "gsr_filter3d.h", "gsr_sh_fit.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_wide.inc",
+               "bilagrid.hip", "neighbours.hip", "color_model.hip", "reg.hip", "visibility.hip", "eval.hip", "filter3d.hip", "sh_fit.hip", "controller.hip"]
+HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_visibility.h", "gsr_eval.h", "gsr_filter3d.h", "gsr_sh_fit.h", "gsr_controller.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_wide.inc",
            os.path.join("..", "..", "include", "gsplat_hip.h")]
 
 
@@ -54,7 +54,7 @@ def build_hostmath(force: bool = False, verbose: bool = False) -> str:
   src = os.path.join(CSRC, "hostmath_shim.cpp")
   deps = [src, os.path.join(CSRC, "gsr_math.h"), os.path.join(CSRC, "gsr_bilagrid.h"), os.path.join(CSRC, "gsr_neighbours.h"),
           os.path.join(CSRC, "gsr_color.h"), os.path.join(CSRC, "gsr_visibility.h"), os.path.join(CSRC, "gsr_eval.h"),
-          os.path.join(CSRC, "gsr_filter3d.h"), os.path.join(CSRC, "gsr_sh_fit.h")]
+          os.path.join(CSRC, "gsr_filter3d.h"), os.path.join(CSRC, "gsr_sh_fit.h"), os.path.join(CSRC, "gsr_controller.h")]
   if not force and _newer(HOSTMATH_PATH, deps):
     return HOSTMATH_PATH
   cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", HOSTMATH_PATH, src]

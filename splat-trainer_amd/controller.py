@@ -1,0 +1,419 @@
+"""The reference's ``controller/`` package (``controller.py``, ``disabled.py``, ``target_controller.py``,
+``mcmc_controller.py`` and ``densify_and_prune`` / ``log_histograms`` of ``point_state.py:59-110``) over this package's
+pieces: ``controller_math.PointState`` / ``take_n`` / ``find_split_prune_indexes``, the scene's ``split_and_prune`` and one
+native kernel for the MCMC controller's per-step position noise (csrc/controller.hip, maths in csrc/gsr_controller.h).
+
+What differs from the reference's surface, because the packages behind it are not here: no hydra, beartype or tensordict.
+A schedule-valued field (``TargetConfig.densify_prune_interval``, ``MCMCConfig.noise_level``) is a number or a callable of
+``t``.  ``scene`` is duck-typed -- ``num_points``, ``device``, ``points`` (a ``ParameterClass``) and
+``split_and_prune(keep_mask, split_idx)`` -- and ``logger`` is None or anything with ``log_values`` / ``log_histogram``.
+``TargetController.step`` does not empty the allocator's cache: that is the trainer's choice.
+
+Two deliberate deviations from ``mcmc_controller.py``:
+
+* its noise branch perturbs ``self.scene.points.tensors[enough_views]``, which with a bool mask is a COPY: ``position +=``
+  never reaches the scene and the reference's noise is a no-op.  Here the noise is applied to ``scene.points.position``
+  in place, on the rows with ``points_in_view > min_views`` -- the evident intent;
+* its prune branch takes the ``n`` top-scored rows with an unstable ``argsort`` over scores of which the pruned rows
+  are zeroed, so pruned rows may be picked among the zeros.  Here a pruned row is never split
+  (``split_mask &= ~prune_mask``); the point count then falls by the overlap.
+
+The noise is drawn by a counter-based generator (Philox4x32-10) keyed on (``MCMCConfig.seed``, step, point index), not by
+``torch.randn``: data-parallel replicas that hold full parameter copies add the SAME noise with no communication, and a
+run restarted from a checkpoint repeats itself.  ``max_prune_rate`` of the reference's dataclass is read nowhere and is
+left out.
+"""
+from __future__ import annotations
+
+from abc import ABCMeta, abstractmethod
+from dataclasses import dataclass, fields
+from typing import Any, Callable, Optional, Tuple, Union
+
+import torch
+
+from . import _lib
+from .controller_math import PointState, find_split_prune_indexes, take_n
+
+_ptr = _lib.ptr
+
+Schedule = Union[float, int, Callable[[float], float]]
+GATE_MARGIN = 16.0                # soft_lt(opacity, threshold / 2, margin=16.0), mcmc_controller.py:95
+SCALE_EPS = 1e-4                  # point_basis(eps=1e-4), gaussians/split.py:17
+
+
+def _clamp(x: float, lo: float, hi: float) -> float:
+  return max(lo, min(x, hi))
+
+
+@dataclass(frozen=True)
+class Progress:
+  """config/__init__.py:25-34."""
+  step: int
+  total_steps: int
+  logging_step: bool = False
+
+  @property
+  def t(self) -> float:
+    return _clamp(self.step / self.total_steps, 0.0, 1.0)
+
+  def __float__(self) -> float:
+    return float(self.t)
+
+
+def eval_schedule(value: Schedule, t: Union[float, Progress]):
+  """A number as it is, a callable at ``t`` (config/__init__.py:181-188 without the ``Varying`` class)."""
+  return value(float(t)) if callable(value) else value
+
+
+def smoothstep(t: float, a: float, b: float) -> float:
+  """config/__init__.py:127-131 on the interval (0, 1)."""
+  t = _clamp(t, 0.0, 1.0)
+  return a + (b - a) * (3 * t ** 2 - 2 * t ** 3)
+
+
+# ---------------------------------------------------------------------------------------------------------- point state
+def _columns(state: PointState):
+  return [(f.name, getattr(state, f.name)) for f in fields(PointState)]
+
+
+def point_state_dict(state: PointState) -> dict:
+  return {k: v.detach().clone() for k, v in _columns(state)}
+
+
+def load_point_state(state: PointState, state_dict: dict) -> PointState:
+  """Copies ``state_dict`` into the columns of ``state`` (same lengths, the columns' own dtypes and device)."""
+  for k, v in _columns(state):
+    src = state_dict[k]
+    if tuple(src.shape) != tuple(v.shape):
+      raise ValueError(f"point state column {k}: {tuple(src.shape)} in the state dict, {tuple(v.shape)} in the controller")
+    v.copy_(src)
+  return state
+
+
+def log_histograms(points: PointState, logger, name: str = "densify"):
+  """point_state.py:61-72."""
+  def log_scale(k, t, min_val=1e-12):
+    logger.log_histogram(f"{name}/{k}", torch.log10(torch.clamp_min(t, min_val)))
+  log_scale("prune_cost", points.prune_cost)
+  log_scale("split_score", points.split_score)
+  log_scale("max_scale_px", points.max_scale_px, min_val=1e-6)
+  logger.log_histogram(f"{name}/points_in_view", points.points_in_view)
+  logger.log_histogram(f"{name}/visibility", points.visibility)
+
+
+@torch.no_grad()
+def densify_and_prune(state: PointState, scene, split_mask: torch.Tensor, prune_mask: torch.Tensor, logger=None,
+                      generator: Optional[torch.Generator] = None) -> PointState:
+  """point_state.py:76-110: logs the round's metrics, calls ``scene.split_and_prune(~(split | prune), split_idx)``
+  (``generator`` is passed on only when one is given) and returns the carried state: the kept rows of all five columns,
+  then zeros for the 2 n_split children."""
+  split_idx = split_mask.nonzero().squeeze(1)
+  n_prune, n_split = int(prune_mask.sum().item()), int(split_idx.shape[0])
+  n = int(state.prune_cost.shape[0])
+  if logger is not None:
+    metrics = dict(n=n, prune=n_prune, split=n_split,
+                   max_prune_score=state.prune_cost[prune_mask].max().item() if n_prune > 0 else 0.,
+                   min_split_score=state.split_score[split_idx].min().item() if n_split > 0 else 0.,
+                   unseen=n - int(torch.count_nonzero(state.prune_cost).item()))
+    logger.log_values("densify", metrics)
+    log_histograms(state, logger, "densify")
+  keep_mask = ~(split_mask | prune_mask)
+  if generator is None:
+    scene.split_and_prune(keep_mask, split_idx)
+  else:
+    scene.split_and_prune(keep_mask, split_idx, generator=generator)
+  return PointState(**{k: torch.cat([v[keep_mask], v.new_zeros(2 * n_split)]) for k, v in _columns(state)})
+
+
+# ------------------------------------------------------------------------------------------------------------ interface
+class ControllerConfig(metaclass=ABCMeta):
+  """controller/controller.py:9-17."""
+
+  @abstractmethod
+  def make_controller(self, scene, target_points: int, progress: Progress, logger=None) -> "Controller":
+    raise NotImplementedError
+
+  @abstractmethod
+  def from_state_dict(self, state_dict: dict, scene, target_points: int, progress: Progress, logger=None) -> "Controller":
+    raise NotImplementedError
+
+
+class Controller(metaclass=ABCMeta):
+  """controller/controller.py:20-37."""
+
+  @abstractmethod
+  def step(self, progress: Progress, log_details: bool = False):
+    """Perform densification and pruning."""
+    raise NotImplementedError
+
+  @abstractmethod
+  def add_rendering(self, image_idx: int, rendering, progress: Progress):
+    """Add a rendering to the controller."""
+    raise NotImplementedError
+
+  @abstractmethod
+  def state_dict(self) -> dict:
+    """Return controller state for checkpointing."""
+    raise NotImplementedError
+
+
+# ------------------------------------------------------------------------------------------------------------- disabled
+class DisabledConfig(ControllerConfig):
+  """controller/disabled.py:11-16."""
+
+  def make_controller(self, scene, target_points: int, progress: Progress, logger=None) -> "DisabledController":
+    return DisabledController(scene, logger)
+
+  def from_state_dict(self, state_dict: dict, scene, target_points: int, progress: Progress, logger=None
+                      ) -> "DisabledController":
+    return self.make_controller(scene, target_points, progress, logger)
+
+
+class DisabledController(Controller):
+  """controller/disabled.py:20-38: gathers the statistics (for the histograms), never touches the scene."""
+
+  def __init__(self, scene, logger=None):
+    self.scene = scene
+    self.logger = logger
+    self.points = PointState.new_zeros(scene.num_points, device=scene.device)
+
+  def __repr__(self):
+    return f"DisabledController(points={self.points.prune_cost.shape[0]})"
+
+  def step(self, progress: Progress, log_details: bool = False):
+    if log_details and self.logger is not None:
+      log_histograms(self.points, self.logger, "step")
+    self.points = PointState.new_zeros(self.points.prune_cost.shape[0], device=self.points.prune_cost.device)
+
+  def add_rendering(self, image_idx: int, rendering, progress: Progress):
+    self.points.add_rendering(rendering)
+
+  def state_dict(self) -> dict:
+    return {}
+
+
+# --------------------------------------------------------------------------------------------------------------- target
+@dataclass
+class TargetConfig(ControllerConfig):
+  """target_controller.py:17-46 (the dataclass's defaults; config/controller/target.yaml's prune_rate 0.025 is the
+  caller's to pass)."""
+  prune_rate: float = 0.04                    # base rate (relative to count) to prune points
+  target_count_t: float = 0.8                 # proportion of training when we hit the target count
+  min_views: int = 5                          # times a point is in view before it may be pruned
+  max_scale_px: float = 200                   # maximum screen-space size for a floater point (otherwise pruned)
+  min_split_px: float = 0.0                   # minimum max-screen-space size for a point to be split
+  densify_prune_interval: Schedule = 100
+
+  def make_controller(self, scene, target_points: int, progress: Progress, logger=None) -> "TargetController":
+    return TargetController(self, scene, target_points, progress, logger)
+
+  def from_state_dict(self, state_dict: dict, scene, target_points: int, progress: Progress, logger=None
+                      ) -> "TargetController":
+    controller = TargetController(self, scene, target_points, progress, logger, start_points=state_dict["start_points"])
+    load_point_state(controller.points, state_dict["points"])
+    return controller
+
+
+class TargetController(Controller):
+  """target_controller.py:50-148: every ``densify_prune_interval`` steps, prune the cheapest points and the oversized
+  ones and split the top-scored ones so that the count follows a smoothstep from ``start_points`` to ``target_points``."""
+
+  def __init__(self, config: TargetConfig, scene, target_points: int, progress: Progress, logger=None,
+               start_points: Optional[int] = None):
+    self.config = config
+    self.scene = scene
+    self.logger = logger
+    self.points = PointState.new_zeros(scene.num_points, device=scene.device)
+    self.start_points = start_points or scene.num_points
+    self.next_densify = self.find_next_densify(progress)
+    self.max_points = target_points
+
+  def __repr__(self):
+    return f"TargetController(points={self.points.prune_cost.shape[0]})"
+
+  def state_dict(self) -> dict:
+    return dict(points=point_state_dict(self.points), start_points=self.start_points)
+
+  def find_split_prune_indexes(self, t: float, target_points: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    c = self.config
+    return find_split_prune_indexes(self.points, t, target_points, prune_rate=c.prune_rate, min_views=c.min_views,
+                                    max_scale_px=c.max_scale_px, min_split_px=c.min_split_px)
+
+  def find_next_densify(self, progress: Progress) -> Optional[int]:
+    """target_controller.py:99-103."""
+    interval = eval_schedule(self.config.densify_prune_interval, progress.t)
+    next_densify = progress.step + interval
+    return next_densify if next_densify + interval < progress.total_steps else None
+
+  def target_points(self, progress: Progress) -> int:
+    """target_controller.py:106-109."""
+    target_step = self.config.target_count_t * progress.total_steps
+    t = _clamp(progress.step / target_step, 0.0, 1.0)
+    return int(smoothstep(t, self.start_points, self.max_points))
+
+  @torch.no_grad()
+  def step(self, progress: Progress, log_details: bool = False, generator: Optional[torch.Generator] = None):
+    """target_controller.py:111-126.  ``generator`` (beyond the reference): passed on to ``scene.split_and_prune``."""
+    if log_details and self.logger is not None:
+      log_histograms(self.points, self.logger, "step")
+    next_densify = self.next_densify
+    if next_densify is not None and progress.step >= next_densify:
+      split_mask, prune_mask = self.find_split_prune_indexes(progress.t, self.target_points(progress))
+      densify_and_prune(self.points, self.scene, split_mask, prune_mask, self.logger, generator=generator)
+      self.points = PointState.new_zeros(self.scene.num_points, device=self.scene.device)
+      self.next_densify = self.find_next_densify(progress)
+
+  def add_rendering(self, image_idx: int, rendering, progress: Progress):
+    self.points.add_rendering(rendering)
+
+
+# ----------------------------------------------------------------------------------------------------------------- mcmc
+def _check_rows(name: str, t: Any, shape: tuple, dtype: torch.dtype, device=None):
+  if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+    raise ValueError(f"{name} must be a tensor of shape {shape}, got "
+                     f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+  if t.dtype is not dtype:
+    raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+  if not t.is_cuda:
+    raise _lib.GsplatHipError(f"{name} is on {t.device}: the MCMC noise step runs on the HIP device only "
+                              "(there is no CPU fallback)")
+  if device is not None and t.device != device:
+    raise ValueError(f"inputs on different devices: {device}, {t.device}")
+
+
+def _u64(name: str, v) -> int:
+  v = int(v)
+  if not 0 <= v < 2 ** 64:
+    raise ValueError(f"{name} must be in [0, 2^64), got {v}")
+  return v
+
+
+@torch.no_grad()
+def mcmc_noise(position: torch.Tensor, log_scaling: torch.Tensor, rotation: torch.Tensor, alpha_logit: torch.Tensor,
+               points_in_view: torch.Tensor, *, min_views: int, opacity_threshold: float, noise_level: float, seed: int,
+               step: int, margin: float = GATE_MARGIN, scale_eps: float = SCALE_EPS) -> torch.Tensor:
+  """One noise step of the MCMC controller, IN PLACE on ``position`` (N, 3), which is returned: for every row with
+  ``points_in_view > min_views``
+
+      position += R(rotation / |rotation|) (max(exp(log_scaling), scale_eps) * (xi level))
+      level = soft_lt(sigmoid(alpha_logit), opacity_threshold / 2, margin) noise_level
+
+  with ``xi`` three standard normals drawn by Philox4x32-10 at key ``seed``, counter (row, ``step``): a row's noise
+  depends on its own values, the seed, the step and its index alone.  Rows with too few views or with a level that
+  underflows (opaque points) are not written.  One launch on the current stream, no host wait.  ``log_scaling`` (N, 3),
+  ``rotation`` (N, 4) xyzw, ``alpha_logit`` (N, 1) or (N,) float32, ``points_in_view`` (N,) int16; contiguous device
+  tensors, there is no CPU fallback."""
+  n = int(position.shape[0]) if isinstance(position, torch.Tensor) and position.dim() == 2 else -1
+  _check_rows("position", position, (n, 3), torch.float32)
+  dev = position.device
+  _check_rows("log_scaling", log_scaling, (n, 3), torch.float32, dev)
+  _check_rows("rotation", rotation, (n, 4), torch.float32, dev)
+  flat = isinstance(alpha_logit, torch.Tensor) and alpha_logit.dim() == 1
+  _check_rows("alpha_logit", alpha_logit, (n,) if flat else (n, 1), torch.float32, dev)
+  _check_rows("points_in_view", points_in_view, (n,), torch.int16, dev)
+  opacity_threshold, margin, noise_level, scale_eps = (float(opacity_threshold), float(margin), float(noise_level),
+                                                       float(scale_eps))
+  if not (opacity_threshold > 0 and margin >= 0 and noise_level >= 0 and scale_eps >= 0):
+    raise ValueError(f"need opacity_threshold > 0 and margin, noise_level, scale_eps >= 0, got {opacity_threshold}, "
+                     f"{margin}, {noise_level}, {scale_eps}")
+  seed, step = _u64("seed", seed), _u64("step", step)
+  if not position.is_contiguous():
+    raise ValueError("position must be contiguous: it is updated in place")
+  if n == 0:
+    return position
+  ls, rot, a, views = (t.detach().contiguous() for t in (log_scaling, rotation, alpha_logit, points_in_view))
+  with torch.cuda.device(dev):
+    _lib.check(_lib.load().gsr_mcmc_noise(_ptr(position.detach()), _ptr(ls), _ptr(rot), _ptr(a), _ptr(views), n,
+                                          int(min_views), opacity_threshold, margin, noise_level, scale_eps, seed, step,
+                                          _lib.current_stream_ptr()), "gsr_mcmc_noise")
+  return position
+
+
+def mcmc_draws(num_points: int, seed: int, step: int, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+  """What ``mcmc_noise`` draws for the rows 0..num_points-1 at (seed, step), from the same device functions: the raw
+  Philox words (N, 4), uint32 bit patterns held as int32, and the normals ``xi`` (N, 3) float32."""
+  n = int(num_points)
+  dev = torch.device(device)
+  if dev.type != "cuda":
+    raise _lib.GsplatHipError(f"mcmc_draws runs on the HIP device only, got {dev} (there is no CPU fallback)")
+  with torch.cuda.device(dev):
+    dev = torch.device("cuda", torch.cuda.current_device())
+    words = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().gsr_mcmc_draws(n, _u64("seed", seed), _u64("step", step), _ptr(words), _ptr(normals),
+                                          _lib.current_stream_ptr()), "gsr_mcmc_draws")
+  return words, normals
+
+
+@dataclass
+class MCMCConfig(ControllerConfig):
+  """mcmc_controller.py:24-50 without ``max_prune_rate`` (read nowhere there) and with ``seed``, the key of the noise."""
+  opacity_threshold: float = 0.1
+  prune_interval: int = 50
+  min_views: int = 5
+  max_scale_px: float = 200
+  min_split_px: float = 0.0
+  noise_level: Schedule = 100.0
+  seed: int = 0
+
+  def make_controller(self, scene, target_points: int, progress: Progress, logger=None) -> "MCMCController":
+    return MCMCController(self, scene, target_points, progress, logger)
+
+  def from_state_dict(self, state_dict: dict, scene, target_points: int, progress: Progress, logger=None
+                      ) -> "MCMCController":
+    controller = MCMCController(self, scene, target_points, progress, logger)
+    load_point_state(controller.points, state_dict["points"])
+    return controller
+
+
+class MCMCController(Controller):
+  """mcmc_controller.py:54-112.  Every ``prune_interval`` steps: prune the oversized and the nearly transparent points
+  and split as many top-scored ones (never a pruned one: the count falls by the overlap the reference's unstable sort
+  may produce); the statistics are carried across the round, the children start from zero.  Every other step: the
+  native noise step on ``scene.points.position`` in place -- the reference's own code perturbs a copy (a bool-mask
+  index), so its noise never reaches the scene; see the module docstring."""
+
+  def __init__(self, config: MCMCConfig, scene, target_points: int, progress: Progress, logger=None):
+    self.config = config
+    self.scene = scene
+    self.logger = logger
+    self.target_points = target_points
+    self.points = PointState.new_zeros(scene.num_points, device=scene.device)
+    self.num_points = scene.num_points
+
+  def __repr__(self):
+    return f"MCMCController(points={self.points.prune_cost.shape[0]})"
+
+  def state_dict(self) -> dict:
+    return {"points": point_state_dict(self.points)}
+
+  def find_split_prune_masks(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mcmc_controller.py:77-87 with ties to the lowest index (``take_n``) and no pruned row split."""
+    c, state = self.config, self.points
+    opacity = torch.sigmoid(self.scene.points.alpha_logit.detach()).reshape(-1)
+    prune_mask = (state.max_scale_px > c.max_scale_px) | (opacity < c.opacity_threshold)
+    n = int(prune_mask.sum().item())
+    too_small = state.max_scale_px < c.min_split_px
+    split_score = torch.where(prune_mask | too_small, torch.zeros_like(state.split_score), state.split_score)
+    split_mask = take_n(split_score, n, descending=True) & ~prune_mask
+    return split_mask, prune_mask
+
+  @torch.no_grad()
+  def step(self, progress: Progress, log_details: bool = False, generator: Optional[torch.Generator] = None):
+    """``generator`` (beyond the reference): passed on to ``scene.split_and_prune`` on a prune step."""
+    c = self.config
+    if log_details and self.logger is not None:
+      log_histograms(self.points, self.logger, "step")
+    if progress.step % c.prune_interval == 0:
+      split_mask, prune_mask = self.find_split_prune_masks()
+      self.points = densify_and_prune(self.points, self.scene, split_mask, prune_mask, logger=self.logger,
+                                      generator=generator)
+      self.num_points = self.scene.num_points
+    else:
+      p = self.scene.points
+      mcmc_noise(p.position, p.log_scaling, p.rotation, p.alpha_logit, self.points.points_in_view,
+                 min_views=c.min_views, opacity_threshold=c.opacity_threshold,
+                 noise_level=eval_schedule(c.noise_level, progress.t), seed=c.seed, step=progress.step)
+
+  def add_rendering(self, image_idx: int, rendering, progress: Progress):
+    self.points.add_rendering(rendering)

@@ -10,6 +10,7 @@
 #include "gsr_visibility.h"
 #include "gsr_filter3d.h"
 #include "gsr_sh_fit.h"
+#include "gsr_controller.h"
 #include "gsr_color.h"
 #include "gsr_eval.h"
 
@@ -529,6 +530,44 @@ void hm_sh_fit_solve(const double* acc, int64_t N, int K, float ridge, float* sh
     case 4: shf_solve<4>(acc, N, ridge, sh, weight); break;
     case 9: shf_solve<9>(acc, N, ridge, sh, weight); break;
     case 16: shf_solve<16>(acc, N, ridge, sh, weight); break;
+  }
+}
+
+}  // extern "C"
+
+// MCMC position noise (gsr_controller.h) on the host's libm: the device's order of operations, one row at a time.
+extern "C" {
+
+void hm_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out) { gsr_philox4x32(counter, key, out); }
+
+// words [N, 4] and normals [N, 3] of rows first .. first + N - 1 (either may be NULL)
+void hm_mcmc_draws(uint64_t first, int64_t N, uint64_t seed, uint64_t step, uint32_t* words, float* normals) {
+  for (int64_t i = 0; i < N; ++i) {
+    uint32_t w[4];
+    float z[4];
+    gsr_mcmc_words(first + (uint64_t)i, seed, step, w);
+    gsr_mcmc_normals(w, z);
+    for (int j = 0; j < 4 && words; ++j) words[4 * i + j] = w[j];
+    for (int j = 0; j < 3 && normals; ++j) normals[3 * i + j] = z[j];
+  }
+}
+
+// level [N] of alpha_logit [N]
+void hm_mcmc_level(const float* alpha_logit, int64_t N, float opacity_threshold, float margin, float noise_level,
+                   float* level) {
+  for (int64_t i = 0; i < N; ++i) level[i] = gsr_mcmc_level(alpha_logit[i], opacity_threshold, margin, noise_level);
+}
+
+// the row loop of gsr_mcmc_noise, in place on position [N, 3]
+void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
+                   const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
+                   float noise_level, float scale_eps, uint64_t seed, uint64_t step) {
+  for (int64_t i = 0; i < N; ++i) {
+    if (!(points_in_view[i] > min_views)) continue;
+    const float level = gsr_mcmc_level(alpha_logit[i], opacity_threshold, margin, noise_level);
+    if (level != 0.f)
+      gsr_mcmc_noise_row(position + 3 * i, log_scaling + 3 * i, rotation_xyzw + 4 * i, level, scale_eps, (uint64_t)i, seed,
+                         step);
   }
 }
 
