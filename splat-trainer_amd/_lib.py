@@ -31,29 +31,30 @@ SCALARS = {"float": C.c_float, "int": C.c_int, "int32_t": C.c_int32, "int64_t": 
 _TYPE = r"\s*(const\s+)?(\w+)\s*(\*?)\s*"
 _DECLARATOR = r"\w+(?:\[\d+\])?"
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
-_FUNCTION = re.compile(_TYPE + r"(gsr_\w+)\s*\(([^(){};]*)\)\s*;")
+_FUNCTION = re.compile(_TYPE + r"(\w+)\s*\(([^(){};]*)\)\s*;")
 _FIELD = re.compile(_TYPE + rf"({_DECLARATOR}(?:\s*,\s*{_DECLARATOR})*)\s*")      # `T a;`, `T a, b, c;`, `T a[7];`
 _ARGUMENT = re.compile(_TYPE + r"\w*\s*")
 _DEFINE = re.compile(r"#\s*define\s+(\w+)(\([^)]*\))?\s*(.*)")                     # group 2: a function-like macro
 _SPACE = re.compile(r"\s*")
 
 
-def parse_header(text: str):
+def parse_header(text: str, prefix: str = "gsr_", filename: str = "gsplat_hip.h"):
   """The ABI a header text declares, in declaration order: (constants, structs, functions) with constants name -> int
   (the object-like macros that have a value), structs name -> [(field, C type, array length or 0)] and functions
   name -> (return C type, [argument C types]).  Function-like macros, #include, #ifndef / #endif guards and
   `extern "C"` carry no ABI; anything else it cannot read -- any other directive (#if, #else, #pragma: they could change
-  what the compiler sees) and a name declared twice included -- raises GsplatHipError naming the line."""
+  what the compiler sees), a name declared twice, a function whose name lacks `prefix` and `void` held by value anywhere
+  but as a function's return type included -- raises GsplatHipError naming `filename` and the line."""
   constants, structs, functions = {}, {}, {}
 
   def fail(pos):
     line = text.count("\n", 0, pos) + 1
-    raise GsplatHipError(f"gsplat_hip.h:{line}: cannot parse {text.splitlines()[line - 1].strip()!r}")
+    raise GsplatHipError(f"{filename}:{line}: cannot parse {text.splitlines()[line - 1].strip()!r}")
 
-  def ctype(m, pos):
+  def ctype(m, pos, returned=False):
     const, base, star = m.group(1, 2, 3)
-    if not star and base not in SCALARS and base not in structs:      # held by value: a scalar or an earlier struct
-      fail(pos)
+    if not star and base not in SCALARS and base not in structs and not (returned and base == "void" and not const):
+      fail(pos)                                                       # held by value: a scalar or an earlier struct
     return ("const " if const else "") + base + star
 
   def declare(table, name, value, pos):
@@ -93,9 +94,10 @@ def parse_header(text: str):
       declare(structs, m.group(1), fields, pos)
     else:
       m = _FUNCTION.match(text, pos) or fail(pos)
+      m.group(4).startswith(prefix) or fail(pos)
       arguments = [] if m.group(5).strip() == "void" else m.group(5).split(",")
       declare(functions, m.group(4),
-              (ctype(m, pos), [ctype(_ARGUMENT.fullmatch(a) or fail(pos), pos) for a in arguments]), pos)
+              (ctype(m, pos, returned=True), [ctype(_ARGUMENT.fullmatch(a) or fail(pos), pos) for a in arguments]), pos)
     pos = _SPACE.match(text, m.end()).end()
   return constants, structs, functions
 
@@ -113,13 +115,14 @@ def make_mirrors(structs) -> dict:
 
 
 def make_prototypes(functions, mirrors) -> dict:
-  """name -> (restype, argtypes) for every parsed function."""
+  """name -> (restype, argtypes) for every parsed function; a `void` return is restype None."""
   def argument(ctype):
     base = ctype.removeprefix("const ").rstrip("*")
     if ctype.endswith("*"):
       return C.POINTER(mirrors[base]) if base in mirrors else C.c_void_p
     return SCALARS.get(base) or mirrors[base]
-  return {name: (C.c_char_p if ret == "const char*" else argument(ret), [argument(a) for a in args])
+  returns = {"const char*": C.c_char_p, "void": None}
+  return {name: (returns[ret] if ret in returns else argument(ret), [argument(a) for a in args])
           for name, (ret, args) in functions.items()}
 
 

@@ -8,6 +8,7 @@ host-only ``splat-trainer_amd/libgsr_hostmath.so`` used by the CPU unit tests of
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -19,8 +20,12 @@ LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 HOSTMATH_PATH = os.path.join(PKG_DIR, "libgsr_hostmath.so")
 HIP_SOURCES = ["prims.hip", "geometry.hip", "binning.hip", "composite.hip", "frame.hip", "ssim.hip", "optim.hip", "densify.hip",
                "bilagrid.hip", "neighbours.hip", "color_model.hip", "reg.hip", "visibility.hip", "eval.hip", "filter3d.hip", "sh_fit.hip", "controller.hip"]
-HEADERS = ["gsr_math.h", "gsr_bilagrid.h", "gsr_neighbours.h", "gsr_color.h", "gsr_visibility.h", "gsr_eval.h", "gsr_filter3d.h", "gsr_sh_fit.h", "gsr_controller.h", "gsr_device.h", "gsr_dpp_reduce.h", "composite_wide.inc",
-           os.path.join("..", "..", "include", "gsplat_hip.h")]
+PUBLIC_HEADER = os.path.join(PKG_DIR, "..", "include", "gsplat_hip.h")
+
+
+def _included(*patterns) -> list:
+  """Every file of csrc/ a source may include: the dependency lists are globbed, so a new header cannot be left out."""
+  return sorted(f for p in patterns for f in glob.glob(os.path.join(CSRC, p)))
 
 
 def _newer(target: str, sources) -> bool:
@@ -39,7 +44,7 @@ def _hipcc() -> str:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
   srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-  deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
+  deps = srcs + _included("*.h", "*.inc") + [PUBLIC_HEADER]
   if not force and _newer(LIB_PATH, deps):
     return LIB_PATH
   cmd = [_hipcc(), "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
@@ -52,12 +57,12 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
 
 def build_hostmath(force: bool = False, verbose: bool = False) -> str:
   src = os.path.join(CSRC, "hostmath_shim.cpp")
-  deps = [src, os.path.join(CSRC, "gsr_math.h"), os.path.join(CSRC, "gsr_bilagrid.h"), os.path.join(CSRC, "gsr_neighbours.h"),
-          os.path.join(CSRC, "gsr_color.h"), os.path.join(CSRC, "gsr_visibility.h"), os.path.join(CSRC, "gsr_eval.h"),
-          os.path.join(CSRC, "gsr_filter3d.h"), os.path.join(CSRC, "gsr_sh_fit.h"), os.path.join(CSRC, "gsr_controller.h")]
-  if not force and _newer(HOSTMATH_PATH, deps):
+  if not force and _newer(HOSTMATH_PATH, [src] + _included("*.h")):
     return HOSTMATH_PATH
-  cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", HOSTMATH_PATH, src]
+  # every entry point is declared in hostmath_shim.h, which the shim includes: with this flag the compiler rejects a
+  # definition that has no declaration there (and, C linkage, always one that disagrees with its declaration)
+  cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Werror=missing-declarations",
+         "-o", HOSTMATH_PATH, src]
   if verbose:
     print(" ".join(cmd), flush=True)
   subprocess.run(cmd, check=True, cwd=CSRC)

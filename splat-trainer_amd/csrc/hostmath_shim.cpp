@@ -1,6 +1,9 @@
 // CPU unit-test shim: exposes the per-splat maths of gsr_math.h (the very source the HIP kernels compile)
 // to the `-m "not gpu"` tests.  It is NOT a product path: nothing in the package calls it, it renders
-// nothing, and the rasterizer fails loudly without libgsplat_hip.so.
+// nothing, and the rasterizer fails loudly without libgsplat_hip.so.  Its entry points are declared, with the layout of
+// their arrays, in hostmath_shim.h: the build rejects a definition that has no declaration there or disagrees with it.
+#include "hostmath_shim.h"
+
 #include <stdint.h>
 #include <string.h>
 
@@ -16,7 +19,6 @@
 
 extern "C" {
 
-// params: 8 x 4 bytes laid out as GsrRasterParams
 void hm_project_forward(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
                         const float* ls, const float* rot, const float* logit, float* g2d, float* depth,
                         float* sscale) {
@@ -47,7 +49,6 @@ void hm_project_backward(const float* T, const float* proj, const void* params, 
   }
 }
 
-// per-splat camera terms of the K2 backward: cam[M, 16] (gsr_math.h: GSR_CAM_GRAD_FLOATS layout), overwritten
 void hm_project_backward_camera(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
                                 const float* ls, const float* rot, const float* logit, const float* dg2d,
                                 const float* ddepth, float* cam) {
@@ -61,7 +62,6 @@ void hm_project_backward_camera(const float* T, const float* proj, const void* p
   }
 }
 
-// dT[12] += the fold of dL/d(camera position) dcam[3] through cam = -R^T t
 void hm_fold_camera_position(const float* T, const float* dcam, float* dT) {
   const float proj[4] = {1.f, 1.f, 0.f, 0.f};
   gsr_fold_camera_position(gsr_load_cam(T, proj), dcam, dT);
@@ -87,7 +87,6 @@ void hm_sh_basis(int K, int64_t M, const float* dirs, float* Y) {
   }
 }
 
-// per-splat tile hit mask over the whole tile grid: hits[m * tiles_x * tiles_y + ty * tiles_x + tx]
 void hm_tile_hits(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, uint8_t* hits) {
   GsrRasterParams rp;
   memcpy(&rp, params, sizeof(rp));
@@ -123,7 +122,6 @@ void hm_bilagrid_forward(const float* grid, int L, int GH, int GW, const float* 
     }
 }
 
-// d_rgb [H, W, 3] and d_grid [12, L, GH, GW] (summed in double, overwritten)
 void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, const float* d_out,
                           float* d_rgb, float* d_grid) {
   float cols[4 * 64 * GSR_BG_CH];
@@ -158,7 +156,6 @@ void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float*
 }
 
 // ---- colour fit of the evaluation pass (gsr_eval.h) -----------------------------------------------------------------
-// sums [3][45]: the moments of iterate x [P, 3] against ref over the pixels unclipped in x0, x and ref, in pixel order
 void hm_color_fit_moments(const float* x0, const float* x, const float* ref, int64_t P, float eps, double* sums) {
   const float lo = eps, hi = (float)(1.0 - (double)eps);
   for (int k = 0; k < 3 * GSR_EV_SUMS; ++k) sums[k] = 0.0;
@@ -173,15 +170,11 @@ void hm_color_fit_moments(const float* x0, const float* x, const float* ref, int
   }
 }
 
-// w [10]: the weights of one channel from its 45 sums
 void hm_color_fit_solve(const double* sums, double* w) {
   double work[GSR_EV_WORK];
   gsr_ev_solve(sums, work, w);
 }
 
-// The whole fit in the device's order of operations (eval.hip): min(ceil(P / 256), 1024) blocks of 256 threads, a thread
-// takes the pixels block * 256 + thread + i * blocks * 256 in ascending order, 64 lanes are added in the shuffle tree
-// v[l] += v[l + off] (off = 32 .. 1), the 4 waves in order, then the blocks' slots in order.  out [P, 3].
 void hm_color_fit(const float* x0, const float* ref, int64_t P, int num_iters, float eps, float* out) {
   const float lo = eps, hi = (float)(1.0 - (double)eps);
   const int64_t want = (P + 255) / 256;
@@ -237,9 +230,7 @@ void hm_color_fit(const float* x0, const float* ref, int64_t P, int num_iters, f
 }
 
 
-// brute-force kNN and nearest-centroid assignment (gsr_neighbours.h), one sweep over j = 0 .. N-1 per query: the
-// device's results bit for bit.  Rows [i0, i1) of dist2 [N, k], idx [N, k] int64 and scale [N], written from row 0 of
-// the outputs; returns -1 for k outside 1..16, N <= k or a bad row range.
+// brute-force kNN and nearest-centroid assignment (gsr_neighbours.h): the device's results bit for bit.
 }  // extern "C"
 
 template <int K>
@@ -316,7 +307,6 @@ static void hm_cm_rsh_s(const float* d, int64_t n, float* out, const float* dsh,
 
 extern "C" {
 
-// out [n, (S+1)^2] (NULL: skipped); dd [n, 3] = sum_c dsh[c] dY_c/dd (NULL: skipped).  Returns -1 for S outside 0..5.
 int hm_cm_rsh(int S, const float* d, int64_t n, float* out, const float* dsh, float* dd) {
   switch (S) {
     case 0: hm_cm_rsh_s<0>(d, n, out, dsh, dd); return 0;
@@ -329,7 +319,6 @@ int hm_cm_rsh(int S, const float* d, int64_t n, float* out, const float* dsh, fl
   }
 }
 
-// rows u [n, F]: y = LayerNorm(u) and du for an upstream dy
 void hm_cm_layernorm(const float* u, int64_t n, int F, const float* dy, float* y, float* du) {
   for (int64_t i = 0; i < n; ++i) {
     const float* r = u + i * F;
@@ -355,7 +344,6 @@ void hm_cm_glu(const float* a, const float* b, const float* dh, int64_t n, float
   }
 }
 
-// o [n, 4] -> out [n, 3]; do_ [n, 4] for an upstream dout [n, 3]
 void hm_cm_lum(const float* o, int64_t n, float bias, const float* dout, float* out, float* do_) {
   for (int64_t i = 0; i < n; ++i) {
     gsr_cm_lum(o + 4 * i, bias, out + 3 * i);
@@ -363,7 +351,6 @@ void hm_cm_lum(const float* o, int64_t n, float bias, const float* dout, float* 
   }
 }
 
-// v [n, 3] -> d = F.normalize(v) and dv for an upstream dd
 void hm_cm_normalize(const float* v, const float* dd, int64_t n, float* d, float* dv) {
   for (int64_t i = 0; i < n; ++i) {
     float inv;
@@ -378,7 +365,6 @@ void hm_cm_normalize(const float* v, const float* dd, int64_t n, float* d, float
 // frustum point queries and view features (gsr_visibility.h): the device's results bit for bit.
 extern "C" {
 
-// points [N, 3], records [V, 16]; point_counts [N] / camera_counts [V] int32 (either may be NULL).
 void hm_frustum_counts(const float* p, int64_t N, const float* rec, int64_t V, float depth_below, int32_t* point_counts,
                        int32_t* camera_counts) {
   if (camera_counts) for (int64_t c = 0; c < V; ++c) camera_counts[c] = 0;
@@ -393,8 +379,6 @@ void hm_frustum_counts(const float* p, int64_t N, const float* rec, int64_t V, f
   }
 }
 
-// labels [N] int64 in [0, K); idx [M] int64 distinct in [0, N), vis [M]; out [K]; point_visible [N] int32 (may be NULL)
-// is incremented.  Returns -1 for a label or an index out of range.
 int hm_view_features(const int64_t* labels, int64_t N, int64_t K, const int64_t* idx, const float* vis, int64_t M,
                      float threshold, float* out, int32_t* point_visible) {
   for (int64_t i = 0; i < N; ++i)
@@ -441,7 +425,6 @@ int hm_view_features(const int64_t* labels, int64_t N, int64_t K, const int64_t*
 // sampling rate and 3-D smoothing filter (gsr_filter3d.h) on the host's libm: the device's order of operations.
 extern "C" {
 
-// points [N, 3], records [V, 16], focal [V]; rate [N]
 void hm_sampling_rate(const float* p, int64_t N, const float* rec, const float* focal, int64_t V, float margin,
                       float* rate) {
   for (int64_t i = 0; i < N; ++i) {
@@ -452,7 +435,6 @@ void hm_sampling_rate(const float* p, int64_t N, const float* rec, const float* 
   }
 }
 
-// ls / out_ls [N, 3], a / rate / out_a [N]
 void hm_filter3d_forward(const float* ls, const float* a, const float* rate, int64_t N, float strength, float* out_ls,
                          float* out_a) {
   for (int64_t i = 0; i < N; ++i) {
@@ -512,7 +494,6 @@ extern "C" {
 
 int hm_sh_fit_row_doubles(int K) { return gsr_shf_row_doubles(K); }
 
-// pos [N, 3], idx / wts [M], col [M, 3], cam [3]; acc [N, R(K)] is added to
 void hm_sh_fit_accumulate(const float* pos, int64_t N, const int64_t* idx, int64_t M, const float* col, const float* wts,
                           const float* cam, int K, double* acc) {
   switch (K) {
@@ -523,7 +504,6 @@ void hm_sh_fit_accumulate(const float* pos, int64_t N, const int64_t* idx, int64
   }
 }
 
-// acc [N, R(K)]; sh [N, 3, K], weight [N]
 void hm_sh_fit_solve(const double* acc, int64_t N, int K, float ridge, float* sh, float* weight) {
   switch (K) {
     case 1: shf_solve<1>(acc, N, ridge, sh, weight); break;
@@ -540,7 +520,6 @@ extern "C" {
 
 void hm_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out) { gsr_philox4x32(counter, key, out); }
 
-// words [N, 4] and normals [N, 3] of rows first .. first + N - 1 (either may be NULL)
 void hm_mcmc_draws(uint64_t first, int64_t N, uint64_t seed, uint64_t step, uint32_t* words, float* normals) {
   for (int64_t i = 0; i < N; ++i) {
     uint32_t w[4];
@@ -552,13 +531,11 @@ void hm_mcmc_draws(uint64_t first, int64_t N, uint64_t seed, uint64_t step, uint
   }
 }
 
-// level [N] of alpha_logit [N]
 void hm_mcmc_level(const float* alpha_logit, int64_t N, float opacity_threshold, float margin, float noise_level,
                    float* level) {
   for (int64_t i = 0; i < N; ++i) level[i] = gsr_mcmc_level(alpha_logit[i], opacity_threshold, margin, noise_level);
 }
 
-// the row loop of gsr_mcmc_noise, in place on position [N, 3]
 void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
                    const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
                    float noise_level, float scale_eps, uint64_t seed, uint64_t step) {

@@ -1,0 +1,110 @@
+/* The ABI of the CPU unit-test shim (hostmath_shim.cpp -> libgsr_hostmath.so): every hm_* entry point is declared here and
+ * nowhere else.  The shim compiles with -Werror=missing-declarations, so a definition without a declaration here, or one
+ * that disagrees with it, does not build; tests/hostmath.py derives the ctypes binding from this text with
+ * _lib.parse_header, the reader of include/gsplat_hip.h, so it stays in that dialect: plain C, no conditionals. */
+#ifndef GSR_HOSTMATH_SHIM_H
+#define GSR_HOSTMATH_SHIM_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- per-splat projection, SH basis and tile test (gsr_math.h) ---- */
+/* params: 8 x 4 bytes laid out as GsrRasterParams */
+void hm_project_forward(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
+                        const float* ls, const float* rot, const float* logit, float* g2d, float* depth,
+                        float* sscale);
+void hm_project_backward(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
+                         const float* ls, const float* rot, const float* logit, const float* dg2d,
+                         const float* ddepth, float* dpos, float* dls, float* drot, float* dlogit);
+/* per-splat camera terms of the K2 backward: cam[M, 16] (gsr_math.h: GSR_CAM_GRAD_FLOATS layout), overwritten */
+void hm_project_backward_camera(const float* T, const float* proj, const void* params, int64_t M, const float* pos,
+                                const float* ls, const float* rot, const float* logit, const float* dg2d,
+                                const float* ddepth, float* cam);
+/* dT[12] += the fold of dL/d(camera position) dcam[3] through cam = -R^T t */
+void hm_fold_camera_position(const float* T, const float* dcam, float* dT);
+void hm_in_view(const float* T, const float* proj, int64_t N, const float* pos, int W, int H, float near_p,
+                float far_p, float margin, uint8_t* mask);
+void hm_sh_basis(int K, int64_t M, const float* dirs, float* Y);
+/* per-splat tile hit mask over the whole tile grid: hits[m * tiles_x * tiles_y + ty * tiles_x + tx] */
+void hm_tile_hits(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, uint8_t* hits);
+
+/* ---- bilateral-grid slice of one image (gsr_bilagrid.h) with ONE grid [12, L, GH, GW] ---- */
+void hm_bilagrid_forward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, float* out);
+/* d_rgb [H, W, 3] and d_grid [12, L, GH, GW] (summed in double, overwritten) */
+void hm_bilagrid_backward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, const float* d_out,
+                          float* d_rgb, float* d_grid);
+
+/* ---- colour fit of the evaluation pass (gsr_eval.h) ---- */
+/* sums [3][45]: the moments of iterate x [P, 3] against ref over the pixels unclipped in x0, x and ref, in pixel order */
+void hm_color_fit_moments(const float* x0, const float* x, const float* ref, int64_t P, float eps, double* sums);
+/* w [10]: the weights of one channel from its 45 sums */
+void hm_color_fit_solve(const double* sums, double* w);
+/* The whole fit in the device's order of operations (eval.hip): min(ceil(P / 256), 1024) blocks of 256 threads, a thread
+ * takes the pixels block * 256 + thread + i * blocks * 256 in ascending order, 64 lanes are added in the shuffle tree
+ * v[l] += v[l + off] (off = 32 .. 1), the 4 waves in order, then the blocks' slots in order.  out [P, 3]. */
+void hm_color_fit(const float* x0, const float* ref, int64_t P, int num_iters, float eps, float* out);
+
+/* ---- brute-force kNN and nearest-centroid assignment (gsr_neighbours.h): the device's results bit for bit ---- */
+/* one sweep over j = 0 .. N-1 per query.  Rows [i0, i1) of dist2 [N, k], idx [N, k] int64 and scale [N], written from
+ * row 0 of the outputs; returns -1 for k outside 1..16, N <= k or a bad row range. */
+int hm_knn(const float* p, int64_t N, int k, int64_t i0, int64_t i1, float* dist2, int64_t* idx, float* scale);
+void hm_assign_clusters(const float* x, int64_t N, const float* c, int64_t K, int64_t* labels);
+
+/* ---- colour-model row maths (gsr_color.h), one row at a time, each with its derivative ---- */
+/* out [n, (S+1)^2] (NULL: skipped); dd [n, 3] = sum_c dsh[c] dY_c/dd (NULL: skipped).  Returns -1 for S outside 0..5. */
+int hm_cm_rsh(int S, const float* d, int64_t n, float* out, const float* dsh, float* dd);
+/* rows u [n, F]: y = LayerNorm(u) and du for an upstream dy */
+void hm_cm_layernorm(const float* u, int64_t n, int F, const float* dy, float* y, float* du);
+void hm_cm_glu(const float* a, const float* b, const float* dh, int64_t n, float* h, float* da, float* db);
+/* o [n, 4] -> out [n, 3]; do_ [n, 4] for an upstream dout [n, 3] */
+void hm_cm_lum(const float* o, int64_t n, float bias, const float* dout, float* out, float* do_);
+/* v [n, 3] -> d = F.normalize(v) and dv for an upstream dd */
+void hm_cm_normalize(const float* v, const float* dd, int64_t n, float* d, float* dv);
+
+/* ---- frustum point queries and view features (gsr_visibility.h): the device's results bit for bit ---- */
+/* points [N, 3], records [V, 16]; point_counts [N] / camera_counts [V] int32 (either may be NULL). */
+void hm_frustum_counts(const float* p, int64_t N, const float* rec, int64_t V, float depth_below, int32_t* point_counts,
+                       int32_t* camera_counts);
+/* labels [N] int64 in [0, K); idx [M] int64 distinct in [0, N), vis [M]; out [K]; point_visible [N] int32 (may be NULL)
+ * is incremented.  Returns -1 for a label or an index out of range. */
+int hm_view_features(const int64_t* labels, int64_t N, int64_t K, const int64_t* idx, const float* vis, int64_t M,
+                     float threshold, float* out, int32_t* point_visible);
+
+/* ---- sampling rate and 3-D smoothing filter (gsr_filter3d.h) on the host's libm: the device's order of operations ---- */
+/* points [N, 3], records [V, 16], focal [V]; rate [N] */
+void hm_sampling_rate(const float* p, int64_t N, const float* rec, const float* focal, int64_t V, float margin,
+                      float* rate);
+/* ls / out_ls [N, 3], a / rate / out_a [N] */
+void hm_filter3d_forward(const float* ls, const float* a, const float* rate, int64_t N, float strength, float* out_ls,
+                         float* out_a);
+void hm_filter3d_backward(const float* ls, const float* a, const float* rate, int64_t N, float strength, const float* g_ls,
+                          const float* g_a, float* d_ls, float* d_a);
+
+/* ---- SH export fit (gsr_sh_fit.h): the device's updates and its solve, in its order, one point at a time ---- */
+int hm_sh_fit_row_doubles(int K);
+/* pos [N, 3], idx / wts [M], col [M, 3], cam [3]; acc [N, R(K)] is added to */
+void hm_sh_fit_accumulate(const float* pos, int64_t N, const int64_t* idx, int64_t M, const float* col, const float* wts,
+                          const float* cam, int K, double* acc);
+/* acc [N, R(K)]; sh [N, 3, K], weight [N] */
+void hm_sh_fit_solve(const double* acc, int64_t N, int K, float ridge, float* sh, float* weight);
+
+/* ---- MCMC position noise (gsr_controller.h) on the host's libm: the device's order of operations, row by row ---- */
+void hm_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+/* words [N, 4] and normals [N, 3] of rows first .. first + N - 1 (either may be NULL) */
+void hm_mcmc_draws(uint64_t first, int64_t N, uint64_t seed, uint64_t step, uint32_t* words, float* normals);
+/* level [N] of alpha_logit [N] */
+void hm_mcmc_level(const float* alpha_logit, int64_t N, float opacity_threshold, float margin, float noise_level,
+                   float* level);
+/* the row loop of gsr_mcmc_noise, in place on position [N, 3] */
+void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
+                   const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
+                   float noise_level, float scale_eps, uint64_t seed, uint64_t step);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -6,10 +6,9 @@
   R(q / |q|) (max(exp(ls), eps) * (xi level));
 * the float32 RESTATEMENT of the kernel's formula, operation by operation in numpy float32 (a fused multiply-add as the
   float32 rounding of the fp64 product and sum);
-* the ctypes wrappers of the host shim;
+* the wrappers of the host shim;
 * a scene of plain tensors that records its ``split_and_prune`` calls, a logger that records, random statistics.
 """
-import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
@@ -187,33 +186,23 @@ def row_error(got, want, s_row):
 
 # ---- host shim -----------------------------------------------------------------------------------------------------------
 
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
-
-
 def shim_philox(lib, counter, key):
   counter, key = np.ascontiguousarray(counter, dtype=np.uint32), np.ascontiguousarray(key, dtype=np.uint32)
   out = np.empty(4, dtype=np.uint32)
-  lib.hm_philox4x32.restype = None
-  lib.hm_philox4x32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-  lib.hm_philox4x32(_p(counter), _p(key), _p(out))
+  lib.hm_philox4x32(counter, key, out)
   return out
 
 
 def shim_draws(lib, first, n, seed, step):
   w, z = np.empty((n, 4), dtype=np.uint32), np.empty((n, 3), dtype=F)
-  lib.hm_mcmc_draws.restype = None
-  lib.hm_mcmc_draws.argtypes = [C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-  lib.hm_mcmc_draws(int(first), n, int(seed), int(step), _p(w), _p(z))
+  lib.hm_mcmc_draws(int(first), n, int(seed), int(step), w, z)
   return w, z
 
 
 def shim_level(lib, a, noise_level, threshold=THRESHOLD, margin=GATE_MARGIN):
   a = np.ascontiguousarray(a, dtype=F)
   out = np.empty_like(a)
-  lib.hm_mcmc_level.restype = None
-  lib.hm_mcmc_level.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_void_p]
-  lib.hm_mcmc_level(_p(a), a.shape[0], float(threshold), float(margin), float(noise_level), _p(out))
+  lib.hm_mcmc_level(a, a.shape[0], float(threshold), float(margin), float(noise_level), out)
   return out
 
 
@@ -222,9 +211,7 @@ def shim_noise(lib, position, ls, q, a, views, min_views, noise_level, seed, ste
   position = np.array(position, dtype=F, order="C")
   ls, q, a = (np.ascontiguousarray(t, dtype=F) for t in (ls, q, a))
   views = np.ascontiguousarray(views, dtype=np.int16)
-  lib.hm_mcmc_noise.restype = None
-  lib.hm_mcmc_noise.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32] + [C.c_float] * 4 + [C.c_uint64, C.c_uint64]
-  lib.hm_mcmc_noise(_p(position), _p(ls), _p(q), _p(a), _p(views), a.shape[0], int(min_views), float(threshold),
+  lib.hm_mcmc_noise(position, ls, q, a, views, a.shape[0], int(min_views), float(threshold),
                     float(margin), float(noise_level), float(eps), int(seed), int(step))
   return position
 

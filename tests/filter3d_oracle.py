@@ -7,9 +7,8 @@ there is no golden file from it: the oracle is this build's own, as for the rast
   float32, and the naive float32 form ``logit(sigmoid(a) coef)`` that must not be used;
 * the fp64 lower / upper bounds of the sampling rate: the maximum of f / d over the cameras that pass every inequality
   of the sampling test with slack above E (L) and above -E (U), E twice the modelled float32 rounding of both sides;
-* the scenes the checks use and the ctypes wrappers of the host shim.
+* the scenes the checks use and the wrappers of the host shim.
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -268,33 +267,22 @@ def focal_of(intr):
 
 # ---- host shim -----------------------------------------------------------------------------------------------------------
 
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
-
-
 def shim_sampling_rate(lib, points, records, focal, margin):
   points, records, focal = (np.ascontiguousarray(t, dtype=F) for t in (points, records, focal))
   rate = np.empty(points.shape[0], dtype=F)
-  lib.hm_sampling_rate.restype = None
-  lib.hm_sampling_rate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
-  lib.hm_sampling_rate(_p(points), points.shape[0], _p(records), _p(focal), records.shape[0], float(margin), _p(rate))
+  lib.hm_sampling_rate(points, points.shape[0], records, focal, records.shape[0], float(margin), rate)
   return rate
 
 
 def shim_forward(lib, ls, a, rate, strength=STRENGTH):
   ls, a, rate = (np.ascontiguousarray(t, dtype=F) for t in (ls, a, rate))
   out_ls, out_a = np.empty_like(ls), np.empty_like(a)
-  lib.hm_filter3d_forward.restype = None
-  lib.hm_filter3d_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-  lib.hm_filter3d_forward(_p(ls), _p(a), _p(rate), a.shape[0], float(strength), _p(out_ls), _p(out_a))
+  lib.hm_filter3d_forward(ls, a, rate, a.shape[0], float(strength), out_ls, out_a)
   return out_ls, out_a
 
 
 def shim_backward(lib, ls, a, rate, g_ls, g_a, strength=STRENGTH):
   ls, a, rate, g_ls, g_a = (np.ascontiguousarray(t, dtype=F) for t in (ls, a, rate, g_ls, g_a))
   d_ls, d_a = np.empty_like(ls), np.empty_like(a)
-  lib.hm_filter3d_backward.restype = None
-  lib.hm_filter3d_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]
-  lib.hm_filter3d_backward(_p(ls), _p(a), _p(rate), a.shape[0], float(strength), _p(g_ls), _p(g_a), _p(d_ls), _p(d_a))
+  lib.hm_filter3d_backward(ls, a, rate, a.shape[0], float(strength), g_ls, g_a, d_ls, d_a)
   return d_ls, d_a

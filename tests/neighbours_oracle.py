@@ -2,14 +2,8 @@
 the kernels), an fp64 numpy brute force, and torch restatements of the reference's pykeops formulations
 (gaussians/loading.py estimate_scale, visibility/cluster.py kmeans_iter), chunked so that no N x N or N x K matrix of
 the whole problem is held at once."""
-import ctypes as C
-
 import numpy as np
 import torch
-
-
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
 
 
 def shim_knn(lib, points: np.ndarray, k: int, rows=None):
@@ -20,7 +14,7 @@ def shim_knn(lib, points: np.ndarray, k: int, rows=None):
   d = np.zeros((i1 - i0, k), np.float32)
   j = np.zeros((i1 - i0, k), np.int64)
   s = np.zeros(i1 - i0, np.float32)
-  assert lib.hm_knn(_p(p), C.c_int64(N), k, C.c_int64(i0), C.c_int64(i1), _p(d), _p(j), _p(s)) == 0
+  assert lib.hm_knn(p, N, k, i0, i1, d, j, s) == 0
   return d, j, s
 
 
@@ -28,7 +22,7 @@ def shim_assign(lib, x: np.ndarray, c: np.ndarray):
   x = np.ascontiguousarray(x, np.float32)
   c = np.ascontiguousarray(c, np.float32)
   labels = np.zeros(x.shape[0], np.int64)
-  lib.hm_assign_clusters(_p(x), C.c_int64(x.shape[0]), _p(c), C.c_int64(c.shape[0]), _p(labels))
+  lib.hm_assign_clusters(x, x.shape[0], c, c.shape[0], labels)
   return labels
 
 

@@ -6,7 +6,7 @@ there is no golden file from it: the oracle is this build's own, as for the 3-D 
   W = sum w per point, ``np.linalg.solve`` of (G + ridge W Y0^2 diag(0, 1, ..., 1)) s_c = b_c, and the objective J_p;
 * the RESTATEMENT: the same algorithm with the direction and the basis in float32, operation by operation as
   csrc/gsr_sh_fit.h has them, everything after them fp64, the result rounded to float32;
-* the scenes the checks use and the ctypes wrappers of the host shim.
+* the scenes the checks use and the wrappers of the host shim.
 
 How two solutions are compared.  With many views (V = 64) the coefficients are well conditioned and are compared
 directly.  With few views they are ill conditioned by construction and the objective is compared instead: s* being
@@ -16,7 +16,6 @@ for a point seen by one view (the unpenalised constant term fits one colour exac
 define J_p are float32 numbers, so its data term J_p(0) = sum w (y - 0.5)^2 is not given more finely than one part in
 2^24.
 """
-import ctypes as C
 import math
 from typing import NamedTuple
 
@@ -246,10 +245,6 @@ def ridge_experiment(ridges=(1e-3, 1e-2, 1e-1), view_counts=(4, 8, 16, 32), N=51
 
 # ---- the host shim --------------------------------------------------------------------------------------------------------------
 
-def _p(a, t):
-  return a.ctypes.data_as(C.POINTER(t))
-
-
 def row_doubles(K):
   return K * (K + 1) // 2 + 3 * K + 1
 
@@ -258,20 +253,15 @@ def shim_fit(shim, scene: Scene, K, ridge):
   """(sh (N, 3, K) float32, weight (N,) float32, acc (N, R) fp64) through hm_sh_fit_accumulate / hm_sh_fit_solve."""
   N = len(scene.positions)
   acc = np.zeros((N, row_doubles(K)))
-  shim.hm_sh_fit_accumulate.restype = None
-  shim.hm_sh_fit_solve.restype = None
   pos = np.ascontiguousarray(scene.positions, dtype=F)
   for camera, (idx, colours, weights) in zip(scene.cameras, scene.views):
     if len(idx) == 0:
       continue
     cam = np.ascontiguousarray(camera, dtype=F)
-    shim.hm_sh_fit_accumulate(_p(pos, C.c_float), C.c_int64(N), _p(np.ascontiguousarray(idx), C.c_int64),
-                              C.c_int64(len(idx)), _p(np.ascontiguousarray(colours), C.c_float),
-                              _p(np.ascontiguousarray(weights), C.c_float), _p(cam, C.c_float), C.c_int(K),
-                              _p(acc, C.c_double))
+    shim.hm_sh_fit_accumulate(pos, N, np.ascontiguousarray(idx), len(idx), np.ascontiguousarray(colours),
+                              np.ascontiguousarray(weights), cam, K, acc)
   sh, weight = np.empty((N, 3, K), dtype=F), np.empty(N, dtype=F)
-  shim.hm_sh_fit_solve(_p(acc, C.c_double), C.c_int64(N), C.c_int(K), C.c_float(ridge), _p(sh, C.c_float),
-                       _p(weight, C.c_float))
+  shim.hm_sh_fit_solve(acc, N, K, ridge, sh, weight)
   return sh, weight, acc
 
 

@@ -1,12 +1,11 @@
 """CPU checks of the per-pixel bilateral-grid maths (csrc/gsr_bilagrid.h, the source the HIP kernels compile) through
 the host shim: the slice forward, dL/drgb and dL/dgrid against fp64 F.grid_sample and autograd, including the guidance
 border (luma at or beyond 0 and 1, where the guidance gradient is 0 as in torch)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import hostmath
 from bilagrid_recovery import oracle_slice, random_grids
 
 TOL = 1e-5          # relative to the largest magnitude of the reference tensor
@@ -14,10 +13,6 @@ TOL = 1e-5          # relative to the largest magnitude of the reference tensor
 
 def _np(t):
   return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
-
-
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
 
 
 def _rel(got, want):
@@ -32,8 +27,8 @@ def _run(lib, grid, rgb, go):
   out = np.zeros((H, W, 3), np.float32)
   d_rgb = np.zeros((H, W, 3), np.float32)
   d_grid = np.zeros(grid.shape, np.float32)
-  lib.hm_bilagrid_forward(_p(g32), L, GH, GW, _p(x32), H, W, _p(out))
-  lib.hm_bilagrid_backward(_p(g32), L, GH, GW, _p(x32), H, W, _p(go32), _p(d_rgb), _p(d_grid))
+  lib.hm_bilagrid_forward(g32, L, GH, GW, x32, H, W, out)
+  lib.hm_bilagrid_backward(g32, L, GH, GW, x32, H, W, go32, d_rgb, d_grid)
   return out, d_rgb, d_grid
 
 
@@ -48,7 +43,7 @@ def _oracle(grid, rgb, go):
 @pytest.mark.parametrize("shape,H,W,seed", [((16, 16, 8), 48, 64, 0), ((8, 12, 4), 37, 29, 1), ((2, 2, 2), 7, 5, 2),
                                             ((32, 32, 16), 40, 50, 3), ((5, 3, 6), 1, 1, 4)])
 def test_slice_matches_grid_sample(built_libs, shape, H, W, seed):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   grid = random_grids(1, shape, scale=0.3, seed=seed)[0]
   gen = torch.Generator().manual_seed(100 + seed)
   rgb = 1.4 * torch.rand(H, W, 3, generator=gen) - 0.2          # luma below 0 and above 1 included
@@ -80,7 +75,7 @@ def _affine_only_grad(grid, rgb, go):
 def test_guidance_gradient_is_zero_on_and_beyond_the_border(built_libs):
   """Pixels with luma exactly 0, below 0, above 1 and exactly 1 get no guidance term (dL/drgb = A^T go), as grid_sample
   gives; just inside the border the term is there."""
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   grid = random_grids(1, (4, 4, 4), scale=0.5, seed=9)[0]
   vals = [[0.0, 0.0, 0.0], [-0.3, -0.1, -0.2], [1.2, 1.5, 1.1], [1.0, 1.0, 1.0], [0.01, 0.02, 0.01], [0.98, 0.99, 0.97]]
   rgb = torch.tensor(vals, dtype=torch.float32).view(1, 6, 3)
@@ -97,7 +92,7 @@ def test_guidance_gradient_is_zero_on_and_beyond_the_border(built_libs):
 
 
 def test_identity_grid_reproduces_the_image_bit_for_bit(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   from bilagrid_recovery import identity
   grid = identity(1, (16, 16, 8))[0]
   gen = torch.Generator().manual_seed(5)

@@ -2,7 +2,6 @@
 from the reference's own modules, ColorModel's state_dict matches the reference's keys and shapes, the shared row maths
 (csrc/gsr_color.h through the host shim) match the oracle, and unsupported configurations raise the documented
 ValueError."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -11,14 +10,11 @@ import torch
 import torch.nn.functional as F
 
 import color_model_oracle as cmo
+import hostmath
 from splat_trainer_amd.color_model import SUPPORTED, ColorModel, ColorModelConfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "color_model_ref.npz"))
-
-
-def _f32p(a):
-  return a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.mark.parametrize("c", [0, 1])
@@ -58,20 +54,20 @@ def test_shipped_config_parameter_count():
 
 
 def test_shim_sh_basis_matches_golden(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   d = np.ascontiguousarray(GOLDEN["dirs"], dtype=np.float32)
   out = np.zeros((len(d), 36), np.float32)
-  assert lib.hm_cm_rsh(5, _f32p(d), C.c_int64(len(d)), _f32p(out), None, None) == 0
+  assert lib.hm_cm_rsh(5, d, len(d), out, None, None) == 0
   ref = GOLDEN["rsh_cart_5"]
   assert np.abs(out - ref).max() < 4e-6 * np.abs(ref).max()
   for S in range(6):          # lower degrees are the leading columns
     o = np.zeros((len(d), (S + 1) ** 2), np.float32)
-    lib.hm_cm_rsh(S, _f32p(d), C.c_int64(len(d)), _f32p(o), None, None)
+    lib.hm_cm_rsh(S, d, len(d), o, None, None)
     assert np.abs(o - ref[:, :(S + 1) ** 2]).max() < 4e-6 * np.abs(ref).max()
 
 
 def test_shim_row_maths_match_oracle(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   rng = np.random.default_rng(0)
   n = 200
   # SH vector-Jacobian product (also at d = 0, a point at the camera)
@@ -81,7 +77,7 @@ def test_shim_row_maths_match_oracle(built_libs):
     d[0] = 0
     dsh = rng.standard_normal((n, K)).astype(np.float32)
     dd = np.zeros((n, 3), np.float32)
-    lib.hm_cm_rsh(S, _f32p(d), C.c_int64(n), None, _f32p(dsh), _f32p(dd))
+    lib.hm_cm_rsh(S, d, n, None, dsh, dd)
     dt = torch.tensor(d, dtype=torch.float64, requires_grad=True)
     (cmo.rsh(dt, S) * torch.tensor(dsh, dtype=torch.float64)).sum().backward()
     assert np.abs(dd - dt.grad.numpy()).max() < 1e-5 * np.abs(dt.grad.numpy()).max()
@@ -90,7 +86,7 @@ def test_shim_row_maths_match_oracle(built_libs):
   u = rng.standard_normal((n, F_)).astype(np.float32)
   dy = rng.standard_normal((n, F_)).astype(np.float32)
   y, du = np.zeros_like(u), np.zeros_like(u)
-  lib.hm_cm_layernorm(_f32p(u), C.c_int64(n), C.c_int(F_), _f32p(dy), _f32p(y), _f32p(du))
+  lib.hm_cm_layernorm(u, n, F_, dy, y, du)
   ut = torch.tensor(u, dtype=torch.float64, requires_grad=True)
   yt = F.layer_norm(ut, (F_,), eps=1e-5)
   (yt * torch.tensor(dy, dtype=torch.float64)).sum().backward()
@@ -98,7 +94,7 @@ def test_shim_row_maths_match_oracle(built_libs):
   # GLU
   a, b, dh = (rng.standard_normal(n).astype(np.float32) * 3 for _ in range(3))
   h, da, db = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
-  lib.hm_cm_glu(_f32p(a), _f32p(b), _f32p(dh), C.c_int64(n), _f32p(h), _f32p(da), _f32p(db))
+  lib.hm_cm_glu(a, b, dh, n, h, da, db)
   at, bt = (torch.tensor(v, dtype=torch.float64, requires_grad=True) for v in (a, b))
   ht = F.glu(torch.cat([at[:, None], bt[:, None]], 1), dim=1)[:, 0]
   (ht * torch.tensor(dh, dtype=torch.float64)).sum().backward()
@@ -109,7 +105,7 @@ def test_shim_row_maths_match_oracle(built_libs):
     o = rng.standard_normal((n, 4)).astype(np.float32)
     dout = rng.standard_normal((n, 3)).astype(np.float32)
     out, do = np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32)
-    lib.hm_cm_lum(_f32p(o), C.c_int64(n), C.c_float(bias), _f32p(dout), _f32p(out), _f32p(do))
+    lib.hm_cm_lum(o, n, bias, dout, out, do)
     ot = torch.tensor(o, dtype=torch.float64, requires_grad=True)
     lt = cmo.lum(ot, bias)
     (lt * torch.tensor(dout, dtype=torch.float64)).sum().backward()
@@ -120,7 +116,7 @@ def test_shim_row_maths_match_oracle(built_libs):
   v[0] = 0
   ddv = rng.standard_normal((n, 3)).astype(np.float32)
   dn, dv = np.zeros_like(v), np.zeros_like(v)
-  lib.hm_cm_normalize(_f32p(v), _f32p(ddv), C.c_int64(n), _f32p(dn), _f32p(dv))
+  lib.hm_cm_normalize(v, ddv, n, dn, dv)
   vt = torch.tensor(v, dtype=torch.float64, requires_grad=True)
   nt = F.normalize(vt, dim=1)
   (nt * torch.tensor(ddv, dtype=torch.float64)).sum().backward()

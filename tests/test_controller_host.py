@@ -15,6 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import controller_oracle as co  # noqa: E402
+import hostmath  # noqa: E402
 from controller_oracle import FakeLogger, FakeScene, fill_state as _fill  # noqa: E402
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib, controller as ctl  # noqa: E402
@@ -29,7 +30,7 @@ def _note(line: str):
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  return C.CDLL(built_libs[1])
+  return hostmath.load(built_libs)
 
 
 # ------------------------------------------------------------------------------------------------------------ generator

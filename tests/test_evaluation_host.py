@@ -2,7 +2,6 @@
 (tests/golden/color_fit_ref.npz), the shared maths of csrc/gsr_eval.h through the host shim -- the moments, the
 rank-revealing solve on full-rank and rank-deficient systems, the whole fit in the device's order of operations -- and
 the argument checks of the Python layer."""
-import ctypes as C
 import dataclasses
 import math
 import os
@@ -12,6 +11,7 @@ import pytest
 import torch
 
 import color_fit_oracle as cfo
+import hostmath
 from helpers import PARITY_LOG
 
 EPS = 0.5 / 255
@@ -24,30 +24,20 @@ def fixtures(golden_dir):
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  lib = C.CDLL(built_libs[1])
-  lib.hm_color_fit_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]
-  lib.hm_color_fit_solve.argtypes = [C.c_void_p, C.c_void_p]
-  lib.hm_color_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p]
-  for fn in (lib.hm_color_fit_moments, lib.hm_color_fit_solve, lib.hm_color_fit):
-    fn.restype = None
-  return lib
-
-
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
+  return hostmath.load(built_libs)
 
 
 def _host_fit(shim, img, ref, num_iters=5):
   x, r = np.ascontiguousarray(img, np.float32), np.ascontiguousarray(ref, np.float32)
   out = np.zeros_like(x)
-  shim.hm_color_fit(_p(x), _p(r), x.size // 3, num_iters, EPS, _p(out))
+  shim.hm_color_fit(x, r, x.size // 3, num_iters, EPS, out)
   return out
 
 
 def _host_solve(shim, sums):
   sums = np.ascontiguousarray(sums, np.float64)
   w = np.zeros(10)
-  shim.hm_color_fit_solve(_p(sums), _p(w))
+  shim.hm_color_fit_solve(sums, w)
   return w
 
 
@@ -80,7 +70,7 @@ def test_host_moments_match_the_oracle(shim, fixtures):
   ref = np.ascontiguousarray(f["ref"].reshape(-1, 3))
   x = np.ascontiguousarray(cfo.fit(f["img"], f["ref"], num_iters=2)[0].reshape(-1, 3).astype(np.float32))
   got = np.zeros((3, 45))
-  shim.hm_color_fit_moments(_p(x0), _p(x), _p(ref), x0.shape[0], EPS, _p(got))
+  shim.hm_color_fit_moments(x0, x, ref, x0.shape[0], EPS, got)
   want = cfo.moments(x0, x, ref, EPS)
   assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
   S, t = cfo.system_from_sums(got[0])

@@ -14,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import filter3d_oracle as fo  # noqa: E402
+import hostmath  # noqa: E402
 import visibility_oracle as vo  # noqa: E402
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib, visibility as vis  # noqa: E402
@@ -28,7 +29,7 @@ def _note(line: str):
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  return C.CDLL(built_libs[1])
+  return hostmath.load(built_libs)
 
 
 @pytest.fixture(scope="module")

@@ -1,12 +1,11 @@
 """The neighbour searches on the MI355X (splat_trainer_amd.neighbours): kNN and assignment bit-identical to the host shim
 (the same header), estimate_scale and k-means against torch restatements of the reference's pykeops formulations,
 determinism, the in-place contract of kmeans_iter, empty clusters, the reference's initial rows and every ValueError."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import hostmath
 import splat_trainer_amd as sta
 from neighbours_oracle import (assign_torch, blobs, estimate_scale_torch, kmeans_iter_torch, shim_assign, shim_knn)
 
@@ -26,7 +25,7 @@ def _rows(n):
 @pytest.mark.parametrize("k", [1, 5, 16])
 @pytest.mark.parametrize("n", ["k+1", 1000, 65537])
 def test_knn_bit_identical_to_host(built_libs, n, k):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   n = k + 1 if n == "k+1" else n
   p = _cloud(n, 10 + k)
   d, j = sta.knn(p, k)
@@ -42,7 +41,7 @@ def test_knn_bit_identical_to_host(built_libs, n, k):
 
 
 def test_knn_duplicates_and_lattice_ties(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   g = torch.stack(torch.meshgrid(torch.arange(20), torch.arange(12), torch.arange(9), indexing="ij"), -1).reshape(-1, 3)
   p = g[torch.randperm(len(g), generator=torch.Generator().manual_seed(0))].float()
   p = torch.cat([p, p[:100]])                                  # duplicates: distance 0
@@ -54,7 +53,7 @@ def test_knn_duplicates_and_lattice_ties(built_libs):
 
 
 def test_assign_bit_identical_to_host(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   for n, K, seed in [(1, 1, 0), (1000, 7, 1), (65537, 256, 2), (200_000, 100, 3)]:
     x, c = _cloud(n, seed), _cloud(K, 100 + seed)
     labels = sta.assign_clusters(x, c)

@@ -2,13 +2,13 @@
 (the same header), deterministic and independent of the list order; the whole chain renderer -> PointClusters ->
 ViewClustering -> sample_batch on a synthetic scene against the oracle; balanced_points / crop_cloud / foreground_points
 against the fp64 test and the reference's torch lines; every ValueError."""
-import ctypes as C
 import dataclasses
 
 import numpy as np
 import pytest
 import torch
 
+import hostmath
 import splat_trainer_amd as sta
 from splat_trainer_amd import synthetic
 from splat_trainer_amd import visibility as vis
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  return C.CDLL(built_libs[1])
+  return hostmath.load(built_libs)
 
 
 def _np(t):

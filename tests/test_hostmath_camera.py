@@ -1,12 +1,11 @@
 """CPU checks of the camera terms of the K2 backward (csrc/gsr_math.h: gsr_project_one_bwd<true>, gsr_fold_camera_position)
 through the host build of the shared maths header: dL/dT_camera_world and dL/dprojection against fp64 autograd of the
 oracle, which uses plain torch ops on both."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import hostmath
 from helpers import oracle, small_scene
 from splat_trainer_amd import RasterConfig
 from splat_trainer_amd._lib import raster_params
@@ -18,10 +17,6 @@ def _np(t):
   return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
 
 
-def _p(a):
-  return a.ctypes.data_as(C.c_void_p)
-
-
 def _rel(got, want):
   want = np.asarray(want, np.float64)
   return np.abs(np.asarray(got, np.float64) - want).max() / np.abs(want).max()
@@ -29,7 +24,7 @@ def _rel(got, want):
 
 @pytest.mark.parametrize("antialias", [False, True])
 def test_camera_terms_match_autograd(built_libs, antialias):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   g, cam = small_scene(2000, 96, 64, seed=23, sigma_px=3.0)
   cfg = RasterConfig(antialias=antialias, blur_cov=0.0 if antialias else 0.3)
   M = g.position.shape[0]
@@ -44,9 +39,9 @@ def test_camera_terms_match_autograd(built_libs, antialias):
 
   per_splat = np.zeros((M, 16), np.float32)
   rp = raster_params(cfg)
-  lib.hm_project_backward_camera(_p(_np(cam.T_camera_world)), _p(_np(cam.projection)), C.byref(rp), C.c_int64(M),
-                                 _p(_np(g.position)), _p(_np(g.log_scaling)), _p(_np(g.rotation)),
-                                 _p(_np(g.alpha_logit)), _p(_np(dg)), _p(_np(dd[:, 0])), _p(per_splat))
+  lib.hm_project_backward_camera(_np(cam.T_camera_world), _np(cam.projection), rp, M, _np(g.position),
+                                 _np(g.log_scaling), _np(g.rotation), _np(g.alpha_logit), _np(dg), _np(dd[:, 0]),
+                                 per_splat)
   total = per_splat.astype(np.float64).sum(0)
   dT, dproj = T.grad.numpy(), proj.grad.numpy()
   assert np.all(dT[3] == 0)
@@ -58,7 +53,7 @@ def test_camera_terms_match_autograd(built_libs, antialias):
 def test_camera_position_fold_matches_autograd(built_libs, K):
   """The view-direction term: dL/dcam from autograd of evaluate_sh_at, folded through cam = -R^T t by the shim, equals
   autograd straight through T."""
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   g, cam = small_scene(500, 96, 64, sh_degree=int(round(K ** 0.5)) - 1, seed=24)
   assert g.feature.shape[2] == K
   M = g.position.shape[0]
@@ -74,5 +69,5 @@ def test_camera_position_fold_matches_autograd(built_libs, K):
   (oracle.evaluate_sh_at(sh, pos, torch.arange(M), leaf) * dcol).sum().backward()
 
   dT = np.zeros(12, np.float32)
-  lib.hm_fold_camera_position(_p(_np(cam.T_camera_world)), _p(_np(leaf.grad)), _p(dT))
+  lib.hm_fold_camera_position(_np(cam.T_camera_world), _np(leaf.grad), dT)
   assert _rel(dT.reshape(3, 4), T.grad.numpy()[:3]) < TOL, (K, dT, T.grad)

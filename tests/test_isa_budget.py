@@ -1,21 +1,11 @@
 """Static budget of the hot kernels' gfx950 code (hipcc cross-compiles without a GPU): a toolchain or source change must
 not silently spill K6 / K7 to scratch, push them over the register budget their occupancy rests on, or introduce
 barriers / matrix instructions the design excludes."""
-import importlib.util
-import os
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _audit():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  return mod.audit()
+from isa import audit
 
 
 def test_composite_kernels_stay_inside_their_register_budget():
-  a = _audit()
+  a = audit()
   # no kernel of composite.hip may use scratch memory (a spill in the per-pair loop costs more than the occupancy it buys)
   spilled = {n: k["scratch_bytes"] for n, k in a["all_kernels"].items() if k["scratch_bytes"]}
   assert not spilled, spilled

@@ -1,25 +1,16 @@
 """Static budget of the bilateral-grid kernels (csrc/bilagrid.hip) on gfx950 -- hipcc cross-compiles without a GPU: every
 kernel is there with no scratch and at most 128 VGPRs, and the code holds no float atomic (the grid gradient and the
 TV sum are fixed-order reductions)."""
-import importlib.util
-import os
-import re
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import FLOAT_ATOMIC, compiled
+
 KERNELS = ("bg_slice_fwd_kernel", "bg_slice_bwd_kernel", "bg_grad_finish_kernel", "bg_tv_kernel", "bg_tv_finish_kernel")
-FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*)\b",
-                          re.M)
 
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("bilagrid.hip")
-  return asm, mod.kernels(asm)
+  return compiled("bilagrid.hip")
 
 
 def test_every_bilagrid_kernel_is_there_inside_its_budget(isa):

@@ -2,12 +2,9 @@
 camera kernel is there with no scratch and at most 128 VGPRs, and the parameter-backward kernels keep the register counts
 they had before the camera gradient existed (the camera terms are formed by kernels of their own, so that the parameter
 gradients keep their bits)."""
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import compiled
 
 DEFAULT_VGPR = {"project_bwd_rows_kernelILi0E": 114, "project_bwd_rows_kernelILi1E": 102,
                 "project_bwd_rows_kernelILi2E": 102, "project_bwd_kernelILb0E": 94, "project_bwd_kernelILb1E": 96}
@@ -17,10 +14,7 @@ CAMERA_KERNELS = ("project_bwd_camera_kernel", "project_bwd_rows_camera_kernel",
 
 @pytest.fixture(scope="module")
 def geometry_kernels():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  return mod.kernels(mod.compile_isa("geometry.hip"))
+  return compiled("geometry.hip")[1]
 
 
 def _one(meta, needle):

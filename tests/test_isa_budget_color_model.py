@@ -3,26 +3,19 @@ every instantiation (L in {1, 2} x F blocks in {1, 2} x SH degree 2..5) is there
 budget (arch + accumulation registers: the backward keeps the workgroup's weight-gradient tiles and the recomputed
 forward in registers at one wave per SIMD), the forward and backward run their Linears on f16 MFMA, and the code holds
 no float atomic (the gradient slots are summed in a fixed order)."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import FLOAT_ATOMIC, compiled
+
 KERNELS = {"cm_pack_kernel": (1, 64), "cm_forward_kernel": (16, 160), "cm_backward_kernel": (16, 512),
            "cm_finish_kernel": (16, 32)}
-FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*)\b",
-                          re.M)
 
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("color_model.hip")
-  return asm, mod.kernels(asm)
+  return compiled("color_model.hip")
 
 
 def _names(meta, needle):

@@ -2,20 +2,14 @@
 the forward walk's four-pair loop holds no wait on the vector-memory counter -- the per-pair visibility is parked in LDS
 and handed over once per 64 list positions, outside that loop -- and the backward kernel's entry state arrives with one
 wait, next to the one of the launch-order lookup."""
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import audit
 
 
 @pytest.fixture(scope="module")
 def waits():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  return mod.audit()["composite_waits"]
+  return audit()["composite_waits"]
 
 
 @pytest.mark.parametrize("kernel,copies", [("K6_fwd_C3_vis", 2), ("K6_segC_C3_vis", 1)])

@@ -1,22 +1,18 @@
 """Static budget of the MCMC noise kernels (csrc/controller.hip) on gfx950 -- hipcc cross-compiles without a GPU: the two
 kernels are there, with no scratch, no LDS and no more registers than the build they were measured in
 (profiles/r20_controllers.txt)."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import compiled
+
 VGPRS = {"mcmc_noise_kernel": 70, "mcmc_draws_kernel": 42}     # as built
 
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  return mod.kernels(mod.compile_isa("controller.hip"))
+  return compiled("controller.hip")[1]
 
 
 def test_both_kernels_are_there_inside_their_budget(isa):

@@ -2,13 +2,12 @@
 is there once with no scratch (the pass kernel carries 45 fp64 accumulators per thread, one channel per blockIdx.y, so
 that they stay in registers; the solve works in LDS), and the code holds no float atomic: the sums are fixed-order
 reductions."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import compiled
+
 # registers the compiler gives today, pinned with a little slack so that a change that spills or doubles them is noticed
 KERNELS = {"color_fit_pass_kernel": (184, 208), "color_fit_finish_kernel": (104, 128)}
 FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*|"
@@ -17,11 +16,7 @@ FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("eval.hip")
-  return asm, mod.kernels(asm)
+  return compiled("eval.hip")
 
 
 def test_every_eval_kernel_is_there_inside_its_budget(isa):

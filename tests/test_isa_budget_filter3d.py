@@ -2,25 +2,18 @@
 GPU: the three kernels are there, with no scratch, no LDS and no more registers than the build they were measured in
 (profiles/r17_filter3d.txt), the code holds no float atomic, and the rate kernel's cameras come through the scalar
 cache."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import FLOAT_ATOMIC, compiled, ops as ops_of
+
 VGPRS = {"sampling_rate_kernel": 107, "filter3d_forward_kernel": 59, "filter3d_backward_kernel": 77}     # as built
-FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*)\b",
-                          re.M)
 
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("filter3d.hip")
-  return asm, mod.kernels(asm)
+  return compiled("filter3d.hip")
 
 
 def test_every_filter_kernel_is_there_inside_its_budget(isa):
@@ -42,7 +35,7 @@ def test_no_float_atomics(isa):
 def test_cameras_come_through_the_scalar_cache(isa):
   _, meta = isa
   body = meta[next(n for n in meta if "sampling_rate_kernel" in n)]["body"]
-  ops = [ln.split()[0] for ln in body if ln.strip() and not ln.strip().startswith((";", "."))]
+  ops = ops_of(body)
   assert sum(op.startswith("s_load_dwordx") for op in ops) >= 4
   assert sum(op.startswith("global_load") for op in ops) <= 12       # the lane's own points, nothing per camera
 
@@ -51,6 +44,6 @@ def test_filter_rows_travel_as_float4(isa):
   _, meta = isa
   for needle, loads, stores in (("filter3d_forward_kernel", 5, 4), ("filter3d_backward_kernel", 9, 4)):
     body = meta[next(n for n in meta if needle in n)]["body"]
-    ops = [ln.split()[0] for ln in body if ln.strip() and not ln.strip().startswith((";", "."))]
+    ops = ops_of(body)
     assert sum(op == "global_load_dwordx4" for op in ops) >= loads, needle
     assert sum(op == "global_store_dwordx4" for op in ops) >= stores, needle

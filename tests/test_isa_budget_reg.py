@@ -1,16 +1,11 @@
 """Static budget of the regulariser and post-step kernels (csrc/reg.hip) on gfx950 -- hipcc cross-compiles without a
 GPU: every kernel is there once with no scratch and at most 128 VGPRs, and the code holds no float atomic (the sums are
 fixed-order reductions, the log_scaling gradient a plain read-modify-write on unique rows)."""
-import importlib.util
-import os
-import re
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import FLOAT_ATOMIC, compiled
+
 KERNELS = ("reg_fwd_kernel", "reg_finish_kernel", "reg_bwd_kernel", "scene_post_step_kernel")
-FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*)\b",
-                          re.M)
 # registers the compiler gives today (29 / 24 / 32 / 32): far inside the budget, pinned with a little slack so that a
 # change that doubles them is noticed
 VGPR_SEEN_MAX = 48
@@ -18,11 +13,7 @@ VGPR_SEEN_MAX = 48
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("reg.hip")
-  return asm, mod.kernels(asm)
+  return compiled("reg.hip")
 
 
 def test_every_reg_kernel_is_there_inside_its_budget(isa):

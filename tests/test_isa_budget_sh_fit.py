@@ -2,32 +2,21 @@
 two kernels exist for K = 1, 4, 9, 16 and nothing else, with no scratch and no more registers than the build they were
 measured in (profiles/r18_sh_fit.txt), the code holds no float atomic, the accumulation is fused fp64 multiply-adds and
 its rows travel as 8-byte words."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import FLOAT_ATOMIC, compiled, ops as ops_of
+
 KS = (1, 4, 9, 16)
 VGPRS = {("sh_fit_accumulate_kernel", 1): 13, ("sh_fit_accumulate_kernel", 4): 18, ("sh_fit_accumulate_kernel", 9): 33,
          ("sh_fit_accumulate_kernel", 16): 54, ("sh_fit_solve_kernel", 1): 30, ("sh_fit_solve_kernel", 4): 38,
          ("sh_fit_solve_kernel", 9): 40, ("sh_fit_solve_kernel", 16): 68}                                  # as built
-FLOAT_ATOMIC = re.compile(r"^\s*(\S*atomic_add_f\S*|\S*atomic_pk_add\S*|ds_add_f32|ds_add_rtn_f32|ds_pk_add_\S*)\b",
-                          re.M)
 
 
 @pytest.fixture(scope="module")
 def isa():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  asm = mod.compile_isa("sh_fit.hip")
-  return asm, mod.kernels(asm)
-
-
-def _ops(kernel):
-  return [ln.split()[0] for ln in kernel["body"] if ln.strip() and not ln.strip().startswith((";", "."))]
+  return compiled("sh_fit.hip")
 
 
 def test_every_instantiation_is_there_inside_its_budget(isa):
@@ -38,7 +27,7 @@ def test_every_instantiation_is_there_inside_its_budget(isa):
     k = meta[names[0]]
     print(f"{needle}<{K}>: {k['vgpr']} VGPRs, {k['sgpr']} SGPRs, scratch {k['scratch']} B")
     assert k["scratch"] == 0 and k["vgpr"] <= vgprs, (names[0], k["vgpr"], k["scratch"])
-    assert not any(op.startswith("scratch_") for op in _ops(k)), names[0]
+    assert not any(op.startswith("scratch_") for op in ops_of(k["body"])), names[0]
   assert len(meta) == len(VGPRS), sorted(meta)
 
 
@@ -53,7 +42,7 @@ def test_accumulation_is_fused_fp64_on_8_byte_words(isa):
   _, meta = isa
   for K in KS:
     k = meta[next(n for n in meta if f"sh_fit_accumulate_kernelILi{K}E" in n)]
-    ops = _ops(k)
+    ops = ops_of(k["body"])
     components = K * (K + 1) // 2 + 3 * K + 1
     per_lane = -(-components // 16)
     fused = sum(op.startswith(("v_fma_f64", "v_fmac_f64")) for op in ops)

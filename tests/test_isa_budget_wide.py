@@ -1,13 +1,11 @@
 """Static budget of the wide-feature kernels (K6 / K7 for 4..16 channels, composite_wide.inc compiled into
 composite.hip) on gfx950 -- hipcc cross-compiles without a GPU: no scratch, no barrier, no matrix instructions, and the
 VGPR counts the occupancy of DESIGN.md section 4 rests on."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import compiled
 
 # VGPR ceilings per feature-table width: K6 wide (every VIS / MEDIAN form) and K7 wide
 K6_VGPR = {4: 64, 8: 80, 16: 112}      # 8 / 6 / 4 waves per SIMD
@@ -16,10 +14,7 @@ K7_VGPR = {4: 102, 8: 168, 16: 256}    # 5 / 3 / 2 waves per SIMD
 
 @pytest.fixture(scope="module")
 def wide_kernels():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  meta = mod.kernels(mod.compile_isa("composite.hip"))
+  meta = compiled("composite.hip")[1]
   return {n: k for n, k in meta.items() if "composite_fwd_wide" in n or "composite_bwd_wide" in n}
 
 

@@ -1,13 +1,11 @@
 """Static budget of the segmented wide-frame kernels (composite_wide.inc: wide_ckpt_fwd, wide_seg_fwd, wide_seg_combine)
 on gfx950 -- hipcc cross-compiles without a GPU: no scratch, no barrier, no matrix instructions, and the VGPR counts the
 occupancy of DESIGN.md section 4 rests on."""
-import importlib.util
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from isa import compiled
 
 FWD_VGPR = {4: 64, 8: 80, 16: 112}      # the K6 wide ceilings: 8 / 6 / 4 waves per SIMD
 COMBINE_VGPR = 64                        # 8 waves per SIMD at every width (four channels at a time)
@@ -16,10 +14,7 @@ NEW = ("wide_ckpt_fwd", "wide_seg_fwd", "wide_seg_combine")
 
 @pytest.fixture(scope="module")
 def seg_kernels():
-  spec = importlib.util.spec_from_file_location("isa_stats", os.path.join(ROOT, "tools", "isa_stats.py"))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  meta = mod.kernels(mod.compile_isa("composite.hip"))
+  meta = compiled("composite.hip")[1]
   return {n: k for n, k in meta.items() if any(s in n for s in NEW)}
 
 

@@ -2,11 +2,10 @@
 kNN and nearest-centroid assignment against an fp64 numpy brute force -- distances within fp32 rounding, indices equal
 except between distances that fp32 cannot tell apart, equal distances in index order, duplicates at distance 0, the
 assignment's lowest-index tie-break and the label of an all-NaN point."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import hostmath
 from neighbours_oracle import dist2_fp64, knn_fp64, shim_assign, shim_knn
 
 EPS = 4e-7          # relative: a few fp32 roundings of a squared distance
@@ -19,7 +18,7 @@ def _cloud(n, seed):
 
 @pytest.mark.parametrize("n,k,seed", [(2, 1, 0), (17, 16, 1), (1000, 5, 2), (4096, 3, 3), (777, 16, 4)])
 def test_knn_matches_fp64(built_libs, n, k, seed):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   p = _cloud(n, seed)
   d, j, s = shim_knn(lib, p, k)
   D, J = knn_fp64(p, k)
@@ -38,7 +37,7 @@ def test_knn_matches_fp64(built_libs, n, k, seed):
 
 def test_knn_exact_ties_in_index_order(built_libs):
   """Integer lattice: every distance is exact in fp32, so the lists equal the fp64 (distance, index) order bit for bit."""
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   g = np.stack(np.meshgrid(np.arange(6), np.arange(5), np.arange(4), indexing="ij"), -1).reshape(-1, 3)
   p = g[np.random.default_rng(0).permutation(len(g))].astype(np.float32)
   for k in (1, 6, 16):
@@ -48,7 +47,7 @@ def test_knn_exact_ties_in_index_order(built_libs):
 
 
 def test_knn_duplicates_at_distance_zero(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   p = _cloud(50, 5)
   p = np.concatenate([p, p[:10], p[:3]])                 # 10 points twice, 3 of them three times
   d, j, s = shim_knn(lib, p, 2)
@@ -61,7 +60,7 @@ def test_knn_duplicates_at_distance_zero(built_libs):
 
 
 def test_knn_rows_of_a_range(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   p = _cloud(300, 6)
   d, j, s = shim_knn(lib, p, 4)
   d2, j2, s2 = shim_knn(lib, p, 4, rows=(100, 177))
@@ -69,7 +68,7 @@ def test_knn_rows_of_a_range(built_libs):
 
 
 def test_assign_matches_fp64(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   x, c = _cloud(4096, 7), _cloud(100, 8)
   labels = shim_assign(lib, x, c)
   D = dist2_fp64(x, c)
@@ -81,7 +80,7 @@ def test_assign_matches_fp64(built_libs):
 
 
 def test_assign_ties_go_to_the_lowest_index(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   c = np.array([[1, 0, 0], [0, 1, 0], [-1, 0, 0], [0, 1, 0], [0, 0, 2]], np.float32)
   x = np.array([[0, 0, 0], [0, 2, 0], [0, 0, 1], [5, 5, 5]], np.float32)
   # origin: 0,1,2,3 at 1 -> 0;  (0,2,0): 1 and 3 at 1 -> 1;  (0,0,1): 4 at 1 and 0..3 at 2 -> 4
@@ -90,7 +89,7 @@ def test_assign_ties_go_to_the_lowest_index(built_libs):
 
 
 def test_assign_all_nan_point_gets_label_zero(built_libs):
-  lib = C.CDLL(built_libs[1])
+  lib = hostmath.load(built_libs)
   c = _cloud(9, 9)
   x = np.array([[np.nan, 0, 0], [0, np.nan, np.nan], [1, 2, 3]], np.float32)
   labels = shim_assign(lib, x, c)

@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import hostmath  # noqa: E402
 import sh_fit_oracle as so  # noqa: E402
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib, mlp_scene, sh_fit  # noqa: E402
@@ -31,7 +32,7 @@ def _note(line: str):
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  return C.CDLL(built_libs[1])
+  return hostmath.load(built_libs)
 
 
 # ------------------------------------------------------------------------------------------------- oracle self-checks
@@ -220,7 +221,7 @@ def test_library_exports_the_entry_points(built_libs):
   lib = C.CDLL(built_libs[0])
   for name in ("gsr_sh_fit_row_doubles", "gsr_sh_fit_accumulate", "gsr_sh_fit_solve"):
     assert hasattr(lib, name)
-  lib.gsr_sh_fit_row_doubles.argtypes = [C.c_int32]
+  lib.gsr_sh_fit_row_doubles.restype, lib.gsr_sh_fit_row_doubles.argtypes = _lib.PROTOTYPES["gsr_sh_fit_row_doubles"]
   assert [lib.gsr_sh_fit_row_doubles(K) for K in (1, 4, 9, 16, 2, 25)] == [5, 23, 73, 185, 0, 0]
 
 

@@ -1,12 +1,11 @@
 """CPU checks of the frustum test and the view-feature sums (csrc/gsr_visibility.h, the source the HIP kernels compile)
 through the host shim against fp64 numpy, and of the torch-only parts of splat_trainer_amd.visibility (normalisation,
 overlaps, the sampling functions, the two samplers, every state_dict) on CPU tensors against the reference's lines."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import hostmath
 from splat_trainer_amd import visibility as vis
 from visibility_oracle import (camera_batch, frustum_fp64, normalized_visibility_ref, overlaps_ref, ring_cameras,
                                ring_points, sample_batch_grouped_ref, sample_batch_ref, sample_with_temperature_ref,
@@ -14,7 +13,7 @@ from visibility_oracle import (camera_batch, frustum_fp64, normalized_visibility
 
 @pytest.fixture(scope="module")
 def shim(built_libs):
-  return C.CDLL(built_libs[1])
+  return hostmath.load(built_libs)
 
 
 # ---- 1. the issue's scene ----------------------------------------------------------------------------------------------

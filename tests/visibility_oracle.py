@@ -1,9 +1,8 @@
 """Oracles for splat_trainer_amd.visibility.  The reference's visibility/ modules import pykeops, taichi_splatting and
 tensordict, so nothing of them is imported: the frustum test and the view-feature sums are restated in fp64 numpy, and the
 few torch lines of the reference that the sampling and query functions consist of are restated with their file and line
-(splat_trainer/visibility/cluster.py, visibility/query_points.py).  Also the ctypes wrappers of the host shim and the ring
+(splat_trainer/visibility/cluster.py, visibility/query_points.py).  Also the wrappers of the host shim and the ring
 scene the checks use."""
-import ctypes as C
 
 import numpy as np
 import torch
@@ -91,18 +90,12 @@ def view_features_fp64(labels, K, idx, vis, threshold=0.01):
 
 # ---- host shim -------------------------------------------------------------------------------------------------------
 
-def _p(a):
-  return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def shim_frustum(lib, points, records, depth_below=np.inf, want_points=True, want_cameras=True):
   points = np.ascontiguousarray(points, dtype=np.float32)
   records = np.ascontiguousarray(records, dtype=np.float32)
   pc = np.empty(points.shape[0], dtype=np.int32) if want_points else None
   cc = np.empty(records.shape[0], dtype=np.int32) if want_cameras else None
-  lib.hm_frustum_counts.restype = None
-  lib.hm_frustum_counts.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-  lib.hm_frustum_counts(_p(points), points.shape[0], _p(records), records.shape[0], float(depth_below), _p(pc), _p(cc))
+  lib.hm_frustum_counts(points, points.shape[0], records, records.shape[0], float(depth_below), pc, cc)
   return pc, cc
 
 
@@ -111,11 +104,7 @@ def shim_view_features(lib, labels, K, idx, vis, threshold=0.01, point_visible=N
   idx = np.ascontiguousarray(idx, dtype=np.int64)
   vis = np.ascontiguousarray(vis, dtype=np.float32)
   out = np.empty(K, dtype=np.float32)
-  lib.hm_view_features.restype = C.c_int
-  lib.hm_view_features.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                   C.c_void_p, C.c_void_p]
-  rc = lib.hm_view_features(_p(labels), labels.shape[0], K, _p(idx), _p(vis), idx.shape[0], float(threshold), _p(out),
-                            _p(point_visible))
+  rc = lib.hm_view_features(labels, labels.shape[0], K, idx, vis, idx.shape[0], float(threshold), out, point_visible)
   assert rc == 0, rc
   return out
 
