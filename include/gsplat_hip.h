@@ -843,6 +843,28 @@ size_t gsr_image_metrics_workspace_bytes(int32_t H, int32_t W);
 int gsr_image_metrics(const float* image, const float* source, int32_t H, int32_t W, float* metrics_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pose tables (camera_table/pose_table.py PoseTable, RigPoseTable) ------------------------------------------------
+ * A table is q [A, 4] (XYZW, not necessarily unit) and t [A, 3], float32 contiguous.  gsr_pose_forward writes, for image
+ * b of B, T_out[b] (4x4 row-major, T_out 16-byte aligned) = pose(left[idx_left[b]]) when the right table is absent
+ * (q_right, t_right, idx_right all NULL) and pose(left[idx_left[b]]) pose(right[idx_right[b]]) otherwise (a rig: left =
+ * camera_t_rig, right = rig_t_world), with pose(q, t) = [R(q / max(|q|, 1e-12)) t; 0 0 0 1].  One launch; B = 0 returns
+ * GSR_OK without one.  gsr_pose_backward takes d_T [B, 4, 4] (row 3 ignored) and writes d_q [A, 4], d_t [A, 3] of each
+ * table whose pair of outputs is given (a pair may be NULL; not both): every row, zeros for a row no image selects, and
+ * for a selected row the sum over its images in increasing b, chained through the rotation and the normalisation.  One
+ * launch, no float atomics: bit-reproducible.  The order of every operation is in csrc/gsr_camera_table.h.
+ * An index outside [0, A) is no fault: it reads row 0, and the kernel ORs 1 into status[0] (device int32, the caller
+ * zeroes it once and reads it when it chooses to wait).  A and B at most GSR_POSE_MAX_ROWS.
+ * gsr_pose_block_size: the threads per block of both launches. */
+#define GSR_POSE_MAX_ROWS 16777216
+int gsr_pose_forward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                     const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                     float* T_out, int32_t* status, void* stream);
+int gsr_pose_backward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                      const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                      const float* d_T, float* d_q_left, float* d_t_left, float* d_q_right, float* d_t_right,
+                      int32_t* status, void* stream);
+int gsr_pose_block_size(void);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -26,6 +26,10 @@ from .filter3d import sampling_rate, smooth_gaussians
 from .sh_fit import ShFit, fit_sh
 from .controller import (Controller, ControllerConfig, DisabledConfig, DisabledController, MCMCConfig, MCMCController,
                          Progress, TargetConfig, TargetController, densify_and_prune, mcmc_noise)
+from .camera_table import (Camera, CameraRigTable, CameraTable, Cameras, Label, MultiCameraTable, PoseTable, Projections,
+                           RigPoseTable, camera_adjacency_matrix, camera_json, camera_scene_extents, camera_similarity,
+                           check_indices, pose_adjacency, pose_matrices)
+from .normalization import Normalization, NormalizationConfig, median_knn
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -42,4 +46,7 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "mse_to_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "evaluate_scene", "sampling_rate",
            "smooth_gaussians", "ShFit", "fit_sh", "Progress", "ControllerConfig", "Controller", "DisabledConfig",
            "DisabledController", "TargetConfig", "TargetController", "MCMCConfig", "MCMCController", "densify_and_prune",
-           "mcmc_noise"]
+           "mcmc_noise", "Label", "Projections", "Camera", "Cameras", "PoseTable", "RigPoseTable", "CameraTable",
+           "CameraRigTable", "MultiCameraTable", "camera_scene_extents", "pose_adjacency", "camera_similarity",
+           "camera_adjacency_matrix", "camera_json", "pose_matrices", "check_indices", "Normalization",
+           "NormalizationConfig", "median_knn"]

@@ -14,6 +14,7 @@
 #include "gsr_filter3d.h"
 #include "gsr_sh_fit.h"
 #include "gsr_controller.h"
+#include "gsr_camera_table.h"
 #include "gsr_color.h"
 #include "gsr_eval.h"
 
@@ -546,6 +547,41 @@ void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotat
       gsr_mcmc_noise_row(position + 3 * i, log_scaling + 3 * i, rotation_xyzw + 4 * i, level, scale_eps, (uint64_t)i, seed,
                          step);
   }
+}
+
+}  // extern "C"
+
+// ---- pose tables (gsr_camera_table.h) ----
+
+extern "C" {
+
+int hm_pose_forward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                    const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                    float* T) {
+  bool bad = false;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t l = gsr_pose_index(idx_left[b], A_left, &bad);
+    if (q_right) {
+      const int64_t r = gsr_pose_index(idx_right[b], A_right, &bad);
+      gsr_pose_forward_image(q_left + 4 * l, t_left + 3 * l, q_right + 4 * r, t_right + 3 * r, T + 16 * b);
+    } else {
+      gsr_pose_forward_image(q_left + 4 * l, t_left + 3 * l, nullptr, nullptr, T + 16 * b);
+    }
+  }
+  return bad ? -1 : 0;
+}
+
+int hm_pose_backward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                     const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                     const float* d_T, float* d_q_left, float* d_t_left, float* d_q_right, float* d_t_right) {
+  bool bad = false;
+  for (int64_t a = 0; a < A_left && d_q_left; ++a)
+    bad |= gsr_pose_backward_row(true, a, q_left, A_left, idx_left, q_right, t_right, A_right, idx_right, B, d_T,
+                                 d_q_left + 4 * a, d_t_left + 3 * a);
+  for (int64_t a = 0; q_right && a < A_right && d_q_right; ++a)
+    bad |= gsr_pose_backward_row(false, a, q_right, A_right, idx_right, q_left, t_left, A_left, idx_left, B, d_T,
+                                 d_q_right + 4 * a, d_t_right + 3 * a);
+  return bad ? -1 : 0;
 }
 
 }  // extern "C"

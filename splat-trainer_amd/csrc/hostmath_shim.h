@@ -103,6 +103,17 @@ void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotat
                    const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
                    float noise_level, float scale_eps, uint64_t seed, uint64_t step);
 
+/* ---- pose tables (gsr_camera_table.h): the device's order of operations ---- */
+/* q [A, 4], t [A, 3], idx [B]; the right table may be absent (all three NULL).  T [B, 4, 4].  Returns -1 when an index is
+ * outside its table (it then reads row 0, as on the device), 0 otherwise. */
+int hm_pose_forward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                    const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                    float* T);
+/* d_T [B, 4, 4]; d_q / d_t of each table whose pair is given (a pair may be NULL), every row written */
+int hm_pose_backward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
+                     const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
+                     const float* d_T, float* d_q_left, float* d_t_left, float* d_q_right, float* d_t_right);
+
 #ifdef __cplusplus
 }
 #endif
