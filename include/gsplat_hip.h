@@ -865,6 +865,35 @@ int gsr_pose_backward(const float* q_left, const float* t_left, int64_t A_left, 
                       int32_t* status, void* stream);
 int gsr_pose_block_size(void);
 
+/* ---- histograms of the detailed training logs (logger/histogram.py Histogram, scene/mlp_scene.py log_gradients,
+ * hist_log_nonzero, controller/point_state.py log_histograms) -------------------------------------------------------
+ * gsr_histogram bins the entries of values [N, C] (float32, contiguous) in one sweep.  rows [M] int64 (NULL: all N rows,
+ * M ignored) gathers rows, repeats and any order allowed; an index outside [0, N) is never read and its C entries count
+ * as non-finite.  weight [N] float32 (NULL: none) divides: the entry of row r is x = v / (eps + weight[r]), r the index
+ * into values.  mode 0: t = x.  mode 1: t = log10(x) for x > min_value, every other x is dropped.  mode 2:
+ * t = log10(max(x, min_value)).  An entry is kept when it passes the mode's threshold and both x and t are finite; the
+ * non-finite ones are counted apart.
+ * Range: auto_range = 0 takes (lo, hi), finite with hi >= lo; auto_range != 0 ignores them and a first pass takes lo and
+ * hi as the minimum and maximum of the kept t (integer atomics on ordered keys: exact, order-independent); the binning
+ * pass reads them on the device, so the call never waits for the host, and its results equal, bit for bit, those of the
+ * fixed-range call with the (lo, hi) it reports in stats[3], stats[4].
+ * Bin (float32, no contraction; csrc/gsr_histogram.h is the one statement of it, shared with the host shim):
+ * p = (t - lo) * (num_bins / (hi - lo)), b = floor(p); t == hi takes the last bin; hi == lo puts every kept entry in bin
+ * 0; a b outside [0, num_bins) is "outside": left out with trim != 0, clamped in with trim == 0.
+ * Outputs: counts [num_bins] int64 and stats [8] double, both device memory, both overwritten: 0 kept entries, 1 sum of t
+ * and 2 sum of t^2 over the BINNED entries (the kept ones less, with trim, the outside ones: what counts holds), 3 minimum
+ * and 4 maximum of the kept t (0 when nothing was kept), 5 dropped by the threshold, 6 non-finite, 7 outside.
+ * Counts and tallies are integer atomics (LDS counters per wave, then one global add per bin and block, spread over 16
+ * sets of words in the workspace that a last pass adds up), the two sums fp64 partials per block added in a fixed order;
+ * no float atomics: every output is the same bits on every run.
+ * num_bins in 1..GSR_HISTOGRAM_MAX_BINS.  N == 0 or (rows and M == 0) launches nothing and leaves zeros.  workspace: device
+ * memory, 16-byte aligned, gsr_histogram_workspace_bytes() bytes, not shared between calls in flight on two streams. */
+#define GSR_HISTOGRAM_MAX_BINS 1024
+size_t gsr_histogram_workspace_bytes(void);
+int gsr_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows, int64_t M, const float* weight,
+                  float eps, int32_t mode, float min_value, float lo, float hi, int32_t num_bins, int32_t auto_range,
+                  int32_t trim, int64_t* counts, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

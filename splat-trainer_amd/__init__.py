@@ -30,6 +30,15 @@ from .camera_table import (Camera, CameraRigTable, CameraTable, Cameras, Label, 
                            RigPoseTable, camera_adjacency_matrix, camera_json, camera_scene_extents, camera_similarity,
                            check_indices, pose_adjacency, pose_matrices)
 from .normalization import Normalization, NormalizationConfig, median_knn
+from .histogram import Histogram, tensor_histogram
+from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
+                     StepValue)
+from .dataset import Dataset, ImageView, PointCloud, TensorDataset, expand_index, partition_stride, split_every
+from .cloud_init import (CloudInitConfig, from_pointcloud, from_scaled_pointcloud, get_initial_gaussians,
+                         to_pointcloud)
+from .visibility import TargetOverlap, TargetOverlapConfig
+from .trainer import (NaNParameterException, NoProgressException, TrainConfig, Trainer, TrainerState,
+                      TrainingException, TrainingTimeoutException, find_checkpoint, load_checkpoint)
 from .compat import TaichiQueue, check_finite, count_nonfinite, random_3d_gaussians, random_camera
 
 __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Rendering", "pop_raster_config",
@@ -49,4 +58,9 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "mcmc_noise", "Label", "Projections", "Camera", "Cameras", "PoseTable", "RigPoseTable", "CameraTable",
            "CameraRigTable", "MultiCameraTable", "camera_scene_extents", "pose_adjacency", "camera_similarity",
            "camera_adjacency_matrix", "camera_json", "pose_matrices", "check_indices", "Normalization",
-           "NormalizationConfig", "median_knn"]
+           "NormalizationConfig", "median_knn", "Histogram", "tensor_histogram", "Logger", "NullLogger", "CompositeLogger",
+           "StateLogger", "HistoryLogger", "LoggerWithState", "StateTree", "StepValue", "ImageView", "Dataset",
+           "PointCloud", "TensorDataset", "split_every", "partition_stride", "expand_index", "CloudInitConfig",
+           "from_pointcloud", "from_scaled_pointcloud", "to_pointcloud", "get_initial_gaussians", "TargetOverlapConfig",
+           "TargetOverlap", "TrainConfig", "TrainerState", "TrainingException", "NaNParameterException",
+           "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer"]

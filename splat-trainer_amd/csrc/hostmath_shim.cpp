@@ -17,6 +17,7 @@
 #include "gsr_camera_table.h"
 #include "gsr_color.h"
 #include "gsr_eval.h"
+#include "gsr_histogram.h"
 
 extern "C" {
 
@@ -582,6 +583,76 @@ int hm_pose_backward(const float* q_left, const float* t_left, int64_t A_left, c
     bad |= gsr_pose_backward_row(false, a, q_right, A_right, idx_right, q_left, t_left, A_left, idx_left, B, d_T,
                                  d_q_right + 4 * a, d_t_right + 3 * a);
   return bad ? -1 : 0;
+}
+
+void hm_hist_entry(const float* v, const float* w, int64_t n, float eps, int32_t mode, float min_value, int32_t* cls,
+                   float* t) {
+  for (int64_t i = 0; i < n; ++i) cls[i] = gsr_hist_entry(v[i], w != nullptr, w ? w[i] : 0.f, eps, mode, min_value, t + i);
+}
+
+void hm_hist_bin(const float* t, int64_t n, float lo, float hi, int32_t num_bins, int32_t trim, int32_t* bin,
+                 int32_t* outside) {
+  for (int64_t i = 0; i < n; ++i) {
+    int o;
+    bin[i] = gsr_hist_bin(t[i], lo, hi, num_bins, trim != 0, &o);
+    outside[i] = o;
+  }
+}
+
+void hm_hist_keys(const float* x, int64_t n, uint32_t* key, float* back) {
+  for (int64_t i = 0; i < n; ++i) {
+    key[i] = gsr_hist_key(x[i]);
+    back[i] = gsr_hist_unkey(key[i]);
+  }
+}
+
+int hm_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows, int64_t M, const float* weight,
+                 float eps, int32_t mode, float min_value, float lo, float hi, int32_t num_bins, int32_t auto_range,
+                 int32_t trim, int64_t* counts, double* stats) {
+  if (!counts || !stats || N < 0 || M < 0 || C < 1 || mode < 0 || mode > 2 || num_bins < 1) return -1;
+  if (!auto_range && !(gsr_hist_finite(lo) && gsr_hist_finite(hi) && hi >= lo)) return -1;
+  for (int b = 0; b < num_bins; ++b) counts[b] = 0;
+  for (int k = 0; k < 8; ++k) stats[k] = 0.0;
+  const int64_t R = rows ? M : N;
+  uint32_t min_c = 0u, max_k = 0u;
+  for (int pass = auto_range ? 0 : 1; pass < 2; ++pass) {
+    if (pass == 1 && auto_range) {
+      lo = gsr_hist_unkey(~min_c);
+      hi = gsr_hist_unkey(max_k);
+    }
+    for (int64_t r = 0; r < R; ++r) {
+      const int64_t src = rows ? rows[r] : r;
+      for (int64_t c = 0; c < C; ++c) {
+        float t = 0.f;
+        const int cls = src < 0 || src >= N ? GSR_HIST_NONFINITE
+                                            : gsr_hist_entry(values[src * C + c], weight != nullptr,
+                                                             weight ? weight[src] : 0.f, eps, mode, min_value, &t);
+        if (pass == 0) {
+          if (cls == GSR_HIST_KEPT) {
+            const uint32_t k = gsr_hist_key(t);
+            min_c = ~k > min_c ? ~k : min_c;
+            max_k = k > max_k ? k : max_k;
+          }
+          continue;
+        }
+        stats[5] += cls == GSR_HIST_DROPPED;
+        stats[6] += cls == GSR_HIST_NONFINITE;
+        if (cls != GSR_HIST_KEPT) continue;
+        stats[3] = stats[0] == 0.0 || t < stats[3] ? (double)t : stats[3];
+        stats[4] = stats[0] == 0.0 || t > stats[4] ? (double)t : stats[4];
+        stats[0] += 1.0;
+        int outside;
+        const int b = gsr_hist_bin(t, lo, hi, num_bins, trim != 0, &outside);
+        stats[7] += outside;
+        if (b >= 0) {
+          ++counts[b];
+          stats[1] += (double)t;
+          stats[2] += (double)t * (double)t;
+        }
+      }
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

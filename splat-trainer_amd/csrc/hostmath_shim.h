@@ -114,6 +114,21 @@ int hm_pose_backward(const float* q_left, const float* t_left, int64_t A_left, c
                      const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
                      const float* d_T, float* d_q_left, float* d_t_left, float* d_q_right, float* d_t_right);
 
+/* ---- histogram entry and bin rules (gsr_histogram.h): the device's functions, one entry at a time ---- */
+/* cls [n] int32 (0 kept, 1 dropped, 2 non-finite) and t [n] (written where kept) of v [n]; w [n] may be NULL */
+void hm_hist_entry(const float* v, const float* w, int64_t n, float eps, int32_t mode, float min_value, int32_t* cls,
+                   float* t);
+/* bin [n] int32 (-1: outside with trim on) and outside [n] int32 of kept values t [n] */
+void hm_hist_bin(const float* t, int64_t n, float lo, float hi, int32_t num_bins, int32_t trim, int32_t* bin,
+                 int32_t* outside);
+/* gsr_histogram on the host, entries in row order, the sums in fp64 in that order: counts [num_bins], stats [8].
+ * Returns -1 for arguments gsr_histogram rejects. */
+int hm_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows, int64_t M, const float* weight,
+                 float eps, int32_t mode, float min_value, float lo, float hi, int32_t num_bins, int32_t auto_range,
+                 int32_t trim, int64_t* counts, double* stats);
+/* key [n] uint32 of x [n] and back [n] = unkey(key) */
+void hm_hist_keys(const float* x, int64_t n, uint32_t* key, float* back);
+
 #ifdef __cplusplus
 }
 #endif

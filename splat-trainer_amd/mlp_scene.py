@@ -27,6 +27,7 @@ from .color_model import ColorModel, ColorModelConfig, Colors
 from .filter3d import sampling_rate, smooth_gaussians
 from .data_types import CameraParams, Gaussians3D, RasterConfig, Rendering, pop_raster_config
 from .harness import split_gaussians_uniform
+from .histogram import tensor_histogram
 from .optim import ParameterClass, VisibilityAwareLaProp, VisibilityOptimizer, point_basis_rows
 from .renderer import project_to_image, render_projected
 from .sh import evaluate_sh_at
@@ -191,6 +192,60 @@ class MLPScene:
     self.glo_opt.step()
     reg.scene_post_step(pts.rotation.data, pts.log_scaling.data)
     self.zero_grad()
+
+  # ---- detailed logs (mlp_scene.py:163-211).  The scene holds no logger: each method is handed one.  Every histogram is
+  # a Histogram built by tensor_histogram -- gather, weight and log10 fused into the native sweep, no boolean-mask
+  # indexing, no host wait per histogram -- and none of them writes a parameter, a gradient or optimizer state.
+  @torch.no_grad()
+  def detail_histograms(self, what: str, min_vis: float = 0.1) -> Dict[str, "Histogram"]:
+    """{name: Histogram} of one family of the detailed logs: ``"gradients"`` (log10 of the positive gradient entries of
+    the rows whose accumulated visibility exceeds ``min_vis``, raw and divided by ``vis_smooth + visibility``),
+    ``"optimizer"`` (log10 of the positive entries of the optimizer state) or ``"params"``."""
+    pts, out = self.points, {}
+    if what == "gradients":
+      visible = pts.visible
+      vis_idx = torch.nonzero(visible > min_vis).squeeze(1)          # (the one wait of a detailed log)
+      for key in pts.parameter_groups:
+        grad = pts.tensors[key].grad
+        if grad is not None:
+          out[f"log10_grad/{key}"] = tensor_histogram(grad, rows=vis_idx, log10="drop", min_value=1e-16)
+          out[f"log10_norm_grad/{key}"] = tensor_histogram(grad, rows=vis_idx, weight=visible, eps=self.config.vis_smooth,
+                                                           log10="drop", min_value=1e-16)
+    elif what == "optimizer":
+      for key, state in pts.tensor_state.items():
+        for k, v in state.items():
+          out[f"{key}/{k}"] = tensor_histogram(v, log10="drop", min_value=1e-16)
+    elif what == "params":
+      out["params/opacity"] = tensor_histogram(torch.sigmoid(pts.alpha_logit.detach()))
+      out["params/log_scale"] = tensor_histogram(pts.log_scaling)
+      out["params/feature"] = tensor_histogram(pts.feature)
+      out["params/glo_feature"] = tensor_histogram(self.color_table.weight)
+      scale = torch.exp(pts.log_scaling.detach())
+      largest = scale.max(1).values
+      out["params/stable_rank"] = tensor_histogram(scale.sum(1) / largest)
+      out["params/aspect"] = tensor_histogram(largest / (scale.min(1).values + 1e-4))
+    else:
+      raise ValueError(f"what must be 'gradients', 'optimizer' or 'params', got {what!r}")
+    return out
+
+  def log_gradients(self, logger, min_vis: float = 0.1):
+    """mlp_scene.py:167-178; call it before ``step``, which clears the gradients and ``visible``."""
+    for name, hist in self.detail_histograms("gradients", min_vis).items():
+      logger.log_histogram(name, hist)
+
+  def log_optimizer_state(self, logger, name: str = "optimizer"):
+    """mlp_scene.py:180-187."""
+    for key, hist in self.detail_histograms("optimizer").items():
+      logger.log_histogram(f"{name}/{key}", hist)
+
+  def log_params(self, logger):
+    """mlp_scene.py:190-206."""
+    for name, hist in self.detail_histograms("params").items():
+      logger.log_histogram(name, hist)
+
+  def log_checkpoint(self, logger, progress=None):
+    """mlp_scene.py:210-211."""
+    self.log_params(logger)
 
   @torch.no_grad()
   def add_rendering(self, image_idx: Optional[int], rendering: Rendering):

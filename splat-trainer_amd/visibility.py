@@ -592,3 +592,54 @@ class RandomSampler:
     indices = self.next[:batch_size]
     self.next = self.next[batch_size:]
     return indices
+
+
+@dataclass(frozen=True)
+class TargetOverlapConfig:
+  batch_size: int = 1
+  overlap_temperature: float = 0.5
+  history_size: int = 2
+  target_overlap: float = 0.5
+
+  def create(self, train_idx: torch.Tensor) -> "TargetOverlap":
+    return TargetOverlap(self, train_idx)
+
+  def from_state_dict(self, state_dict: dict, train_idx: torch.Tensor) -> "TargetOverlap":
+    return TargetOverlap(self, train_idx, state_dict["history_idx"], state_dict["available_mask"])
+
+
+class TargetOverlap:
+  """Selects views whose overlap with a short history of the last selected views is near ``target_overlap``; every view
+  is used once before any is used again.  ``history_idx`` and ``available_mask`` index ``train_idx`` and with it the rows
+  of the view clustering, which the trainer builds over the training views in that order; ``select_images`` returns
+  entries of ``train_idx``.
+
+  One deviation from the reference: it updates the history with ``history_idx[batch_idx:]``, a slice by a tensor, which
+  only works for a batch of one; here the new history is ``cat([batch, history])[:history_size]``, for any batch size."""
+
+  def __init__(self, config: TargetOverlapConfig, train_idx: torch.Tensor, history_idx: Optional[torch.Tensor] = None,
+               available_mask: Optional[torch.Tensor] = None):
+    self.train_idx = train_idx
+    self.config = config
+    if available_mask is None:
+      available_mask = torch.ones(len(train_idx), device=train_idx.device, dtype=torch.bool)
+    if history_idx is None:
+      history_idx = torch.randperm(len(train_idx))[:config.history_size].to(train_idx.device)
+    self.available_mask = available_mask
+    self.history_idx = history_idx
+
+  def state_dict(self) -> dict:
+    return dict(history_idx=self.history_idx, available_mask=self.available_mask)
+
+  def select_images(self, view_clustering: ViewClustering, progress: Any = None) -> torch.Tensor:
+    batch_size = self.config.batch_size
+    if int(self.available_mask.sum()) < batch_size:
+      self.available_mask.fill_(True)
+    vis = F.normalize(view_clustering.normalized_visibility[self.history_idx].sum(0), dim=0, p=2)
+    overlaps = view_clustering.overlaps_with(vis)
+    score = 1 - (self.config.target_overlap - overlaps[self.available_mask]).pow(2)
+    available = torch.nonzero(self.available_mask).squeeze(1)
+    chosen = available[sample_with_temperature(score + 1e-6, temperature=self.config.overlap_temperature, n=batch_size)]
+    self.available_mask[chosen] = False
+    self.history_idx = torch.cat([chosen, self.history_idx])[:self.config.history_size]
+    return self.train_idx[chosen]
