@@ -112,7 +112,9 @@ size_t gsr_sort_workspace_bytes(int64_t n);
 /* Stable LSD radix sort of (key, value) pairs by key bits [begin_bit, end_bit); ping-pongs a<->b.
  * Returns 0 if the result ends in (keys_a, vals_a), 1 if in (keys_b, vals_b), negative on error.
  * n_dev (may be NULL): device word with the element count when n is only the capacity of the arrays (workspace sized
- * for n): the sort can then be enqueued before the count has reached the host; min(n, *n_dev) elements are sorted. */
+ * for n): the sort can then be enqueued before the count has reached the host; min(n, *n_dev) elements are sorted.
+ * Read-ahead: all n slots of the input arrays -- keys, values and, in gsr_sort_pairs2_u32, the second values -- may be
+ * read (never past n); what lies behind the count is not used. */
 int gsr_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, int64_t n,
                        int vals_are_iota, int begin_bit, int end_bit, void* workspace, size_t workspace_bytes,
                        const uint32_t* n_dev, void* stream);
@@ -208,7 +210,9 @@ int gsr_sh_backward_multi(const float* dL_dcolors_dense, int64_t dense_stride, c
 /* ---- K2 + K3 fused  (render_gaussians: project_to_image + evaluate_sh_at in one sweep) ------------------------ */
 /* One [M,16] row per visible splat (GSR_ROW_FLOATS), written whole:  u v A B | C opacity qlim f0 | f1 f2 depth 0 | 0 0 0 0,
  * exactly the values gsr_project_forward + gsr_sh_forward return (same device code).  screen_scale_out [M,2];
- * jacobian_out [M,9] or NULL, depth_keys_out [M] or NULL, count_dev or NULL as in the two single calls. */
+ * jacobian_out [M,9] or NULL, depth_keys_out [M] or NULL, count_dev or NULL as in the two single calls.
+ * Read-ahead: with count_dev the kernel requests `indexes` before it knows the count, at ranks up to M - 1: the array
+ * holds M entries (what lies behind the count is never used as an index), and threads past the count read scene row 0. */
 int gsr_project_sh_forward(const float* position, const float* log_scaling, const float* rotation_xyzw,
                            const float* alpha_logit, const float* sh_features, int32_t K, const int64_t* indexes, int64_t M,
                            const float* T_camera_world, const float* projection, const float* camera_pos,
@@ -269,7 +273,10 @@ int gsr_pack_rows_wide(const float* gaussians2d, const float* depth, const float
 int gsr_tile_count(const float* rows, const uint32_t* order, int64_t M, int32_t W, int32_t H,
                    const GsrRasterParamsC* params_host, uint32_t* count_out, uint32_t* tile_hits_out,
                    const uint32_t* M_dev /* NULL, or the device word with the visible count when M is a capacity: ranks at
-                                            or beyond it get count 0 */, void* stream);
+                                            or beyond it get count 0.  Read-ahead: order[] is requested before the
+                                            count is known, at ranks up to M - 1: it holds M words, and what lies
+                                            behind the count is never used as a row number (gsr_tile_count_offsets
+                                            alike) */, void* stream);
 /* gsr_tile_count followed by the exclusive scan of the counts in TWO launches instead of three (the count pass leaves
  * per-block totals in the workspace, the scan pass adds them up itself): offsets_out [M], total_dev = the pair count O,
  * overflow_flag raised when O reaches 2^31 (as gsr_exclusive_scan_u32_checked does).  M <= GSR_TILE_COUNT_OFFSETS_MAX

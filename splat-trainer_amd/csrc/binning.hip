@@ -97,7 +97,7 @@ __device__ __forceinline__ uint32_t wave_large_extents(bool large, float u, floa
 
 // One depth rank's tile count and hit record (see TileHits).  `live` false: a lane without a rank (it only takes part
 // in the wave's cooperative passes).
-__device__ __forceinline__ uint32_t tile_count_one(const float* __restrict__ rows, const uint32_t* __restrict__ order,
+__device__ __forceinline__ uint32_t tile_count_one(const float* __restrict__ rows, uint32_t splat,
                                                    int64_t k, bool live, int tiles_x, int tiles_y,
                                                    const GsrRasterParams& rp, TileHits* __restrict__ hits) {
   float2 uv = make_float2(0.f, 0.f), ab = uv, co = uv;
@@ -108,7 +108,7 @@ __device__ __forceinline__ uint32_t tile_count_one(const float* __restrict__ row
   uint32_t n = 0;
   bool large = false;
   if (live) {
-    const int64_t s = order[k];
+    const int64_t s = splat;                  // (read only here: behind the count it is not a splat id)
     const float4* r = reinterpret_cast<const float4*>(rows + GSR_ROW_FLOATS * s);
     const float4 r0 = r[0];
     const float4 r1 = r[1];
@@ -153,8 +153,11 @@ __global__ __launch_bounds__(256) void tile_count_kernel(const float* __restrict
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // (M may be a capacity with the visible count still on the device: ranks behind it count zero tiles, so the scan over
   // the capacity needs no count of its own; every lane stays for the wave's cooperative pass over large extents)
+  // the rank's splat id is requested next to the device count, at a rank clamped to the capacity (M >= 1), and used
+  // as a row number only by a live rank
+  const uint32_t splat = order[min(k, M - 1)];
   const bool live = k < M && !(M_dev && k >= (int64_t)*M_dev);
-  uint32_t n = tile_count_one(rows, order, k, live, tiles_x, tiles_y, rp, hits);
+  uint32_t n = tile_count_one(rows, splat, k, live, tiles_x, tiles_y, rp, hits);
   if (k < M) count[k] = n;
   if (block_sums) {
     // also leaves the block's total for offsets_from_sums_kernel (the scan's reduce pass, folded in here)
@@ -337,6 +340,8 @@ __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* __restric
   const int64_t k = k0 + threadIdx.x;
   const bool have = k < M;
   const uint32_t b = have ? offsets[k] : 0u, n = have ? count[k] : 0u;
+  // (the row this rank writes at the end: requested with the other two words, not behind the whole reduction)
+  const int64_t s = have && order ? (int64_t)order[k] : k;    // order == NULL: ranks are splat ids already
   const bool serial = n <= GSR_REDUCE_SERIAL;
   if (threadIdx.x == 0) s_lo = b;
   const int64_t klast = (k0 + 255 < M ? k0 + 255 : M - 1);
@@ -352,12 +357,20 @@ __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* __restric
     const float v = mine ? vis_partial[c + threadIdx.x] : 0.f;
     s_vis[threadIdx.x] = v;
     __syncthreads();
-    // slots never written by the backward pass (vis == 0) hold garbage: neither fetched nor summed
+    // slots never written by the backward pass (vis == 0) hold garbage: neither fetched nor summed.  The thread's three
+    // pieces are requested before the first is parked: one memory wait per chunk, not one per piece.
+    float4 piece[3];
+    bool take[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const uint32_t f = threadIdx.x + t * CH;                 // float4 index inside the chunk
-      if (f < 3 * m && s_vis[f / 3] > 0.f) s_part[f] = src[(size_t)3 * c + f];
+      take[t] = f < 3 * m && s_vis[f / 3] > 0.f;
+      piece[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (take[t]) piece[t] = src[(size_t)3 * c + f];
     }
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+      if (take[t]) s_part[threadIdx.x + t * CH] = piece[t];
     __syncthreads();
     const uint32_t j0 = max(b, c), j1 = serial ? min(b + n, c + m) : 0u;
     for (uint32_t j = j0; j < j1; ++j) {
@@ -408,7 +421,6 @@ __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* __restric
     }
   }
   if (!have) return;
-  const int64_t s = order ? (int64_t)order[k] : k;           // order == NULL: ranks are splat ids already
   float4* g = reinterpret_cast<float4*>(grows + GSR_ROW_FLOATS * s);
   g[0] = a0;
   g[1] = a1;

@@ -12,6 +12,21 @@ constexpr int CULL_ITEMS = 16;                     // points per lane
 constexpr int CULL_WAVE_SPAN = 64 * CULL_ITEMS;    // 1024 consecutive points per wave
 constexpr int64_t CULL_SELF_PREFIX_MAX_WAVES = 4096;    // up to 4.2 M points the write pass sums the wave counts itself
 
+constexpr int CULL_BATCH = 8;                      // positions per lane requested before one wait
+
+// CULL_BATCH of a lane's positions, requested together, for a wave whose whole span lies inside the N points: the
+// addresses depend on the lane alone and share one base, so the wave waits for memory twice per span instead of once
+// per group of four.  Eight and not all sixteen: 24 registers of positions keep the kernels at eight waves per SIMD.
+// (The one wave whose span crosses N walks it point by point under `i < N`, as before.)
+__device__ __forceinline__ void cull_load_batch(const float* __restrict__ pos, int64_t first, int lane,
+                                                float (&p)[CULL_BATCH][3]) {
+  const float* q = pos + 3 * (first + lane);
+#pragma unroll
+  for (int it = 0; it < CULL_BATCH; ++it)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[it][k] = q[192 * it + k];
+}
+
 // pass 1: each wave counts the in-view points of its 1024-point span (ballot + popcount)
 __global__ __launch_bounds__(256) void cull_count_kernel(const float* __restrict__ pos, int64_t N,
                                                          const float* __restrict__ Tcw, const float* __restrict__ proj,
@@ -20,15 +35,28 @@ __global__ __launch_bounds__(256) void cull_count_kernel(const float* __restrict
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wave >= num_waves) return;
   const int lane = gsr_lane();
-  const GsrCam cam = gsr_load_cam(Tcw, proj);
   const int64_t base = wave * CULL_WAVE_SPAN;
   uint32_t cnt = 0;
+  if (base + CULL_WAVE_SPAN <= N) {                // (wave-uniform)
+    float p[CULL_BATCH][3];
+    cull_load_batch(pos, base, lane, p);
+    const GsrCam cam = gsr_load_cam(Tcw, proj);
+#pragma unroll
+    for (int b0 = 0; b0 < CULL_ITEMS; b0 += CULL_BATCH) {
+#pragma unroll
+      for (int it = 0; it < CULL_BATCH; ++it)
+        cnt += (uint32_t)__popcll(__ballot(gsr_in_view(cam, p[it][0], p[it][1], p[it][2], W, H, near_p, far_p, margin)));
+      if (b0 + CULL_BATCH < CULL_ITEMS) cull_load_batch(pos, base + (b0 + CULL_BATCH) * 64, lane, p);
+    }
+  } else {
+    const GsrCam cam = gsr_load_cam(Tcw, proj);
 #pragma unroll 4
-  for (int it = 0; it < CULL_ITEMS; ++it) {
-    int64_t i = base + it * 64 + lane;
-    bool in = false;
-    if (i < N) in = gsr_in_view(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], W, H, near_p, far_p, margin);
-    cnt += (uint32_t)__popcll(__ballot(in));
+    for (int it = 0; it < CULL_ITEMS; ++it) {
+      int64_t i = base + it * 64 + lane;
+      bool in = false;
+      if (i < N) in = gsr_in_view(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], W, H, near_p, far_p, margin);
+      cnt += (uint32_t)__popcll(__ballot(in));
+    }
   }
   if (lane == 0) wave_counts[wave] = cnt;
 }
@@ -43,27 +71,51 @@ __global__ __launch_bounds__(256) void cull_write_kernel(const float* __restrict
   const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wave >= num_waves) return;
   const int lane = gsr_lane();
-  const GsrCam cam = gsr_load_cam(Tcw, proj);
   const int64_t base = wave * CULL_WAVE_SPAN;
+  const bool whole = base + CULL_WAVE_SPAN <= N;   // (wave-uniform)
+  float p[CULL_BATCH][3];
+  if (whole) cull_load_batch(pos, base, lane, p);  // on their way while the predecessors' counts are added up
+  const uint32_t own = wave_offsets[wave];
+  const GsrCam cam = gsr_load_cam(Tcw, proj);
   uint32_t run;
   if (count_dev) {
     // wave_offsets holds the waves' RAW counts: every wave adds up its predecessors' itself (a few thousand words at
-    // millions of points -- cheaper than a scan launch in between) and the last one leaves the total
+    // millions of points -- cheaper than a scan launch in between) and the last one leaves the total.  Two words per
+    // lane and trip (an index behind the last wave reads the last wave's word and counts zero).
     uint32_t before = 0u;
-    for (int64_t j = lane; j < wave; j += 64) before += wave_offsets[j];
+    const uint32_t w32 = (uint32_t)wave, last32 = (uint32_t)(num_waves - 1);   // (gsr_frustum_cull rejects N > 2^31 - 1: at most 2^21 waves)
+#pragma unroll 1
+    for (uint32_t j0 = (uint32_t)lane; j0 < w32; j0 += 128u) {
+      const uint32_t c0 = wave_offsets[j0], c1 = wave_offsets[min(j0 + 64u, last32)];
+      before += c0 + (j0 + 64u < w32 ? c1 : 0u);
+    }
     run = gsr_wave_sum_u32(before);
-    if (wave == num_waves - 1 && lane == 0) *count_dev = run + wave_offsets[wave];
+    if (wave == num_waves - 1 && lane == 0) *count_dev = run + own;
   } else {
-    run = wave_offsets[wave];
+    run = own;
   }
+  if (whole) {
+#pragma unroll
+    for (int b0 = 0; b0 < CULL_ITEMS; b0 += CULL_BATCH) {
+#pragma unroll
+      for (int it = 0; it < CULL_BATCH; ++it) {
+        const bool in = gsr_in_view(cam, p[it][0], p[it][1], p[it][2], W, H, near_p, far_p, margin);
+        const uint64_t m = __ballot(in);
+        if (in) indexes[run + (uint32_t)gsr_mbcnt(m)] = base + (b0 + it) * 64 + lane;
+        run += (uint32_t)__popcll(m);
+      }
+      if (b0 + CULL_BATCH < CULL_ITEMS) cull_load_batch(pos, base + (b0 + CULL_BATCH) * 64, lane, p);
+    }
+  } else {
 #pragma unroll 4
-  for (int it = 0; it < CULL_ITEMS; ++it) {
-    int64_t i = base + it * 64 + lane;
-    bool in = false;
-    if (i < N) in = gsr_in_view(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], W, H, near_p, far_p, margin);
-    uint64_t m = __ballot(in);
-    if (in) indexes[run + (uint32_t)gsr_mbcnt(m)] = i;
-    run += (uint32_t)__popcll(m);
+    for (int it = 0; it < CULL_ITEMS; ++it) {
+      int64_t i = base + it * 64 + lane;
+      bool in = false;
+      if (i < N) in = gsr_in_view(cam, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], W, H, near_p, far_p, margin);
+      uint64_t m = __ballot(in);
+      if (in) indexes[run + (uint32_t)gsr_mbcnt(m)] = i;
+      run += (uint32_t)__popcll(m);
+    }
   }
 }
 
@@ -384,46 +436,73 @@ __global__ __launch_bounds__(256) void project_sh_fwd_kernel(
   constexpr int STAGE_FLOATS = 256 * PITCH > OUT_FLOATS ? 256 * PITCH : OUT_FLOATS;
   __shared__ float s_rows[STAGE_FLOATS];
   __shared__ int32_t s_idx[256];
-  // M is an upper bound when count_dev is given: the true count is still on the device (K1 just produced it)
-  const int64_t count = count_dev ? min(M, (int64_t)*count_dev) : M;
+  // M is an upper bound when count_dev is given: the true count is still on the device (K1 just produced it).  The
+  // thread's index is requested next to that count, at a rank clamped to the capacity; what comes back from behind the
+  // count is not an index and is selected away before anything is addressed with it.
   const int64_t m0 = (int64_t)blockIdx.x * 256;
-  if (m0 >= count) return;                                   // block-uniform
   const int tid = (int)threadIdx.x;
   const int64_t m = m0 + tid;
+  const int64_t i_raw = idx[min(m, M - 1)];                    // M >= 1 (the launch)
+  const int64_t count = count_dev ? min(M, (int64_t)*count_dev) : M;
+  if (m0 >= count) return;                                   // block-uniform
   const bool valid = m < count;
-  const int64_t i = valid ? idx[m] : -1;
+  const int64_t i = valid ? i_raw : -1;
+  // The thread's own parameters: requested as soon as the index is known and consumed behind the coefficient staging,
+  // so the two barriers and the staging's loads no longer stand between the index and them.
+  const int64_t ii = valid ? i : 0;                           // threads past the count redo scene row 0 (unused)
+  float p[3] = {pos[3 * ii], pos[3 * ii + 1], pos[3 * ii + 2]};
+  float s[3] = {ls[3 * ii], ls[3 * ii + 1], ls[3 * ii + 2]};
+  const float4 qv = *reinterpret_cast<const float4*>(rot + 4 * ii);
+  float lg = logit[ii];
   s_idx[tid] = (int32_t)i;                                    // N <= 2^31 - 1 (gsr_frustum_cull)
   __syncthreads();
-  if (ShStage<K>::VEC) {
+  // Staging: ALL of the thread's pieces are requested before the first one is parked in LDS (a row past the count reads
+  // scene row 0 and parks nothing) -- one memory wait for the ROW / 4 (or ROW) loads, not one per piece behind a branch.
+  if constexpr (ShStage<K>::VEC) {
     constexpr int PARTS = ROW / 4;                             // 16-byte pieces per row
+    float4 v[PARTS];
+    int at[PARTS];
 #pragma unroll
     for (int it = 0; it < PARTS; ++it) {
       const int e = it * 256 + tid;
       const int row = e / PARTS, part = e - row * PARTS;
       const int64_t src = s_idx[row];
-      if (src >= 0) {
-        const float4 v = *reinterpret_cast<const float4*>(sh + src * ROW + 4 * part);
-        float* dst = s_rows + row * PITCH + 4 * part;
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+      at[it] = src >= 0 ? row * PITCH + 4 * part : -1;
+      v[it] = *reinterpret_cast<const float4*>(sh + max(src, (int64_t)0) * ROW + 4 * part);
+    }
+#pragma unroll
+    for (int it = 0; it < PARTS; ++it) {
+      if (at[it] >= 0) {
+        float* dst = s_rows + at[it];
+        dst[0] = v[it].x; dst[1] = v[it].y; dst[2] = v[it].z; dst[3] = v[it].w;
       }
     }
   } else {
+    // (rows of 3 or 27 words: nine words per batch -- all 27 at once would hold the degree-2 kernel to three waves per
+    // SIMD where its LDS allows five; the slot and the row's validity are recomputed, not kept, for the same reason)
+    constexpr int NB = ROW < 9 ? ROW : 9;
+    static_assert(ROW % NB == 0, "whole batches");
 #pragma unroll
-    for (int it = 0; it < ROW; ++it) {
-      const int e = it * 256 + tid;
-      const int row = e / ROW, col = e - row * ROW;
-      const int64_t src = s_idx[row];
-      if (src >= 0) s_rows[row * PITCH + col] = sh[src * ROW + col];
+    for (int b0 = 0; b0 < ROW; b0 += NB) {
+      float v[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = (b0 + j) * 256 + tid;
+        const int row = e / ROW, col = e - row * ROW;
+        v[j] = sh[max((int64_t)s_idx[row], (int64_t)0) * ROW + col];
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = (b0 + j) * 256 + tid;
+        const int row = e / ROW, col = e - row * ROW;
+        if (s_idx[row] >= 0) s_rows[row * PITCH + col] = v[j];
+      }
     }
   }
   __syncthreads();
   const GsrCam cam = gsr_load_cam(Tcw, proj);
-  const int64_t ii = valid ? i : idx[m0];                     // threads past the count redo the block's first row (unused)
-  float p[3] = {pos[3 * ii], pos[3 * ii + 1], pos[3 * ii + 2]};
-  float s[3] = {ls[3 * ii], ls[3 * ii + 1], ls[3 * ii + 2]};
-  const float4 qv = *reinterpret_cast<const float4*>(rot + 4 * ii);
   float q[4] = {qv.x, qv.y, qv.z, qv.w};
-  const GsrProjected o = gsr_project_one(cam, rp, p, s, q, logit[ii]);
+  const GsrProjected o = gsr_project_one(cam, rp, p, s, q, lg);
   float w[3][K];
   const float* mine = s_rows + tid * PITCH;
 #pragma unroll

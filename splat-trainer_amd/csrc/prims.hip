@@ -176,14 +176,30 @@ __global__ __launch_bounds__(RS_THREADS) void rs_hist_kernel(const uint32_t* __r
                                                              uint32_t num_blocks, const uint32_t* __restrict__ n_dev) {
   constexpr int BINS = 1 << BITS, PER = BINS / RS_THREADS;
   __shared__ uint32_t s_hist[BINS];
+  // The keys' addresses depend on the capacity alone, so the first four rounds' keys are requested next to the device
+  // count (an index behind the capacity reads the last allocated key; the flag masks it) and every later group of four
+  // while the one before it is counted: one memory wait in front of the atomics instead of count -> key -> key ...
+  // (rounds is 4 or 16, rs_rounds_for; any other count is covered by the guard on r + j below).
+  const uint32_t last = n - 1u;               // n >= 1 (sort_impl)
+  const uint32_t base = blockIdx.x * (uint32_t)(rounds * RS_THREADS) + threadIdx.x;
+  uint32_t k[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) k[j] = keys[min(base + j * RS_THREADS, last)];
   if (n_dev) n = min(n, *n_dev);              // n is a capacity: the element count is still on the device
 #pragma unroll
-  for (int k = 0; k < PER; ++k) s_hist[threadIdx.x + k * RS_THREADS] = 0;
+  for (int q = 0; q < PER; ++q) s_hist[threadIdx.x + q * RS_THREADS] = 0;
   __syncthreads();
-  const uint32_t base = blockIdx.x * (uint32_t)(rounds * RS_THREADS);
-  for (int r = 0; r < rounds; ++r) {
-    uint32_t idx = base + r * RS_THREADS + threadIdx.x;
-    if (idx < n) atomicAdd(&s_hist[(keys[idx] >> shift) & mask], 1u);
+  for (int r = 0; r < rounds; r += 4) {
+    uint32_t cur[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cur[j] = k[j];
+    if (r + 4 < rounds) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) k[j] = keys[min(base + (r + 4 + j) * RS_THREADS, last)];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (r + j < rounds && base + (r + j) * RS_THREADS < n) atomicAdd(&s_hist[(cur[j] >> shift) & mask], 1u);
   }
   __syncthreads();
 #pragma unroll
@@ -254,8 +270,31 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
                                                                 uint32_t num_blocks, const uint32_t* __restrict__ n_dev) {
   constexpr int TILE = ROUNDS * RS_THREADS, QUARTER = ROUNDS * 64;
   constexpr int BINS = 1 << BITS, PER = BINS / RS_THREADS;     // thread t owns the consecutive digits PER t .. PER t + PER - 1
+  // Everything this block reads from memory has an address that depends on the block, the thread and the capacity only:
+  // its elements (an index behind the capacity reads the last allocated element; the flag masks it), the digits' totals
+  // and the block's column of the offset table.  All of it is requested here, next to the device count, and waited for
+  // once -- not count -> elements -> (barrier) -> totals and offsets.
+  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
+  const uint32_t base = blockIdx.x * (uint32_t)TILE;
+  const uint32_t mine = base + (uint32_t)(wave * QUARTER + lane);   // round r: element mine + 64 r
+  const uint32_t last = n - 1u;                                      // n >= 1 (sort_impl)
+  uint32_t key[ROUNDS], val[ROUNDS], val2[TWO ? ROUNDS : 1];
+#pragma unroll
+  for (int r = 0; r < ROUNDS; ++r) {
+    const uint32_t idx = mine + 64u * r, at = min(idx, last);
+    key[r] = keys_in[at];
+    val[r] = vals_in ? vals_in[at] : idx;
+    if (TWO) val2[r] = vals2_in[at];
+  }
+  uint32_t t[PER], off[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const uint32_t d = PER * threadIdx.x + k;
+    t[k] = digit_total[d];
+    off[k] = offsets[(size_t)d * num_blocks + blockIdx.x];
+  }
   if (n_dev) n = min(n, *n_dev);
-  if (blockIdx.x * (uint32_t)TILE >= n) return;   // uniform over the block; its histogram row is all zeros
+  if (base >= n) return;                          // uniform over the block; its histogram row is all zeros
   __shared__ uint32_t s_start[BINS];          // first image slot of each digit
   __shared__ uint32_t s_goff[BINS];           // global slot of the digit's first element of this block
   __shared__ uint32_t s_slot[4][BINS];        // per wave: digit counts of its quarter, then its running image slot per digit
@@ -263,39 +302,31 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
   __shared__ uint32_t s_key[TILE];
   __shared__ uint32_t s_val[TILE];
   __shared__ uint32_t s_val2[TWO ? TILE : 1];
-  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
 #pragma unroll
   for (int w = 0; w < 4; ++w)
 #pragma unroll
     for (int k = 0; k < PER; ++k) s_slot[w][threadIdx.x + k * RS_THREADS] = 0;
   __syncthreads();
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
   const uint32_t block_n = min((uint32_t)TILE, n - base);
-  const uint32_t mine = base + (uint32_t)(wave * QUARTER + lane);   // round r: element mine + 64 r
-  uint32_t key[ROUNDS], val[ROUNDS], val2[TWO ? ROUNDS : 1];
 #pragma unroll
   for (int r = 0; r < ROUNDS; ++r) {
-    const uint32_t idx = mine + 64u * r;
-    key[r] = 0u; val[r] = 0u;
-    if (TWO) val2[r] = 0u;
-    if (idx < n) {
-      key[r] = keys_in[idx];
-      val[r] = vals_in ? vals_in[idx] : idx;
-      if (TWO) val2[r] = vals2_in[idx];
+    if (mine + 64u * r < n) {
       atomicAdd(&s_slot[wave][(key[r] >> shift) & mask], 1u);
+    } else {
+      key[r] = 0u; val[r] = 0u;
+      if (TWO) val2[r] = 0u;
     }
   }
   __syncthreads();
   {
     // block-wide exclusive scans over the digits: this block's counts -> first image slot of each digit (and of each
     // wave inside it); the digits' totals -> global base of each digit (+ its elements in earlier blocks = global slot)
-    uint32_t c[PER][4], t[PER], here = 0, here_t = 0;
+    uint32_t c[PER][4], here = 0, here_t = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const uint32_t d = PER * threadIdx.x + k;
 #pragma unroll
       for (int w = 0; w < 4; ++w) { c[k][w] = s_slot[w][d]; here += c[k][w]; }
-      t[k] = digit_total[d];
       here_t += t[k];
     }
     const uint32_t incl = gsr_wave_scan_incl_u32(here), incl_t = gsr_wave_scan_incl_u32(here_t);
@@ -309,7 +340,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
     for (int k = 0; k < PER; ++k) {
       const uint32_t d = PER * threadIdx.x + k;
       s_start[d] = at;
-      s_goff[d] = gbase + offsets[(size_t)d * num_blocks + blockIdx.x];
+      s_goff[d] = gbase + off[k];
 #pragma unroll
       for (int w = 0; w < 4; ++w) { s_slot[w][d] = at; at += c[k][w]; }
       gbase += t[k];

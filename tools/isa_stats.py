@@ -56,10 +56,16 @@ def classify(op: str) -> str:
 def kernels(asm: str) -> dict:
   """name -> dict(vgpr, sgpr, scratch, lds, body=[instruction lines])."""
   meta = {}
-  for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)(?=\n  - |\Z)", asm, flags=re.S):
-    name, blk = m.group(1), m.group(2)
+  # one metadata entry per kernel: "  - .agpr_count: ..." up to the next entry; its own keys sit at four spaces (the keys
+  # of its arguments deeper), in alphabetical order -- .group_segment_fixed_size in FRONT of .name
+  for m in re.finditer(r"^  - (\.\w+:.*?)(?=^  - |^\S|\Z)", asm, flags=re.S | re.M):
+    blk = "\n    " + m.group(1)
+    mm = re.search(r"\n    \.name:\s+(\S+)", blk)
+    if not mm:
+      continue
+    name = mm.group(1)
     def num(key):
-      mm = re.search(rf"\.{key}:\s+(\d+)", blk)
+      mm = re.search(rf"\n    \.{key}:\s+(\d+)", blk)
       return int(mm.group(1)) if mm else None
     if num("vgpr_count") is not None:
       meta[name] = dict(vgpr=num("vgpr_count"), sgpr=num("sgpr_count"), scratch=num("private_segment_fixed_size"),
@@ -144,6 +150,63 @@ def prologue_vmcnt_waits(body) -> int:
   raise ValueError("no loop in the kernel")
 
 
+def waits_to_first_store(body) -> dict:
+  """The per-splat and sort kernels: memory round trips from the kernel's entry to its first global store, in layout
+  order.  A wait counts as a trip when at least one load of its kind went out since the last counted one (several partial
+  waits on one batch of loads are one trip): dict(vmem_waits, smem_waits, vmem_loads) -- vector loads before the store."""
+  vm = sm = loads = 0
+  vm_open = sm_open = False
+  for ln in body:
+    s = ln.strip()
+    if not s or s.startswith((";", ".")):
+      continue
+    op = s.split()[0]
+    if op.startswith(("global_store", "buffer_store", "flat_store")):
+      return dict(vmem_waits=vm, smem_waits=sm, vmem_loads=loads)
+    c = classify(op)
+    if c == "vmem" and "_load" in op:
+      vm_open, loads = True, loads + 1
+    elif c == "smem":
+      sm_open = True
+    elif op == "s_waitcnt":
+      if "vmcnt" in s and vm_open:
+        vm, vm_open = vm + 1, False
+      if "lgkmcnt" in s and sm_open:
+        sm, sm_open = sm + 1, False
+  raise ValueError("no global store in the kernel")
+
+
+# the kernels of a frame whose loads go out when their address is known (tests/test_isa_budget_frame_waits.py):
+# label -> (source file, needles of the mangled name)
+FRAME_WAIT_KERNELS = {
+    "cull_count": ("geometry.hip", ("cull_count_kernel",)),
+    "cull_write": ("geometry.hip", ("cull_write_kernel",)),
+    "project_sh_fwd_K16": ("geometry.hip", ("project_sh_fwd_kernelILi16ELb1E",)),
+    "project_sh_fwd_K9": ("geometry.hip", ("project_sh_fwd_kernelILi9ELb1E",)),
+    "project_sh_fwd_K9_nojac": ("geometry.hip", ("project_sh_fwd_kernelILi9ELb0E",)),
+    "project_sh_fwd_K4": ("geometry.hip", ("project_sh_fwd_kernelILi4ELb1E",)),
+    "project_sh_fwd_K1": ("geometry.hip", ("project_sh_fwd_kernelILi1ELb1E",)),
+    "rs_hist_9": ("prims.hip", ("rs_hist_kernelILi9E",)),
+    "rs_hist_8": ("prims.hip", ("rs_hist_kernelILi8E",)),
+    "rs_scatter_1v_4_9": ("prims.hip", ("rs_scatter_kernelILb0ELi4ELi9E",)),
+    "rs_scatter_1v_4_8": ("prims.hip", ("rs_scatter_kernelILb0ELi4ELi8E",)),
+    "rs_scatter_2v_4_8": ("prims.hip", ("rs_scatter_kernelILb1ELi4ELi8E",)),
+    "rs_scatter_2v_16_8": ("prims.hip", ("rs_scatter_kernelILb1ELi16ELi8E",)),
+    "tile_count": ("binning.hip", ("tile_count_kernel",)),
+    "reduce_grad": ("binning.hip", ("18reduce_grad_kernel",)),
+}
+
+
+def frame_waits() -> dict:
+  out = {}
+  for label, (source, needles) in FRAME_WAIT_KERNELS.items():
+    meta = kernels(compile_isa(source))
+    k = meta[find(meta, *needles)]
+    out[label] = dict(waits_to_first_store(k["body"]), vgpr=k["vgpr"], sgpr=k["sgpr"], lds_bytes=k["lds"],
+                      scratch_bytes=k["scratch"])
+  return out
+
+
 def find(meta: dict, *needles: str) -> str:
   for name in meta:
     if all(n in name for n in needles):
@@ -170,6 +233,8 @@ def audit() -> dict:
       "K6_fwd_C3_vis": dict(four_pair_loops=four_pair_loops(meta[find(meta, *picks["K6_fwd_C3_vis"])]["body"])),
       "K6_segC_C3_vis": dict(four_pair_loops=four_pair_loops(meta[find(meta, *picks["K6_segC_C3_vis"])]["body"])),
       "K7_bwd_C3": dict(prologue_vmcnt_waits=prologue_vmcnt_waits(meta[find(meta, *picks["K7_bwd_C3"])]["body"]))}
+  # where the per-splat and sort kernels of a frame wait for memory (tests/test_isa_budget_frame_waits.py)
+  out["frame_waits"] = frame_waits()
   out["all_kernels"] = {n: dict(vgpr=k["vgpr"], scratch_bytes=k["scratch"]) for n, k in meta.items()}
   return out
 
@@ -180,11 +245,14 @@ if __name__ == "__main__":
     print(json.dumps(a))
   else:
     for label, k in a.items():
-      if label in ("all_kernels", "composite_waits"):
+      if label in ("all_kernels", "composite_waits", "frame_waits"):
         continue
       print(f"{label:18s} vgpr {k['vgpr']:3d}  sgpr {k['sgpr']:3d}  scratch {k['scratch_bytes']} B  lds {k['lds_bytes']} B  "
             f"s_barrier {k['s_barrier']}  mfma {k['mfma']}  loop mix {k['static_loop_mix']}")
     for label, w in a["composite_waits"].items():
       print(f"{label:18s} waits {w}")
+    for label, w in a["frame_waits"].items():
+      print(f"{label:18s} to first store: vmem waits {w['vmem_waits']} ({w['vmem_loads']} loads)  smem waits {w['smem_waits']}  "
+            f"vgpr {w['vgpr']}  sgpr {w['sgpr']}  lds {w['lds_bytes']} B  scratch {w['scratch_bytes']} B")
     worst = max(a["all_kernels"].values(), key=lambda k: k["scratch_bytes"])
     print(f"{len(a['all_kernels'])} kernels in composite.hip; max scratch {worst['scratch_bytes']} B")
