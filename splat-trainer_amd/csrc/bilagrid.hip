@@ -16,7 +16,7 @@
 #include "gsr_device.h"
 #include "gsr_dpp_reduce.h"
 #include "gsr_bilagrid.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -25,8 +25,6 @@ constexpr int BG_LW = 1;                                  // levels per backward
 constexpr int BG_ACC = BG_LW * 4 * GSR_BG_CH;             // 48 accumulators per thread
 constexpr int BG_TARGET_WORKGROUPS = 1024;                // 4 per CU
 constexpr int BG_TV_MAX_BLOCKS = 1024;
-
-inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 struct BgShape {
   int L, GH, GW, H, W, S;
@@ -281,7 +279,7 @@ size_t gsr_bilagrid_workspace_bytes(int32_t L, int32_t GH, int32_t GW) {
 
 int gsr_bilagrid_slice_forward(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, int64_t k,
                                const float* rgb, int32_t H, int32_t W, float* out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!grids || !rgb || !out || !bg_shape_ok(L, GH, GW) || k < 0 || k >= N || !bg_image_ok(H, W))
     return GSR_ERR_INVALID_ARGUMENT;
   const BgShape sh = bg_shape(L, GH, GW, H, W);
@@ -295,7 +293,7 @@ int gsr_bilagrid_slice_forward(const float* grids, int64_t N, int32_t L, int32_t
 int gsr_bilagrid_slice_backward(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, int64_t k,
                                 const float* rgb, int32_t H, int32_t W, const float* d_out, float* d_rgb, float* d_grids,
                                 void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!grids || !rgb || !d_out || !bg_shape_ok(L, GH, GW) || k < 0 || k >= N || !bg_image_ok(H, W))
     return GSR_ERR_INVALID_ARGUMENT;
   if (!d_rgb && !d_grids) return GSR_OK;
@@ -316,7 +314,7 @@ int gsr_bilagrid_slice_backward(const float* grids, int64_t N, int32_t L, int32_
 
 int gsr_bilagrid_tv(const float* grids, int64_t N, int32_t L, int32_t GH, int32_t GW, float weight, float* tv_out,
                     float* d_grids, int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!grids || !tv_out || N < 1 || !bg_shape_ok(L, GH, GW)) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < sizeof(float) * BG_TV_MAX_BLOCKS) return GSR_ERR_WORKSPACE_TOO_SMALL;
   unsigned bx, by;

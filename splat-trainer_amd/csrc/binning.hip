@@ -8,7 +8,7 @@
 // The per-tile test is exact for the ellipse {d^T conic d <= qmax} against the rectangles of pixel centres of the
 // tile's two halves, with qmax shrunk for faint splats (alpha can only reach 1/255 inside 2 ln(255 opacity)).
 #include "gsr_device.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -17,7 +17,6 @@ inline GsrRasterParams to_params(const GsrRasterParamsC* c) {
   __builtin_memcpy(&rp, c, sizeof(rp));
   return rp;
 }
-inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 __global__ __launch_bounds__(256) void depth_keys_kernel(const float* __restrict__ depth, int64_t M,
                                                          uint32_t* __restrict__ keys, uint32_t bias, uint32_t max_key) {
@@ -551,7 +550,7 @@ int gsr_depth_key_range(float near_plane, float far_plane, uint32_t* bias_out, u
 }
 
 int gsr_depth_keys(const float* depth, int64_t M, uint32_t bias, uint32_t max_key, uint32_t* keys_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!depth || !keys_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -563,12 +562,12 @@ int gsr_depth_keys(const float* depth, int64_t M, uint32_t bias, uint32_t max_ke
 int gsr_tile_count(const float* rows, const uint32_t* order, int64_t M, int32_t W, int32_t H,
                    const GsrRasterParamsC* params_host, uint32_t* count_out, uint32_t* tile_hits_out,
                    const uint32_t* M_dev, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || M >= (1ll << 30) || !params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!rows || !order || !count_out || !tile_hits_out) return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16;
+  const auto [tx, ty, num_tiles] = gsr_tiles(W, H);
   if (tx > 0xFFFF || ty > 0xFFFF) return GSR_ERR_UNSUPPORTED;      // the hit records hold 16-bit tile coordinates
   tile_count_kernel<<<grid_for(M, 256), 256, 0, stream>>>(rows, order, M, tx, ty, to_params(params_host), count_out,
                                                          reinterpret_cast<TileHits*>(tile_hits_out), M_dev, nullptr);
@@ -584,14 +583,14 @@ int gsr_tile_count_offsets(const float* rows, const uint32_t* order, int64_t M, 
                            const GsrRasterParamsC* params_host, uint32_t* count_out, uint32_t* tile_hits_out,
                            const uint32_t* M_dev, uint32_t* offsets_out, uint32_t* total_dev, uint32_t* overflow_flag,
                            void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || M > GSR_TILE_COUNT_OFFSETS_MAX || !params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16) return GSR_ERR_UNSUPPORTED;
   if (!total_dev || !overflow_flag) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) { hipMemsetAsync(total_dev, 0, sizeof(uint32_t), stream); return GSR_OK; }
   if (!rows || !order || !count_out || !tile_hits_out || !offsets_out) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_tile_count_offsets_workspace_bytes(M)) return GSR_ERR_WORKSPACE_TOO_SMALL;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16;
+  const auto [tx, ty, num_tiles] = gsr_tiles(W, H);
   if (tx > 0xFFFF || ty > 0xFFFF) return GSR_ERR_UNSUPPORTED;
   uint32_t* sums = reinterpret_cast<uint32_t*>(workspace);
   tile_count_kernel<<<grid_for(M, 256), 256, 0, stream>>>(rows, order, M, tx, ty, to_params(params_host), count_out,
@@ -606,13 +605,13 @@ int gsr_tile_count_offsets(const float* rows, const uint32_t* order, int64_t M, 
 int gsr_tile_emit(const float* rows, const uint32_t* order, const uint32_t* offsets, const uint32_t* tile_hits, int64_t M,
                   int32_t W, int32_t H, const GsrRasterParamsC* params_host, uint32_t* keys_out, uint32_t* inst2splat_out,
                   int64_t capacity, const uint32_t* M_dev, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || M >= (1ll << 30) || !params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (capacity < 0 || capacity > 0x7FFFFFFFll) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!rows || !order || !offsets || !tile_hits || !keys_out || !inst2splat_out) return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16;
+  const auto [tx, ty, num_tiles] = gsr_tiles(W, H);
   tile_emit_kernel<<<grid_for(M, 256), 256, 0, stream>>>(rows, order, offsets, reinterpret_cast<const TileHits*>(tile_hits),
                                                         M, tx, ty, to_params(params_host), keys_out, inst2splat_out,
                                                         (uint32_t)capacity, M_dev);
@@ -622,7 +621,7 @@ int gsr_tile_emit(const float* rows, const uint32_t* order, const uint32_t* offs
 
 int gsr_tile_ranges(const uint32_t* sorted_keys, int64_t O, int32_t num_tiles, uint32_t* tile_range,
                     const uint32_t* O_dev, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (O < 0 || num_tiles <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (O == 0) return GSR_OK;
   if (!sorted_keys || !tile_range) return GSR_ERR_INVALID_ARGUMENT;
@@ -634,7 +633,7 @@ int gsr_tile_ranges(const uint32_t* sorted_keys, int64_t O, int32_t num_tiles, u
 int gsr_reduce_visibility(const float* vis_partial, const uint32_t* offsets, const uint32_t* count,
                           const uint32_t* order, int64_t M, float* visibility_out, int64_t capacity,
                           const uint32_t* M_dev, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || capacity < 0 || capacity > 0x7FFFFFFFll) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!offsets || !count || !visibility_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -646,7 +645,7 @@ int gsr_reduce_visibility(const float* vis_partial, const uint32_t* offsets, con
 
 int gsr_reduce_gradients(const float* partial, const float* vis_partial, const uint32_t* offsets,
                          const uint32_t* count, const uint32_t* order, int64_t M, float* grad_rows_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!offsets || !count || !grad_rows_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -658,15 +657,16 @@ int gsr_reduce_gradients(const float* partial, const float* vis_partial, const u
 int gsr_reduce_gradients_wide(const float* partial, const float* vis_partial, const uint32_t* offsets,
                               const uint32_t* count, const uint32_t* order, int64_t M, int32_t C, float* grad_rows_out,
                               float* d_features_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!offsets || !count || !grad_rows_out || !d_features_out || !vis_partial) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  if (C <= 4) reduce_grad_wide_kernel<4><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
-  else if (C <= 8) reduce_grad_wide_kernel<8><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
-  else reduce_grad_wide_kernel<16><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C, grad_rows_out, d_features_out);
+  gsr_pick_wide(C, [&](auto cw) {
+    reduce_grad_wide_kernel<decltype(cw)::value><<<g, 256, 0, stream>>>(partial, vis_partial, offsets, count, order, M, C,
+                                                                       grad_rows_out, d_features_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -674,16 +674,16 @@ int gsr_reduce_gradients_wide(const float* partial, const float* vis_partial, co
 int gsr_unpack_grad_rows(const float* rows, const float* grad_rows, int64_t M, int32_t C, float* d_gaussians2d,
                          float* d_features, float* prune_cost_out, float* split_score_out, float* visibility_out,
                          void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (C < 1 || C > (d_features ? 3 : GSR_MAX_FEATURES)) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!rows || !grad_rows || !d_gaussians2d) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  if (!d_features) unpack_rows_kernel<0><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, nullptr, prune_cost_out, split_score_out, visibility_out);
-  else if (C == 1) unpack_rows_kernel<1><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
-  else if (C == 2) unpack_rows_kernel<2><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
-  else unpack_rows_kernel<3><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features, prune_cost_out, split_score_out, visibility_out);
+  gsr_pick<0, 1, 2, 3>(d_features ? C : 0, [&](auto c) {       // 0: no feature gradient is written
+    unpack_rows_kernel<decltype(c)::value><<<g, 256, 0, stream>>>(rows, grad_rows, M, d_gaussians2d, d_features,
+                                                                 prune_cost_out, split_score_out, visibility_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

@@ -9,13 +9,11 @@
 // An index outside its table reads row 0 and ORs 1 into the caller's status word (an integer atomic, on that path only).
 #include "gsr_device.h"
 #include "gsr_camera_table.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
 constexpr int PT_BLOCK = 256;
-
-inline unsigned grid_for(int64_t n, int64_t block) { return (unsigned)((n + block - 1) / block); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -99,7 +97,7 @@ extern "C" {
 int gsr_pose_forward(const float* q_left, const float* t_left, int64_t A_left, const int64_t* idx_left,
                      const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
                      float* T_out, int32_t* status, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   const int rc = check_tables(q_left, t_left, A_left, idx_left, q_right, t_right, A_right, idx_right, B, status);
   if (rc != GSR_OK) return rc;
   if (B == 0) return GSR_OK;
@@ -114,7 +112,7 @@ int gsr_pose_backward(const float* q_left, const float* t_left, int64_t A_left, 
                       const float* q_right, const float* t_right, int64_t A_right, const int64_t* idx_right, int64_t B,
                       const float* d_T, float* d_q_left, float* d_t_left, float* d_q_right, float* d_t_right,
                       int32_t* status, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   const int rc = check_tables(q_left, t_left, A_left, idx_left, q_right, t_right, A_right, idx_right, B, status);
   if (rc != GSR_OK) return rc;
   if ((B > 0 && !d_T) || !d_q_left != !d_t_left || !d_q_right != !d_t_right || (!q_right && d_q_right) ||

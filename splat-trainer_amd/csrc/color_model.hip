@@ -26,7 +26,7 @@
 #include <type_traits>
 
 #include "gsr_color.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -43,8 +43,6 @@ constexpr int CM_MAX_FEATURES = 64;
 
 // forces compile-time evaluation of a constexpr offset
 #define CM_C(x) (std::integral_constant<int, (x)>::value)
-
-inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 // Packed layers, in this order: 0 base.0, 1 base.1, 2 base.out, 3 encode, 4 dir.0, 5 dir.1, 6 dir.out (1 and 5 only for
 // L = 2).  T = output tiles of 16, KS = input blocks of 32.  KF = input blocks of the F features, KSH = of the SH basis.
@@ -860,7 +858,7 @@ int cm_backward_t(const CmCall& c) {
     cm_backward_kernel<L, KF, S><<<(unsigned)wg, CM_BLOCK, 0, c.stream>>>(
         frags, bias, c.pf, c.pos, c.cam, c.glo, c.M, c.m->P, c.m->P + c.m->G, c.d_diffuse, c.d_specular, want_cam, c.d_pf,
         slots);
-    if (hipGetLastError() != hipSuccess) return GSR_ERR_LAUNCH_FAILED;
+    GSR_CHECK_LAUNCH();
   }
   const CmDims d = cm_dims(*c.m);
   CmOut o{};
@@ -879,27 +877,15 @@ int cm_backward_t(const CmCall& c) {
   return hipGetLastError() == hipSuccess ? GSR_OK : GSR_ERR_LAUNCH_FAILED;
 }
 
-// dispatch on (L, KF, S)
-template <template <int, int, int> class Fn, typename R, typename... A>
-R cm_dispatch(const GsrColorModel* m, A... args) {
-  const int KF = m->P + m->G <= 32 ? 1 : 2;
-#define CM_CASE(L_, KF_, S_) \
-  if (m->L == L_ && KF == KF_ && m->S == S_) return Fn<L_, KF_, S_>::run(args...);
-#define CM_CASES_S(L_, KF_) CM_CASE(L_, KF_, 2) CM_CASE(L_, KF_, 3) CM_CASE(L_, KF_, 4) CM_CASE(L_, KF_, 5)
-  CM_CASES_S(1, 1) CM_CASES_S(1, 2) CM_CASES_S(2, 1) CM_CASES_S(2, 2)
-#undef CM_CASES_S
-#undef CM_CASE
-  return R{};
+// dispatch on (L, KF, S): f(l, kf, s) gets the model's shape as three std::integral_constant
+template <class F>
+void cm_dispatch(const GsrColorModel* m, F&& f) {
+  gsr_pick<1, 2>(m->L, [&](auto l) {
+    gsr_pick<1, 2>(m->P + m->G <= 32 ? 1 : 2, [&](auto kf) {
+      gsr_pick<2, 3, 4, 5>(m->S, [&](auto s) { f(l, kf, s); });
+    });
+  });
 }
-
-template <int L, int KF, int S>
-struct CmFwdFn { static int run(const CmCall& c) { return cm_forward_t<L, KF, S>(c); } };
-template <int L, int KF, int S>
-struct CmBwdFn { static int run(const CmCall& c) { return cm_backward_t<L, KF, S>(c); } };
-template <int L, int KF, int S>
-struct CmPackBytesFn { static size_t run() { return (size_t)CmShape<L, KF, S>::PACK_BYTES; } };
-template <int L, int KF, int S>
-struct CmBwdWsFn { static size_t run(int64_t M) { return cm_bwd_ws_t<L, KF, S>(M); } };
 
 }  // namespace
 
@@ -917,12 +903,20 @@ int gsr_color_supported(const GsrColorModel* m) { return cm_supported(m) ? GSR_O
 
 size_t gsr_color_forward_workspace_bytes(const GsrColorModel* m) {
   if (!cm_supported(m)) return 0;
-  return cm_dispatch<CmPackBytesFn, size_t>(m);
+  size_t bytes = 0;
+  cm_dispatch(m, [&](auto l, auto kf, auto s) {
+    bytes = (size_t)CmShape<decltype(l)::value, decltype(kf)::value, decltype(s)::value>::PACK_BYTES;
+  });
+  return bytes;
 }
 
 size_t gsr_color_backward_workspace_bytes(const GsrColorModel* m, int64_t M) {
   if (!cm_supported(m) || M < 0) return 0;
-  return cm_dispatch<CmBwdWsFn, size_t>(m, M);
+  size_t bytes = 0;
+  cm_dispatch(m, [&](auto l, auto kf, auto s) {
+    bytes = cm_bwd_ws_t<decltype(l)::value, decltype(kf)::value, decltype(s)::value>(M);
+  });
+  return bytes;
 }
 
 int gsr_color_forward(const GsrColorModel* m, const float* point_features, const float* positions, const float* cam_pos,
@@ -932,8 +926,12 @@ int gsr_color_forward(const GsrColorModel* m, const float* point_features, const
   if (M < 0 || !cm_params_present(m) || !cam_pos || (m->G > 0 && !glo_feature) || !workspace) return GSR_ERR_INVALID_ARGUMENT;
   if (M > 0 && ((m->P > 0 && !point_features) || !positions || !diffuse_out || !specular_out)) return GSR_ERR_INVALID_ARGUMENT;
   CmCall c{m, point_features, positions, cam_pos, glo_feature, M, diffuse_out, specular_out, nullptr, nullptr, nullptr,
-           nullptr, workspace, workspace_bytes, (hipStream_t)stream};
-  return cm_dispatch<CmFwdFn, int>(m, c);
+           nullptr, workspace, workspace_bytes, gsr_stream(stream)};
+  int rc = GSR_OK;
+  cm_dispatch(m, [&](auto l, auto kf, auto s) {
+    rc = cm_forward_t<decltype(l)::value, decltype(kf)::value, decltype(s)::value>(c);
+  });
+  return rc;
 }
 
 int gsr_color_backward(const GsrColorModel* m, const float* point_features, const float* positions, const float* cam_pos,
@@ -950,8 +948,12 @@ int gsr_color_backward(const GsrColorModel* m, const float* point_features, cons
   }
   if (M > 0 && ((m->P > 0 && (!point_features || !d_point_features)) || !positions)) return GSR_ERR_INVALID_ARGUMENT;
   CmCall c{m, point_features, positions, cam_pos, glo_feature, M, nullptr, nullptr, d_diffuse, d_specular,
-           d_point_features, grads, workspace, workspace_bytes, (hipStream_t)stream};
-  return cm_dispatch<CmBwdFn, int>(m, c);
+           d_point_features, grads, workspace, workspace_bytes, gsr_stream(stream)};
+  int rc = GSR_OK;
+  cm_dispatch(m, [&](auto l, auto kf, auto s) {
+    rc = cm_backward_t<decltype(l)::value, decltype(kf)::value, decltype(s)::value>(c);
+  });
+  return rc;
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@
 // MFMA is deliberately not used: there is no dense contraction on this path.
 #include "gsr_device.h"
 #include "gsr_dpp_reduce.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -1071,12 +1071,12 @@ int gsr_segment_plan_wide(const uint32_t* tile_range, int32_t num_tiles, int32_t
                           int32_t needs_grad, int32_t wide, int64_t O, const uint32_t* O_dev, int64_t capacity,
                           int64_t heavy_capacity, uint32_t* tile_seg_out, uint32_t* seg_desc_out, uint32_t* seg_total_out,
                           uint32_t* tile_order_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (num_tiles <= 0 || capacity <= 0 || capacity > 0x7fffffffll || (O < 0 && !O_dev)) return GSR_ERR_INVALID_ARGUMENT;
   if (heavy_capacity < 0 || heavy_capacity > capacity) return GSR_ERR_INVALID_ARGUMENT;
   if (seg_pairs_cfg > 0 && heavy_min_cfg > 0 && heavy_min_cfg < seg_pairs_cfg) return GSR_ERR_INVALID_ARGUMENT;
   if (!tile_range || !tile_seg_out || !seg_desc_out || !seg_total_out) return GSR_ERR_INVALID_ARGUMENT;
-  segment_plan_kernel<<<(num_tiles + 255) / 256, 256, 0, stream>>>(tile_range, num_tiles, seg_pairs_cfg, heavy_min_cfg,
+  segment_plan_kernel<<<grid_for(num_tiles, 256), 256, 0, stream>>>(tile_range, num_tiles, seg_pairs_cfg, heavy_min_cfg,
                                                                   needs_grad, wide, O, O_dev, (uint32_t)capacity,
                                                                   (uint32_t)heavy_capacity, tile_seg_out, seg_desc_out,
                                                                   seg_total_out, tile_order_out);
@@ -1089,11 +1089,12 @@ int gsr_composite_forward(const float* rec, const uint32_t* sorted_rank, const u
                           const GsrRasterParamsC* params_host, float* image_out, float* final_T_out, int32_t* last_out,
                           float* median_depth_out, float* vis_partial_out, float* pair_vis_out,
                           const GsrSegmentsC* segments_host, int32_t prefetch_rows, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16 || C < 1 || C > 3) return GSR_ERR_UNSUPPORTED;
   if (!tile_range || !image_out || !final_T_out || !last_out) return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16, nt = tx * ty;
+  const GsrTiles tiles = gsr_tiles(W, H);
+  const int tx = tiles.tx, nt = (int)tiles.n;
   const GsrRasterParams rp = to_params(params_host);
   const bool vis = vis_partial_out != nullptr, med = median_depth_out != nullptr;
   if (vis && !pair_vis_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -1101,40 +1102,25 @@ int gsr_composite_forward(const float* rec, const uint32_t* sorted_rank, const u
   const SegDev seg = to_segdev(segments_host);
   const int cap = segments_host ? (int)segments_host->heavy_capacity : 0;   // blocks of the heavy-tile passes
   const int tb = seg.tile_order ? 8 * gsr_tile_band_stride(nt) : nt;   // tile blocks (ordered form: a band's capacity per XCD)
-#define GSR_LAUNCH_TILES(CC, VV, MM, PP)                                                                               \
-  composite_fwd_kernel<CC, VV, MM, PP><<<tb + cap, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, tile_range, W, H,   \
-                                                                    tx, nt, rp, image_out, final_T_out, last_out,      \
-                                                                    median_depth_out, vis_partial_out, pair_vis_out,   \
-                                                                    seg, tb)
-#define GSR_LAUNCH_FWD2(CC, VV, MM, PP)                                                                                \
-  do {                                                                                                                 \
-    GSR_LAUNCH_TILES(CC, VV, MM, PP);                                                                                  \
-    if (cap) {                                                                                                         \
-      seg_composite_kernel<CC, VV, MM, PP><<<cap, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, tile_range, W, H,    \
-                                                                   tx, nt, rp, vis_partial_out, pair_vis_out, seg);    \
-      seg_combine_kernel<CC, MM><<<nt, 64, 0, stream>>>(W, H, tx, nt, image_out, final_T_out, last_out,                \
-                                                        median_depth_out, seg);                                        \
-    }                                                                                                                  \
-  } while (0)
-#define GSR_LAUNCH_FWD(CC, VV, MM)                 \
-  do {                                             \
-    if (prefetch_rows) GSR_LAUNCH_FWD2(CC, VV, MM, true); \
-    else GSR_LAUNCH_FWD2(CC, VV, MM, false);       \
-  } while (0)
-#define GSR_DISPATCH_FWD(CC)                                       \
-  do {                                                             \
-    if (vis && med) GSR_LAUNCH_FWD(CC, true, true);                \
-    else if (vis) GSR_LAUNCH_FWD(CC, true, false);                 \
-    else if (med) GSR_LAUNCH_FWD(CC, false, true);                 \
-    else GSR_LAUNCH_FWD(CC, false, false);                         \
-  } while (0)
-  if (C == 1) GSR_DISPATCH_FWD(1);
-  else if (C == 2) GSR_DISPATCH_FWD(2);
-  else GSR_DISPATCH_FWD(3);
-#undef GSR_DISPATCH_FWD
-#undef GSR_LAUNCH_FWD
-#undef GSR_LAUNCH_FWD2
-#undef GSR_LAUNCH_TILES
+  gsr_pick_channels(C, [&](auto c) {
+    gsr_pick_bool(vis, [&](auto v) {
+      gsr_pick_bool(med, [&](auto m) {
+        gsr_pick_bool(prefetch_rows != 0, [&](auto pf) {
+          constexpr int CC = decltype(c)::value;
+          constexpr bool VV = decltype(v)::value, MM = decltype(m)::value, PP = decltype(pf)::value;
+          composite_fwd_kernel<CC, VV, MM, PP><<<tb + cap, 64, 0, stream>>>(
+              rec, sorted_rank, sorted_inst, tile_range, W, H, tx, nt, rp, image_out, final_T_out, last_out,
+              median_depth_out, vis_partial_out, pair_vis_out, seg, tb);
+          if (cap) {
+            seg_composite_kernel<CC, VV, MM, PP><<<cap, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, tile_range, W, H, tx,
+                                                                         nt, rp, vis_partial_out, pair_vis_out, seg);
+            seg_combine_kernel<CC, MM><<<nt, 64, 0, stream>>>(W, H, tx, nt, image_out, final_T_out, last_out,
+                                                              median_depth_out, seg);
+          }
+        });
+      });
+    });
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1144,12 +1130,13 @@ int gsr_composite_backward(const float* rec, const uint32_t* sorted_rank, const 
                            const GsrRasterParamsC* params_host, const float* final_T, const int32_t* last,
                            const float* dL_dimage, const float* image, float* partial_out,
                            const GsrSegmentsC* segments_host, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16 || C < 1 || C > 3) return GSR_ERR_UNSUPPORTED;
   if (!tile_range || !final_T || !last || !dL_dimage) return GSR_ERR_INVALID_ARGUMENT;
   if (!seg_ok(segments_host, false) || (segments_host && !image)) return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16, nt = tx * ty;
+  const GsrTiles tiles = gsr_tiles(W, H);
+  const int tx = tiles.tx, nt = (int)tiles.n;
   const GsrRasterParams rp = to_params(params_host);
   const SegDev seg = to_segdev(segments_host);
   // segment blocks: rounded up to the XCD grouping of gsr_xcd_group_remap (blocks past seg_total return)
@@ -1157,9 +1144,11 @@ int gsr_composite_backward(const float* rec, const uint32_t* sorted_rank, const 
   const uint32_t seg_blocks = segments_host ? (uint32_t)((segments_host->capacity + seg_round - 1) / seg_round * seg_round) : 0u;
   const uint32_t seg_cap = (uint32_t)(segments_host ? segments_host->capacity : 0);
   const int grid = 8 * gsr_tile_band_stride(nt) + (int)seg_blocks;
-  if (C == 1) composite_bwd_kernel<1><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
-  else if (C == 2) composite_bwd_kernel<2><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
-  else composite_bwd_kernel<3><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W, H, tx, nt, rp, final_T, last, dL_dimage, image, partial_out, seg, seg_cap, seg_blocks);
+  gsr_pick_channels(C, [&](auto c) {
+    composite_bwd_kernel<decltype(c)::value><<<grid, 64, 0, stream>>>(rec, sorted_rank, sorted_inst, pair_vis, tile_range, W,
+                                                                     H, tx, nt, rp, final_T, last, dL_dimage, image,
+                                                                     partial_out, seg, seg_cap, seg_blocks);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

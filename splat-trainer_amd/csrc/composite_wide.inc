@@ -588,8 +588,6 @@ void composite_bwd_wide(const float* __restrict__ rec, const float* __restrict__
   }
 }
 
-inline int wide_width(int C) { return C <= 4 ? 4 : (C <= 8 ? 8 : 16); }
-
 }  // namespace
 
 extern "C" {
@@ -599,50 +597,43 @@ int gsr_composite_forward_wide_seg(const float* rows, const float* feat_rows, co
                                    int32_t C, const GsrRasterParamsC* params_host, float* image_out, float* final_T_out,
                                    int32_t* last_out, float* median_depth_out, float* vis_partial_out,
                                    float* pair_vis_out, const GsrSegmentsC* segments_host, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16 || C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
   if (!tile_range || !image_out || !final_T_out || !last_out) return GSR_ERR_INVALID_ARGUMENT;
   const bool vis = vis_partial_out != nullptr, med = median_depth_out != nullptr;
   if (vis && !pair_vis_out) return GSR_ERR_INVALID_ARGUMENT;
   if (!seg_ok(segments_host, med) || (segments_host && !segments_host->seg_col)) return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16, nt = tx * ty;
+  const GsrTiles tiles = gsr_tiles(W, H);
+  const int tx = tiles.tx, nt = (int)tiles.n;
   const GsrRasterParams rp = to_params(params_host);
   const SegDev seg = to_segdev(segments_host);
   float4* seg_col = segments_host ? reinterpret_cast<float4*>(segments_host->seg_col) : nullptr;
   const int cap = segments_host ? (int)segments_host->heavy_capacity : 0;   // blocks of the heavy-tile passes
-#define GSR_LAUNCH_FWD_WIDE(CW, VV, MM)                                                                                   \
-  do {                                                                                                                    \
-    if (!segments_host) {                                                                                                 \
-      composite_fwd_wide<CW, VV, MM><<<nt, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W, H, \
-                                                            C, tx, nt, rp, image_out, final_T_out, last_out,              \
-                                                            median_depth_out, vis_partial_out, pair_vis_out);             \
-    } else {                                                                                                              \
-      wide_ckpt_fwd<CW, VV, MM><<<nt + cap, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W,   \
-                                                             H, C, tx, nt, rp, image_out, final_T_out, last_out,          \
-                                                             median_depth_out, vis_partial_out, pair_vis_out, seg,        \
-                                                             seg_col);                                                    \
-      if (cap) {                                                                                                          \
-        wide_seg_fwd<CW, VV, MM><<<cap, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W, H,    \
-                                                         tx, nt, rp, vis_partial_out, pair_vis_out, seg, seg_col);        \
-        wide_seg_combine<CW, MM><<<nt, 64, 0, stream>>>(W, H, C, tx, image_out, final_T_out, last_out,                    \
-                                                        median_depth_out, seg, seg_col);                                  \
-      }                                                                                                                   \
-    }                                                                                                                     \
-  } while (0)
-#define GSR_DISPATCH_FWD_WIDE(CW)                                  \
-  do {                                                             \
-    if (vis && med) GSR_LAUNCH_FWD_WIDE(CW, true, true);           \
-    else if (vis) GSR_LAUNCH_FWD_WIDE(CW, true, false);            \
-    else if (med) GSR_LAUNCH_FWD_WIDE(CW, false, true);            \
-    else GSR_LAUNCH_FWD_WIDE(CW, false, false);                    \
-  } while (0)
-  const int cw = wide_width(C);
-  if (cw == 4) GSR_DISPATCH_FWD_WIDE(4);
-  else if (cw == 8) GSR_DISPATCH_FWD_WIDE(8);
-  else GSR_DISPATCH_FWD_WIDE(16);
-#undef GSR_DISPATCH_FWD_WIDE
-#undef GSR_LAUNCH_FWD_WIDE
+  gsr_pick_wide(C, [&](auto cw) {
+    gsr_pick_bool(vis, [&](auto v) {
+      gsr_pick_bool(med, [&](auto m) {
+        constexpr int CW = decltype(cw)::value;
+        constexpr bool VV = decltype(v)::value, MM = decltype(m)::value;
+        if (!segments_host) {
+          composite_fwd_wide<CW, VV, MM><<<nt, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W, H,
+                                                                C, tx, nt, rp, image_out, final_T_out, last_out,
+                                                                median_depth_out, vis_partial_out, pair_vis_out);
+          return;
+        }
+        wide_ckpt_fwd<CW, VV, MM><<<nt + cap, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W, H,
+                                                               C, tx, nt, rp, image_out, final_T_out, last_out,
+                                                               median_depth_out, vis_partial_out, pair_vis_out, seg,
+                                                               seg_col);
+        if (cap) {
+          wide_seg_fwd<CW, VV, MM><<<cap, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, tile_range, W, H, tx,
+                                                           nt, rp, vis_partial_out, pair_vis_out, seg, seg_col);
+          wide_seg_combine<CW, MM><<<nt, 64, 0, stream>>>(W, H, C, tx, image_out, final_T_out, last_out, median_depth_out,
+                                                          seg, seg_col);
+        }
+      });
+    });
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -662,13 +653,14 @@ int gsr_composite_backward_wide_seg(const float* rows, const float* feat_rows, c
                                     int32_t W, int32_t H, int32_t C, const GsrRasterParamsC* params_host,
                                     const float* final_T, const int32_t* last, const float* dL_dimage, const float* image,
                                     float* partial_out, const GsrSegmentsC* segments_host, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!params_host || W <= 0 || H <= 0) return GSR_ERR_INVALID_ARGUMENT;
   if (params_host->tile_size != 16 || C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
   if (!tile_range || !final_T || !last || !dL_dimage || !pair_vis) return GSR_ERR_INVALID_ARGUMENT;
   if (!seg_ok(segments_host, false) || (segments_host && (!image || !segments_host->seg_col)))
     return GSR_ERR_INVALID_ARGUMENT;
-  const int tx = (W + 15) / 16, ty = (H + 15) / 16, nt = tx * ty;
+  const GsrTiles tiles = gsr_tiles(W, H);
+  const int tx = tiles.tx, nt = (int)tiles.n;
   const GsrRasterParams rp = to_params(params_host);
   const SegDev seg = to_segdev(segments_host);
   const float4* seg_col = segments_host ? reinterpret_cast<const float4*>(segments_host->seg_col) : nullptr;
@@ -678,15 +670,12 @@ int gsr_composite_backward_wide_seg(const float* rows, const float* feat_rows, c
       segments_host ? (uint32_t)((segments_host->capacity + seg_round - 1) / seg_round * seg_round) : 0u;
   const uint32_t seg_cap = (uint32_t)(segments_host ? segments_host->capacity : 0);
   const int grid = nt + (int)seg_blocks;
-  const int cw = wide_width(C);
-#define GSR_LAUNCH_BWD_WIDE(CW)                                                                                           \
-  composite_bwd_wide<CW><<<grid, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, pair_vis, tile_range, W, H, \
-                                                  C, tx, nt, rp, final_T, last, dL_dimage, partial_out, image, seg,       \
-                                                  seg_col, seg_cap, seg_blocks)
-  if (cw == 4) GSR_LAUNCH_BWD_WIDE(4);
-  else if (cw == 8) GSR_LAUNCH_BWD_WIDE(8);
-  else GSR_LAUNCH_BWD_WIDE(16);
-#undef GSR_LAUNCH_BWD_WIDE
+  gsr_pick_wide(C, [&](auto cw) {
+    composite_bwd_wide<decltype(cw)::value><<<grid, 64, 0, stream>>>(rows, feat_rows, sorted_splat, sorted_inst, pair_vis,
+                                                                    tile_range, W, H, C, tx, nt, rp, final_T, last,
+                                                                    dL_dimage, partial_out, image, seg, seg_col, seg_cap,
+                                                                    seg_blocks);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

@@ -12,14 +12,12 @@
 // mcmc_draws_kernel  one lane per row: the raw words and the normals of rows 0..N-1, for the tests that pin the generator.
 #include "gsr_device.h"
 #include "gsr_controller.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
 constexpr int MN_BLOCK = 256;
 constexpr int MN_ROWS = 4;                  // rows a lane tests: a wave owns 64 * MN_ROWS rows
-
-inline unsigned grid_for(int64_t n, int64_t block) { return (unsigned)((n + block - 1) / block); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -106,7 +104,7 @@ extern "C" {
 int gsr_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
                    const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
                    float noise_level, float scale_eps, uint64_t seed, uint64_t step, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N == 0) return GSR_OK;
   if (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !points_in_view || N < 0 ||
       N > GSR_NEIGHBOURS_MAX_N || !(opacity_threshold > 0.f) || !(margin >= 0.f) || !(noise_level >= 0.f) ||
@@ -120,7 +118,7 @@ int gsr_mcmc_noise(float* position, const float* log_scaling, const float* rotat
 }
 
 int gsr_mcmc_draws(int64_t N, uint64_t seed, uint64_t step, uint32_t* words_out, float* normals_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N == 0 || (!words_out && !normals_out)) return GSR_OK;
   if (N < 0 || N > GSR_NEIGHBOURS_MAX_N || !aligned16(words_out)) return GSR_ERR_INVALID_ARGUMENT;
   mcmc_draws_kernel<<<grid_for(N, MN_BLOCK), MN_BLOCK, 0, stream>>>(N, seed, step, words_out, normals_out);

@@ -21,13 +21,11 @@
 //
 // wave64 ballot / mbcnt ranks, LDS-staged row lists, integer atomics only (histogram counts): bit-reproducible.
 #include "gsr_device.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
 constexpr int DN_THREADS = 256;
-
-inline unsigned dn_grid(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // Order-preserving u32 key of a float: -0 folded onto +0 (equal under comparison), NaN above +inf (torch sorts it last).
 __device__ __forceinline__ uint32_t select_key(float v, bool descending) {
@@ -417,13 +415,13 @@ int gsr_point_state_add(const int64_t* idx, const float* screen_scale, int32_t s
                         const float* split_score, const float* prune_cost, int64_t M, float split_alpha,
                         float prune_alpha, float* state_prune_cost, float* state_split_score, float* state_max_scale_px,
                         int16_t* state_points_in_view, float* state_visibility, float* visible_sum, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || (scale_cols != 1 && scale_cols != 2)) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if ((screen_scale && !state_max_scale_px) || (visibility && (!state_points_in_view || !state_visibility)) ||
       (split_score && !state_split_score) || (prune_cost && !state_prune_cost))
     return GSR_ERR_INVALID_ARGUMENT;
-  point_state_add_kernel<<<dn_grid(M, DN_THREADS), DN_THREADS, 0, stream>>>(
+  point_state_add_kernel<<<grid_for(M, DN_THREADS), DN_THREADS, 0, stream>>>(
       idx, screen_scale, scale_cols, visibility, split_score, prune_cost, M, split_alpha, prune_alpha, state_prune_cost,
       state_split_score, state_max_scale_px, state_points_in_view, state_visibility, visibility ? visible_sum : nullptr);
   GSR_CHECK_LAUNCH();
@@ -433,16 +431,16 @@ int gsr_point_state_add(const int64_t* idx, const float* screen_scale, int32_t s
 int gsr_dp_pack(const int64_t* idx, const float* dL_dcolors, const float* split_score, const float* prune_cost,
                 const float* screen_scale, int32_t scale_cols, const float* camera_pos, int64_t M, int64_t N,
                 float* block_out, const float* visibility, float* visibility_sum, float* views_sum, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 3 || M > N || (scale_cols != 1 && scale_cols != 2) || !block_out || !camera_pos)
     return GSR_ERR_INVALID_ARGUMENT;
   if (visibility && (!visibility_sum || !views_sum)) return GSR_ERR_INVALID_ARGUMENT;
   if (M > 0 && (!dL_dcolors || !split_score || !prune_cost || !screen_scale)) return GSR_ERR_INVALID_ARGUMENT;
   if (M < N) {                                      // rows the camera did not see: zero gradient, NaN scores, zero scale
-    dp_fill_kernel<<<dn_grid(6 * N + 3, DN_THREADS), DN_THREADS, 0, stream>>>(block_out, N);
+    dp_fill_kernel<<<grid_for(6 * N + 3, DN_THREADS), DN_THREADS, 0, stream>>>(block_out, N);
     GSR_CHECK_LAUNCH();
   }
-  dp_pack_kernel<<<dn_grid(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(
+  dp_pack_kernel<<<grid_for(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(
       idx, dL_dcolors, split_score, prune_cost, screen_scale, scale_cols, camera_pos, M, N, block_out, visibility,
       visibility_sum, views_sum);
   GSR_CHECK_LAUNCH();
@@ -453,12 +451,12 @@ int gsr_dp_replay(const float* blocks, int64_t stride, const int32_t* slots, int
                   float split_alpha, float prune_alpha, float* state_split_score, float* state_prune_cost,
                   float* state_max_scale_px, const float* visibility_sum, const float* views_sum,
                   float* state_visibility, int16_t* state_points_in_view, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || num_cameras < 0 || stride < 6 * N + 3) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0 || num_cameras == 0) return GSR_OK;
   if (!blocks || !slots || !state_split_score || !state_prune_cost || !state_max_scale_px) return GSR_ERR_INVALID_ARGUMENT;
   if (visibility_sum && (!views_sum || !state_visibility || !state_points_in_view)) return GSR_ERR_INVALID_ARGUMENT;
-  dp_replay_kernel<<<dn_grid(N, DN_THREADS), DN_THREADS, 0, stream>>>(blocks, stride, slots, num_cameras, N, split_alpha,
+  dp_replay_kernel<<<grid_for(N, DN_THREADS), DN_THREADS, 0, stream>>>(blocks, stride, slots, num_cameras, N, split_alpha,
                                                                      prune_alpha, state_split_score, state_prune_cost,
                                                                      state_max_scale_px, visibility_sum, views_sum,
                                                                      state_visibility, state_points_in_view);
@@ -470,7 +468,7 @@ int gsr_dp_pack_sharded(const int64_t* idx, const float* dL_dcolors, const float
                         const float* screen_scale, int32_t scale_cols, const float* camera_pos, int64_t M, int64_t N,
                         int32_t num_ranks, int32_t slots_per_rank, int32_t slot, float* factors_out, float* scores_out,
                         float* scale_max, const float* visibility, float* visibility_sum, float* views_sum, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 3 || M > N || (scale_cols != 1 && scale_cols != 2) || num_ranks < 1 || slots_per_rank < 1 || slot < 0 ||
       slot >= slots_per_rank || !scores_out || !scale_max || (factors_out && !camera_pos))
     return GSR_ERR_INVALID_ARGUMENT;
@@ -478,11 +476,11 @@ int gsr_dp_pack_sharded(const int64_t* idx, const float* dL_dcolors, const float
   if (M > 0 && ((factors_out && !dL_dcolors) || !split_score || !prune_cost || !screen_scale)) return GSR_ERR_INVALID_ARGUMENT;
   const int64_t L = (N + num_ranks - 1) / num_ranks;
   if (M < N) {                                      // rows the camera did not see: zero gradient, NaN scores
-    dp_fill_sharded_kernel<<<dn_grid(factors_out ? 3 * N : N, DN_THREADS), DN_THREADS, 0, stream>>>(factors_out, scores_out, N, L,
+    dp_fill_sharded_kernel<<<grid_for(factors_out ? 3 * N : N, DN_THREADS), DN_THREADS, 0, stream>>>(factors_out, scores_out, N, L,
                                                                                 slots_per_rank, slot);
     GSR_CHECK_LAUNCH();
   }
-  dp_pack_sharded_kernel<<<dn_grid(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(
+  dp_pack_sharded_kernel<<<grid_for(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(
       idx, dL_dcolors, split_score, prune_cost, screen_scale, scale_cols, camera_pos, M, N, L, slots_per_rank, slot,
       factors_out, scores_out, scale_max, visibility, visibility_sum, views_sum);
   GSR_CHECK_LAUNCH();
@@ -491,13 +489,13 @@ int gsr_dp_pack_sharded(const int64_t* idx, const float* dL_dcolors, const float
 
 int gsr_dp_pack_factors_rows(const int64_t* idx, const float* grad_rows, const float* camera_pos, int64_t M, int64_t N,
                              float* factors_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 3 || M > N || !factors_out || !camera_pos || (M > 0 && !grad_rows)) return GSR_ERR_INVALID_ARGUMENT;
   if (M < N) {
-    dp_factors_rows_kernel<<<dn_grid(3 * N, DN_THREADS), DN_THREADS, 0, stream>>>(nullptr, nullptr, nullptr, M, N, factors_out, 1);
+    dp_factors_rows_kernel<<<grid_for(3 * N, DN_THREADS), DN_THREADS, 0, stream>>>(nullptr, nullptr, nullptr, M, N, factors_out, 1);
     GSR_CHECK_LAUNCH();
   }
-  dp_factors_rows_kernel<<<dn_grid(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(M < N ? idx : nullptr, grad_rows, camera_pos,
+  dp_factors_rows_kernel<<<grid_for(M > 3 ? M : 3, DN_THREADS), DN_THREADS, 0, stream>>>(M < N ? idx : nullptr, grad_rows, camera_pos,
                                                                                       M, N, factors_out, 0);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
@@ -506,7 +504,7 @@ int gsr_dp_pack_factors_rows(const int64_t* idx, const float* grad_rows, const f
 int gsr_dp_replay_slice(const float* recv, int32_t num_ranks, int32_t slots_per_rank, int64_t N, int32_t rank,
                         int32_t num_cameras, float split_alpha, float prune_alpha, const float* state_split_score,
                         const float* state_prune_cost, float* slice_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || num_ranks < 1 || slots_per_rank < 1 || rank < 0 || rank >= num_ranks || num_cameras < 0 ||
       num_cameras > num_ranks * slots_per_rank)
     return GSR_ERR_INVALID_ARGUMENT;
@@ -514,7 +512,7 @@ int gsr_dp_replay_slice(const float* recv, int32_t num_ranks, int32_t slots_per_
   const int64_t lo = (int64_t)rank * L, count = lo < N ? (N - lo < L ? N - lo : L) : 0;
   if (count == 0) return GSR_OK;
   if (!recv || !state_split_score || !state_prune_cost || !slice_out) return GSR_ERR_INVALID_ARGUMENT;
-  dp_replay_slice_kernel<<<dn_grid(count, DN_THREADS), DN_THREADS, 0, stream>>>(recv, num_ranks, slots_per_rank, L,
+  dp_replay_slice_kernel<<<grid_for(count, DN_THREADS), DN_THREADS, 0, stream>>>(recv, num_ranks, slots_per_rank, L,
                                                                                num_cameras, lo, count, split_alpha,
                                                                                prune_alpha, state_split_score,
                                                                                state_prune_cost, slice_out);
@@ -525,14 +523,14 @@ int gsr_dp_replay_slice(const float* recv, int32_t num_ranks, int32_t slots_per_
 int gsr_dp_finish(const float* gathered, int32_t num_ranks, int64_t N, float* state_split_score, float* state_prune_cost,
                   const float* scale_max, float* state_max_scale_px, const float* visibility_sum, const float* views_sum,
                   float* state_visibility, int16_t* state_points_in_view, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || num_ranks < 1) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) return GSR_OK;
   if (!gathered || !state_split_score || !state_prune_cost) return GSR_ERR_INVALID_ARGUMENT;
   if (scale_max && !state_max_scale_px) return GSR_ERR_INVALID_ARGUMENT;
   if (visibility_sum && (!views_sum || !state_visibility || !state_points_in_view)) return GSR_ERR_INVALID_ARGUMENT;
   const int64_t L = (N + num_ranks - 1) / num_ranks;
-  dp_finish_kernel<<<dn_grid(N, DN_THREADS), DN_THREADS, 0, stream>>>(gathered, L, N, state_split_score, state_prune_cost,
+  dp_finish_kernel<<<grid_for(N, DN_THREADS), DN_THREADS, 0, stream>>>(gathered, L, N, state_split_score, state_prune_cost,
                                                                      scale_max, state_max_scale_px, visibility_sum,
                                                                      views_sum, state_visibility, state_points_in_view);
   GSR_CHECK_LAUNCH();
@@ -547,7 +545,7 @@ size_t gsr_select_workspace_bytes(int64_t N) {
 
 int gsr_select_n(const float* values, int64_t N, int64_t n, int32_t descending, uint8_t* mask_out, void* workspace,
                  size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || n < 0 || N >= (1ll << 32)) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) return GSR_OK;
   if (!values || !mask_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -560,7 +558,7 @@ int gsr_select_n(const float* values, int64_t N, int64_t n, int32_t descending, 
   SelectState* st = reinterpret_cast<SelectState*>(ws);
   uint32_t* hist = reinterpret_cast<uint32_t*>(ws + 256);
   uint32_t* block_counts = reinterpret_cast<uint32_t*>(ws + 256 + 1024);
-  const unsigned blocks = dn_grid(N, DN_THREADS);
+  const unsigned blocks = grid_for(N, DN_THREADS);
   uint8_t* scan_ws = ws + 256 + 1024 + (((size_t)blocks * 4 + 255) / 256) * 256;
   const size_t scan_bytes = gsr_scan_workspace_bytes((int64_t)blocks);
 
@@ -589,14 +587,14 @@ size_t gsr_compact_workspace_bytes(int64_t N) {
 
 int gsr_compact_offsets(const uint8_t* keep_mask, int64_t N, uint32_t* block_offsets_out, uint32_t* kept_total_dev,
                         void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || N >= (1ll << 32) || !kept_total_dev) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) {
     if (hipMemsetAsync(kept_total_dev, 0, sizeof(uint32_t), stream) != hipSuccess) return GSR_ERR_LAUNCH_FAILED;
     return GSR_OK;
   }
   if (!keep_mask || !block_offsets_out) return GSR_ERR_INVALID_ARGUMENT;
-  const unsigned blocks = dn_grid(N, DN_THREADS);
+  const unsigned blocks = grid_for(N, DN_THREADS);
   if (!workspace || workspace_bytes < gsr_scan_workspace_bytes((int64_t)blocks)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   compact_count_kernel<<<blocks, DN_THREADS, 0, stream>>>(keep_mask, N, block_offsets_out);
   GSR_CHECK_LAUNCH();
@@ -606,7 +604,7 @@ int gsr_compact_offsets(const uint8_t* keep_mask, int64_t N, uint32_t* block_off
 
 int gsr_compact_columns(const uint8_t* keep_mask, int64_t N, const uint32_t* block_offsets, int64_t kept_total,
                         int64_t n_tail, const GsrColumnC* columns_host, int32_t n_columns, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || kept_total < 0 || kept_total > N || n_tail < 0 || n_columns < 0 || n_columns > GSR_MAX_COLUMNS)
     return GSR_ERR_INVALID_ARGUMENT;
   if (n_columns == 0 || (N == 0 && n_tail == 0)) return GSR_OK;
@@ -617,7 +615,7 @@ int gsr_compact_columns(const uint8_t* keep_mask, int64_t N, const uint32_t* blo
     cs.col[c] = columns_host[c];
     if (cs.col[c].width_dwords <= 0 || !cs.col[c].dst || (N > 0 && !cs.col[c].src)) return GSR_ERR_INVALID_ARGUMENT;
   }
-  const unsigned row_blocks = dn_grid(N, DN_THREADS), tail_blocks = dn_grid(n_tail, DN_THREADS);
+  const unsigned row_blocks = grid_for(N, DN_THREADS), tail_blocks = grid_for(n_tail, DN_THREADS);
   if (row_blocks + tail_blocks == 0) return GSR_OK;
   compact_gather_kernel<<<row_blocks + tail_blocks, DN_THREADS, 0, stream>>>(keep_mask, N, block_offsets, row_blocks,
                                                                             kept_total, n_tail, cs);

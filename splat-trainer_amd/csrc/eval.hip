@@ -13,7 +13,7 @@
 // the block's slot.  Nothing is atomic: two runs give the same bits.
 #include "gsr_device.h"
 #include "gsr_eval.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -138,7 +138,7 @@ size_t gsr_color_fit_workspace_bytes(int64_t P) {
 
 int gsr_color_fit(const float* image, const float* ref, int64_t P, int32_t num_iters, float eps, float* out,
                   void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (P <= 0 || !image || !ref || !out || out == image || out == ref || num_iters < 0 || num_iters > EV_MAX_ITERS ||
       !(eps >= 0.f && eps < 0.5f))
     return GSR_ERR_INVALID_ARGUMENT;

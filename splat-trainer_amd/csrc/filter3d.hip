@@ -11,7 +11,7 @@
 //                          forward's terms from the inputs: nothing is saved between the two.
 #include "gsr_device.h"
 #include "gsr_filter3d.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -19,8 +19,6 @@ constexpr int F3_BLOCK = 256;
 constexpr int SR_PPL = 4;                   // points per lane
 constexpr int SR_STEP = 4;                  // cameras per step of the sweep
 constexpr int F3_ROWS = 4;                  // rows per lane: 3 float4 of log_scaling, one each of alpha_logit and rate
-
-inline unsigned grid_for(int64_t n, int64_t block) { return (unsigned)((n + block - 1) / block); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -144,7 +142,7 @@ extern "C" {
 
 int gsr_sampling_rate(const float* points, int64_t N, const float* records, const float* focal, int64_t V, float margin,
                       float* rate_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!points || !records || !focal || !rate_out || N < 1 || N > GSR_NEIGHBOURS_MAX_N || V < 1 ||
       V > GSR_VISIBILITY_MAX_CAMERAS || !(margin >= 0.f))
     return GSR_ERR_INVALID_ARGUMENT;
@@ -156,7 +154,7 @@ int gsr_sampling_rate(const float* points, int64_t N, const float* records, cons
 
 int gsr_filter3d_forward(const float* log_scaling, const float* alpha_logit, const float* rate, int64_t N, float strength,
                          float* out_log_scaling, float* out_alpha_logit, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!log_scaling || !alpha_logit || !rate || !out_log_scaling || !out_alpha_logit || N < 1 ||
       N > GSR_NEIGHBOURS_MAX_N || !(strength >= 0.f))
     return GSR_ERR_INVALID_ARGUMENT;
@@ -172,7 +170,7 @@ int gsr_filter3d_forward(const float* log_scaling, const float* alpha_logit, con
 int gsr_filter3d_backward(const float* log_scaling, const float* alpha_logit, const float* rate, int64_t N, float strength,
                           const float* d_out_log_scaling, const float* d_out_alpha_logit, float* d_log_scaling,
                           float* d_alpha_logit, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!log_scaling || !alpha_logit || !rate || !d_out_log_scaling || !d_out_alpha_logit || !d_log_scaling ||
       !d_alpha_logit || N < 1 || N > GSR_NEIGHBOURS_MAX_N || !(strength >= 0.f))
     return GSR_ERR_INVALID_ARGUMENT;

@@ -12,11 +12,9 @@
 //
 // No allocation here either: gsr_frame_plan lays the frame's buffers out in two caller-owned arenas (outputs that outlive
 // the frame's backward pass / scratch) and returns their offsets; gsr_frame_forward enqueues.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -57,14 +55,14 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
   if (f->N < 0 || f->N >= (1ll << 30) || f->W <= 0 || f->H <= 0 || f->pair_capacity < 0 || f->pair_capacity > 0x7FFFFFFFll)
     return GSR_ERR_INVALID_ARGUMENT;
   const bool projected = f->position == nullptr;
-  if (!projected && f->K != 1 && f->K != 4 && f->K != 9 && f->K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!projected && !gsr_sh_degree_ok(f->K)) return GSR_ERR_UNSUPPORTED;
   if (f->C < 1 || f->C > GSR_MAX_FEATURES || (!projected && f->C != 3)) return GSR_ERR_UNSUPPORTED;
   const bool wide = f->C >= GSR_WIDE_MIN_FEATURES;         // features in their own table
   if (wide && !f->feature_table) return GSR_ERR_UNSUPPORTED;
   if (f->params.tile_size != 16) return GSR_ERR_UNSUPPORTED;
   memset(p, 0, sizeof(*p));
   const int64_t N = f->N, cap = f->pair_capacity;
-  const int64_t tx = (f->W + 15) / 16, ty = (f->H + 15) / 16, T = tx * ty, P = (int64_t)f->W * f->H;
+  const int64_t T = gsr_tiles(f->W, f->H).n, P = (int64_t)f->W * f->H;
   const bool vis_partial = f->compute_visibility || f->needs_grad;
 
   Cursor out;
@@ -95,7 +93,7 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
   p->trank_a = out.take(4 * cap + 16);         // (+ 3 words: K6's large-frame walk fetches list words four at a time)
   p->trank_b = out.take(4 * cap + 16);
   p->pair_vis = vis_partial ? out.take(4 * cap) : -1;
-  const int64_t CW = f->C <= 4 ? 4 : f->C <= 8 ? 8 : 16;
+  const int64_t CW = gsr_wide_width(f->C);
   p->feat_rows = wide ? out.take(4 * CW * N) : -1;
   // segment tables and pixel slots (forward checkpoints read by the backward pass)
   p->seg_capacity = 0;
@@ -144,7 +142,7 @@ int gsr_frame_plan(const GsrFrameC* f, GsrFramePlanC* p) {
 int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, void* work, GsrFrameResultC* res,
                       uint32_t* counts_host, void* event_counts, void* event_k6_begin, void* event_k6_end,
                       void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!f || !p || !out || !work || !res) return GSR_ERR_INVALID_ARGUMENT;
   if (f->N <= 0) return GSR_ERR_INVALID_ARGUMENT;          // an empty scene is the caller's blank frame
   const bool projected = f->position == nullptr;
@@ -156,16 +154,10 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
   }
   memset(res, 0, sizeof(*res));
   const int64_t N = f->N, cap = f->pair_capacity;
-  const int tx = (f->W + 15) / 16, ty = (f->H + 15) / 16, T = tx * ty;
+  const int T = (int)gsr_tiles(f->W, f->H).n;
   uint32_t* counts = at<uint32_t>(out, p->counts);
   uint32_t* M_dev = projected ? nullptr : counts;          // projected mode: N is exact
   uint32_t* O_dev = counts + 1;
-  int rc;
-#define GSR_TRY(call)          \
-  do {                         \
-    rc = (call);               \
-    if (rc < 0) return rc;     \
-  } while (0)
 
   if (hipMemsetAsync(at<uint8_t>(out, p->zero_begin), 0, (size_t)p->zero_bytes, stream) != hipSuccess)
     return GSR_ERR_LAUNCH_FAILED;
@@ -197,10 +189,11 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
   const uint32_t* order = f->depth_order;
   res->order = -1;                                          // the caller's own array
   if (!order) {
-    GSR_TRY(gsr_sort_pairs_u32(keys_a, vals_a, at<uint32_t>(work, p->keys_b), vals_b, N, 1, 0, bit_length(key_max),
-                               at<uint8_t>(work, p->sort_ws), (size_t)p->sort_ws_bytes, M_dev, stream_));
-    res->order = rc == 1 ? p->vals_b : p->vals_a;
-    order = rc == 1 ? vals_b : vals_a;
+    const int in_b = gsr_sort_pairs_u32(keys_a, vals_a, at<uint32_t>(work, p->keys_b), vals_b, N, 1, 0, bit_length(key_max),
+                                        at<uint8_t>(work, p->sort_ws), (size_t)p->sort_ws_bytes, M_dev, stream_);
+    if (in_b < 0) return in_b;
+    res->order = in_b == 1 ? p->vals_b : p->vals_a;
+    order = in_b == 1 ? vals_b : vals_a;
   }
   uint32_t* count = at<uint32_t>(out, p->count);
   uint32_t* offsets = at<uint32_t>(out, p->offsets);
@@ -233,9 +226,10 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
     uint32_t* trank_b = at<uint32_t>(out, p->trank_b);
     GSR_TRY(gsr_tile_emit(rows, order, offsets, hits, N, f->W, f->H, &f->params, tkeys_a, trank_a, cap, M_dev, stream_));
     // values: instance id (implicit 0..O-1) and splat id (+ half mask) travel with the tile key
-    GSR_TRY(gsr_sort_pairs2_u32(tkeys_a, tvals_a, trank_a, tkeys_b, tvals_b, trank_b, cap, 1, 0, tile_bits_of(T),
-                                at<uint8_t>(work, p->tsort_ws), (size_t)p->tsort_ws_bytes, O_dev, stream_));
-    const bool in_b = rc == 1;
+    const int sorted = gsr_sort_pairs2_u32(tkeys_a, tvals_a, trank_a, tkeys_b, tvals_b, trank_b, cap, 1, 0, tile_bits_of(T),
+                                           at<uint8_t>(work, p->tsort_ws), (size_t)p->tsort_ws_bytes, O_dev, stream_);
+    if (sorted < 0) return sorted;
+    const bool in_b = sorted == 1;
     res->sorted_inst = in_b ? p->tvals_b : p->tvals_a;
     res->sorted_splat = in_b ? p->trank_b : p->trank_a;
     const uint32_t* sorted_keys = in_b ? tkeys_b : tkeys_a;
@@ -287,7 +281,6 @@ int gsr_frame_forward(const GsrFrameC* f, const GsrFramePlanC* p, void* out, voi
       GSR_TRY(gsr_reduce_visibility(at<float>(out, p->vis_partial), offsets, count, order, N,
                                     at<float>(out, p->visibility), cap, M_dev, stream_));
   }
-#undef GSR_TRY
   return GSR_OK;
 }
 
@@ -317,7 +310,7 @@ int gsr_frame_backward(const GsrFrameBackwardC* b, void* event_k7_begin, void* e
 // next to the sweep (distributed.CameraShardedStep: early factor gather).  3 = gsr_frame_backward.
 int gsr_frame_backward_stages(const GsrFrameBackwardC* b, int32_t stages, void* event_k7_begin, void* event_k7_end,
                               void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (stages < 1 || stages > 3) return GSR_ERR_INVALID_ARGUMENT;
   if (!b || b->N < 0 || b->M < 0 || b->M > b->N || b->O < 0 || b->mode < 0 || b->mode > 2 || b->sh_mode < 0 ||
       b->sh_mode > 2)
@@ -327,11 +320,6 @@ int gsr_frame_backward_stages(const GsrFrameBackwardC* b, int32_t stages, void* 
   if (b->sh_mode && (!b->d_sh || !b->sh_features || !b->camera_pos || (M > 0 && !b->d_colors))) return GSR_ERR_INVALID_ARGUMENT;
   const bool needs_inverse = M < N && (b->mode == 2 || b->sh_mode == 1);
   if (needs_inverse && !b->inverse) return GSR_ERR_INVALID_ARGUMENT;
-#define GSR_TRY(call)                 \
-  do {                                \
-    const int rc_ = (call);           \
-    if (rc_ < 0) return rc_;          \
-  } while (0)
   const bool live = M > 0 && b->O > 0 && b->d_image != nullptr;
   if (!(stages & 1)) {
     // (the rows were formed by an earlier call)
@@ -371,7 +359,6 @@ int gsr_frame_backward_stages(const GsrFrameBackwardC* b, int32_t stages, void* 
     GSR_TRY(gsr_sh_backward(b->d_colors, b->sh_features, b->position, b->indexes, M, b->K, b->camera_pos, nullptr, b->d_sh,
                             nullptr, 1, stream_));
   }
-#undef GSR_TRY
   return GSR_OK;
 }
 

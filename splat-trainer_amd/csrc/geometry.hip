@@ -2,7 +2,7 @@
 // All HBM-streaming kernels: one thread per point, coalesced row reads, no LDS.
 #include "gsr_device.h"
 #include "gsr_dpp_reduce.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 static_assert(sizeof(GsrRasterParams) == sizeof(GsrRasterParamsC), "raster params layout");
 
@@ -377,8 +377,9 @@ __device__ __forceinline__ float gsr_qlim(float opacity, const GsrRasterParams& 
 
 // Pixel bounding box of a splat's support, for the rows' words 12 / 13 (x0 | x1 << 16, y0 | y1 << 16; signed 16-bit pixel
 // coordinates, inclusive; x0 > x1: empty): every pixel whose centre passes the composite kernels' test q <= qlim lies
-// inside -- the half-widths are gsr_splat_extent's (the same inflated support K4 bins with).  Read by the windowed
-// backward walk (composite.hip: composite_bwd_win_kernel), which evaluates 64-pixel windows laid over box-and-tile.
+// inside -- the half-widths are gsr_splat_extent's (the same inflated support K4 bins with).  No kernel reads the two
+// words today: their one reader, the windowed backward walk, was rejected and removed (variant (a)).  The three
+// kernels that write rows still compute and store them; dropping that is a device-code change of its own.
 __device__ __forceinline__ float2 gsr_pixel_bbox(float u, float v, float A, float B, float C, float opacity,
                                                  const GsrRasterParams& rp) {
   int x0 = 1, x1 = 0, y0 = 1, y1 = 0;
@@ -981,8 +982,6 @@ inline GsrRasterParams to_params(const GsrRasterParamsC* c) {
   return rp;
 }
 
-inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 }  // namespace
 
 extern "C" {
@@ -1000,32 +999,27 @@ const char* gsr_error_string(int code) {
   }
 }
 
-size_t gsr_cull_workspace_bytes(int64_t N) {
-  if (N < 0) N = 0;
-  int64_t nw = (N + CULL_WAVE_SPAN - 1) / CULL_WAVE_SPAN;
-  size_t counts = (((size_t)nw * sizeof(uint32_t) + 255) / 256) * 256;
-  return counts + gsr_scan_workspace_bytes(nw) + 256;
-}
+size_t gsr_cull_workspace_bytes(int64_t N) { return gsr_cull_carve(N < 0 ? 0 : N, CULL_WAVE_SPAN).total_bytes; }
 
 int gsr_frustum_cull(const float* position, int64_t N, const float* T_camera_world, const float* projection, int32_t W,
                      int32_t H, float near_plane, float far_plane, float margin_px, int64_t* indexes_out,
                      uint32_t* count_dev, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || N > 0x7FFFFFFFll || !count_dev || !T_camera_world || !projection) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) { hipMemsetAsync(count_dev, 0, sizeof(uint32_t), stream); return GSR_OK; }
   if (!position || !indexes_out) return GSR_ERR_INVALID_ARGUMENT;
-  if (!workspace || workspace_bytes < gsr_cull_workspace_bytes(N)) return GSR_ERR_WORKSPACE_TOO_SMALL;
-  const int64_t nw = (N + CULL_WAVE_SPAN - 1) / CULL_WAVE_SPAN;
+  const GsrCullCarve carve = gsr_cull_carve(N, CULL_WAVE_SPAN);
+  if (!workspace || workspace_bytes < carve.total_bytes) return GSR_ERR_WORKSPACE_TOO_SMALL;
+  const int64_t nw = carve.waves;
   uint32_t* wave_counts = reinterpret_cast<uint32_t*>(workspace);
-  size_t counts_bytes = (((size_t)nw * sizeof(uint32_t) + 255) / 256) * 256;
-  uint8_t* scan_ws = reinterpret_cast<uint8_t*>(workspace) + counts_bytes;
+  uint8_t* scan_ws = reinterpret_cast<uint8_t*>(workspace) + carve.counts_bytes;
   const unsigned blocks = grid_for(nw, 4);
   cull_count_kernel<<<blocks, 256, 0, stream>>>(position, N, T_camera_world, projection, W, H, near_plane, far_plane,
                                                margin_px, wave_counts, nw);
   GSR_CHECK_LAUNCH();
   const bool self_prefix = nw <= CULL_SELF_PREFIX_MAX_WAVES;
   if (!self_prefix) {
-    int rc = gsr_exclusive_scan_u32(wave_counts, wave_counts, nw, count_dev, scan_ws, workspace_bytes - counts_bytes, stream_);
+    int rc = gsr_exclusive_scan_u32(wave_counts, wave_counts, nw, count_dev, scan_ws, workspace_bytes - carve.counts_bytes, stream_);
     if (rc != GSR_OK) return rc;
   }
   cull_write_kernel<<<blocks, 256, 0, stream>>>(position, N, T_camera_world, projection, W, H, near_plane, far_plane,
@@ -1039,7 +1033,7 @@ int gsr_project_forward(const float* position, const float* log_scaling, const f
                         const float* projection, const GsrRasterParamsC* params_host, float* gaussians2d_out,
                         float* depth_out, const uint32_t* count_dev, uint32_t* depth_keys_out, uint32_t depth_key_bias,
                         uint32_t depth_key_max, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !indexes || !T_camera_world || !projection ||
@@ -1058,22 +1052,17 @@ int gsr_project_backward(const float* position, const float* log_scaling, const 
                          const float* projection, const GsrRasterParamsC* params_host, const float* dL_dgaussians2d,
                          const float* dL_ddepth, float* d_position, float* d_log_scaling, float* d_rotation,
                          float* d_alpha_logit, int32_t accumulate, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !indexes || !T_camera_world || !projection ||
       !dL_dgaussians2d || !d_position || !d_log_scaling || !d_rotation || !d_alpha_logit)
     return GSR_ERR_INVALID_ARGUMENT;
-  if (accumulate)
-    project_bwd_kernel<true><<<grid_for(M, 256), 256, 0, stream>>>(position, log_scaling, rotation_xyzw, alpha_logit,
-                                                                  indexes, M, T_camera_world, projection,
-                                                                  to_params(params_host), dL_dgaussians2d, dL_ddepth,
-                                                                  d_position, d_log_scaling, d_rotation, d_alpha_logit);
-  else
-    project_bwd_kernel<false><<<grid_for(M, 256), 256, 0, stream>>>(position, log_scaling, rotation_xyzw, alpha_logit,
-                                                                   indexes, M, T_camera_world, projection,
-                                                                   to_params(params_host), dL_dgaussians2d, dL_ddepth,
-                                                                   d_position, d_log_scaling, d_rotation, d_alpha_logit);
+  gsr_pick_bool(accumulate != 0, [&](auto acc) {
+    project_bwd_kernel<decltype(acc)::value><<<grid_for(M, 256), 256, 0, stream>>>(
+        position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, T_camera_world, projection, to_params(params_host),
+        dL_dgaussians2d, dL_ddepth, d_position, d_log_scaling, d_rotation, d_alpha_logit);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1082,7 +1071,7 @@ int64_t gsr_camera_grad_partial_rows(int64_t count) { return count > 0 ? (int64_
 
 int gsr_camera_grad_finish(const float* partials, int64_t rows, const float* T_camera_world, float* d_camera,
                            void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (rows < 0 || !d_camera || (rows > 0 && !partials)) return GSR_ERR_INVALID_ARGUMENT;
   cam_grad_finish_kernel<<<1, 256, 0, stream>>>(partials, rows, T_camera_world, d_camera);
   GSR_CHECK_LAUNCH();
@@ -1095,7 +1084,7 @@ int gsr_project_backward_camera(const float* position, const float* log_scaling,
                                 const float* dL_dgaussians2d, const float* dL_ddepth, float* d_position,
                                 float* d_log_scaling, float* d_rotation, float* d_alpha_logit, int32_t accumulate,
                                 float* camera_partials, float* d_camera, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host || !T_camera_world || !projection || !d_camera) return GSR_ERR_INVALID_ARGUMENT;
   if (M > 0 && (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !indexes || !dL_dgaussians2d ||
                 !d_position || !d_log_scaling || !d_rotation || !d_alpha_logit || !camera_partials))
@@ -1117,7 +1106,7 @@ int gsr_project_backward_camera(const float* position, const float* log_scaling,
 
 int gsr_sh_camera_position_grad(const float* dL_dcolors, const float* jacobian, int64_t M, float* camera_partials,
                                 float* d_camera_pos, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !d_camera_pos) return GSR_ERR_INVALID_ARGUMENT;
   const bool live = M > 0 && jacobian != nullptr;        // no Jacobian (K = 1): the colour does not depend on the camera
   if (live && (!dL_dcolors || !camera_partials)) return GSR_ERR_INVALID_ARGUMENT;
@@ -1135,44 +1124,39 @@ int gsr_project_sh_forward(const float* position, const float* log_scaling, cons
                            const GsrRasterParamsC* params_host, float* rows_out, float* screen_scale_out,
                            float* jacobian_out, const uint32_t* count_dev, uint32_t* depth_keys_out,
                            uint32_t depth_key_bias, uint32_t depth_key_max, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
-  if (K != 1 && K != 4 && K != 9 && K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!gsr_sh_degree_ok(K)) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !sh_features || !indexes || !T_camera_world ||
       !projection || !camera_pos || !rows_out || !screen_scale_out)
     return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
   const GsrRasterParams rp = to_params(params_host);
-#define GSR_LAUNCH_PSF(KK, JJ)                                                                                          \
-  project_sh_fwd_kernel<KK, JJ><<<g, 256, 0, stream>>>(position, log_scaling, rotation_xyzw, alpha_logit, sh_features,   \
-                                                       indexes, M, T_camera_world, projection, camera_pos, rp, rows_out, \
-                                                       screen_scale_out, jacobian_out, count_dev, depth_keys_out,        \
-                                                       depth_key_bias, depth_key_max)
-  const bool jj = jacobian_out != nullptr;
-  switch (K) {
-    case 1: if (jj) GSR_LAUNCH_PSF(1, true); else GSR_LAUNCH_PSF(1, false); break;
-    case 4: if (jj) GSR_LAUNCH_PSF(4, true); else GSR_LAUNCH_PSF(4, false); break;
-    case 9: if (jj) GSR_LAUNCH_PSF(9, true); else GSR_LAUNCH_PSF(9, false); break;
-    default: if (jj) GSR_LAUNCH_PSF(16, true); else GSR_LAUNCH_PSF(16, false); break;
-  }
-#undef GSR_LAUNCH_PSF
+  gsr_pick_sh(K, [&](auto k) {
+    gsr_pick_bool(jacobian_out != nullptr, [&](auto jac) {
+      project_sh_fwd_kernel<decltype(k)::value, decltype(jac)::value><<<g, 256, 0, stream>>>(
+          position, log_scaling, rotation_xyzw, alpha_logit, sh_features, indexes, M, T_camera_world, projection,
+          camera_pos, rp, rows_out, screen_scale_out, jacobian_out, count_dev, depth_keys_out, depth_key_bias,
+          depth_key_max);
+    });
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
 
 int gsr_pack_rows(const float* gaussians2d, const float* depth, const float* features, int64_t M, int32_t C,
                   const GsrRasterParamsC* params_host, float* rows_out, float* screen_scale_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
   const GsrRasterParams rp = to_params(params_host);
   if (C < 1 || C > 3) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!gaussians2d || !depth || !features || !rows_out || !screen_scale_out) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  if (C == 1) pack_rows_kernel<1><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
-  else if (C == 2) pack_rows_kernel<2><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
-  else pack_rows_kernel<3><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
+  gsr_pick_channels(C, [&](auto c) {
+    pack_rows_kernel<decltype(c)::value><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, rp, rows_out, screen_scale_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1180,16 +1164,17 @@ int gsr_pack_rows(const float* gaussians2d, const float* depth, const float* fea
 int gsr_pack_rows_wide(const float* gaussians2d, const float* depth, const float* features, int64_t M, int32_t C,
                        const GsrRasterParamsC* params_host, float* rows_out, float* feat_rows_out, float* screen_scale_out,
                        void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !params_host) return GSR_ERR_INVALID_ARGUMENT;
   const GsrRasterParams rp = to_params(params_host);
   if (C < GSR_WIDE_MIN_FEATURES || C > GSR_MAX_FEATURES) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!gaussians2d || !depth || !features || !rows_out || !feat_rows_out || !screen_scale_out) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  if (C <= 4) pack_rows_wide_kernel<4><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
-  else if (C <= 8) pack_rows_wide_kernel<8><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
-  else pack_rows_wide_kernel<16><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out, feat_rows_out, screen_scale_out);
+  gsr_pick_wide(C, [&](auto cw) {
+    pack_rows_wide_kernel<decltype(cw)::value><<<g, 256, 0, stream>>>(gaussians2d, depth, features, M, C, rp, rows_out,
+                                                                     feat_rows_out, screen_scale_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1202,7 +1187,7 @@ int gsr_project_backward_rows(const float* position, const float* log_scaling, c
                               float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
                               int32_t mode, float* d_colors_out, float* prune_cost_out, float* split_score_out,
                               float* visibility_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 0 || M > N || !params_host || mode < 0 || mode > 2) return GSR_ERR_INVALID_ARGUMENT;
   const bool geom = d_position != nullptr;
   if (geom && (!position || !log_scaling || !rotation_xyzw || !alpha_logit || !T_camera_world || !projection ||
@@ -1213,15 +1198,12 @@ int gsr_project_backward_rows(const float* position, const float* log_scaling, c
   if (mode == 2 && N == 0) return GSR_OK;
   if (M > 0 && !grad_rows) return GSR_ERR_INVALID_ARGUMENT;
   const GsrRasterParams rp = to_params(params_host);
-#define GSR_LAUNCH_PBR(MODE, COUNT)                                                                                      \
-  project_bwd_rows_kernel<MODE><<<grid_for(COUNT, 256), 256, 0, stream>>>(                                               \
-      position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, inverse, N, T_camera_world, projection, rp, rows,   \
-      grad_rows, dL_dgaussians2d_extra, dL_ddepth, jacobian, d_position, d_log_scaling, d_rotation, d_alpha_logit,       \
-      d_colors_out, prune_cost_out, split_score_out, visibility_out)
-  if (mode == 2) GSR_LAUNCH_PBR(2, N);
-  else if (mode == 1) GSR_LAUNCH_PBR(1, M);
-  else GSR_LAUNCH_PBR(0, M);
-#undef GSR_LAUNCH_PBR
+  gsr_pick<0, 1, 2>(mode, [&](auto m) {                     // mode 2 sweeps the N scene rows, the others the M visible
+    project_bwd_rows_kernel<decltype(m)::value><<<grid_for(mode == 2 ? N : M, 256), 256, 0, stream>>>(
+        position, log_scaling, rotation_xyzw, alpha_logit, indexes, M, inverse, N, T_camera_world, projection, rp, rows,
+        grad_rows, dL_dgaussians2d_extra, dL_ddepth, jacobian, d_position, d_log_scaling, d_rotation, d_alpha_logit,
+        d_colors_out, prune_cost_out, split_score_out, visibility_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1234,7 +1216,7 @@ int gsr_project_backward_rows_camera(const float* position, const float* log_sca
                                      float* d_position, float* d_log_scaling, float* d_rotation, float* d_alpha_logit,
                                      int32_t mode, float* d_colors_out, float* prune_cost_out, float* split_score_out,
                                      float* visibility_out, float* camera_partials, float* d_camera, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || !d_camera || !T_camera_world || !projection || !d_position || (M > 0 && (!indexes || !grad_rows || !camera_partials)))
     return GSR_ERR_INVALID_ARGUMENT;
   // the sweep exactly as gsr_project_backward_rows runs it, then the camera terms over the visible splats
@@ -1256,30 +1238,18 @@ int gsr_project_backward_rows_camera(const float* position, const float* log_sca
 int gsr_sh_forward(const float* sh_features, const float* positions, const int64_t* indexes, int64_t M, int32_t K,
                    const float* camera_pos, float* colors_out, float* jacobian_out, const uint32_t* count_dev,
                    void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
-  if (K != 1 && K != 4 && K != 9 && K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!gsr_sh_degree_ok(K)) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!sh_features || !positions || !indexes || !camera_pos || !colors_out) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  switch (K) {
-    case 1:
-      if (jacobian_out) sh_fwd_kernel<1, true><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, jacobian_out, count_dev);
-      else sh_fwd_kernel<1, false><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, nullptr, count_dev);
-      break;
-    case 4:
-      if (jacobian_out) sh_fwd_kernel<4, true><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, jacobian_out, count_dev);
-      else sh_fwd_kernel<4, false><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, nullptr, count_dev);
-      break;
-    case 9:
-      if (jacobian_out) sh_fwd_kernel<9, true><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, jacobian_out, count_dev);
-      else sh_fwd_kernel<9, false><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, nullptr, count_dev);
-      break;
-    default:
-      if (jacobian_out) sh_fwd_kernel<16, true><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, jacobian_out, count_dev);
-      else sh_fwd_kernel<16, false><<<g, 256, 0, stream>>>(sh_features, positions, indexes, M, camera_pos, colors_out, nullptr, count_dev);
-      break;
-  }
+  gsr_pick_sh(K, [&](auto k) {
+    gsr_pick_bool(jacobian_out != nullptr, [&](auto jac) {
+      sh_fwd_kernel<decltype(k)::value, decltype(jac)::value><<<g, 256, 0, stream>>>(
+          sh_features, positions, indexes, M, camera_pos, colors_out, jacobian_out, count_dev);
+    });
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1287,37 +1257,25 @@ int gsr_sh_forward(const float* sh_features, const float* positions, const int64
 int gsr_sh_backward(const float* dL_dcolors, const float* sh_features, const float* positions, const int64_t* indexes,
                     int64_t M, int32_t K, const float* camera_pos, const float* jacobian, float* d_sh_features,
                     float* d_positions, int32_t accumulate, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
-  if (K != 1 && K != 4 && K != 9 && K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!gsr_sh_degree_ok(K)) return GSR_ERR_UNSUPPORTED;
   if (M == 0) return GSR_OK;
   if (!dL_dcolors || !sh_features || !positions || !indexes || !camera_pos || !d_sh_features)
     return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(M, 256);
-  switch (K) {
-    case 1:
-      if (accumulate) sh_bwd_kernel<1, true><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      else sh_bwd_kernel<1, false><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      break;
-    case 4:
-      if (accumulate) sh_bwd_kernel<4, true><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      else sh_bwd_kernel<4, false><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      break;
-    case 9:
-      if (accumulate) sh_bwd_kernel<9, true><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      else sh_bwd_kernel<9, false><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      break;
-    default:
-      if (accumulate) sh_bwd_kernel<16, true><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      else sh_bwd_kernel<16, false><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
-      break;
-  }
+  gsr_pick_sh(K, [&](auto k) {
+    gsr_pick_bool(accumulate != 0, [&](auto acc) {
+      sh_bwd_kernel<decltype(k)::value, decltype(acc)::value><<<g, 256, 0, stream>>>(
+          dL_dcolors, sh_features, positions, indexes, M, camera_pos, d_sh_features, d_positions, jacobian);
+    });
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
 
 int gsr_inverse_map(const int64_t* indexes, int64_t M, int64_t N, int32_t* inverse_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 0 || M > N || N > 0x7FFFFFFFll) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) return GSR_OK;
   if (!inverse_out || (M > 0 && !indexes)) return GSR_ERR_INVALID_ARGUMENT;
@@ -1329,19 +1287,17 @@ int gsr_inverse_map(const int64_t* indexes, int64_t M, int64_t N, int32_t* inver
 int gsr_sh_backward_dense(const float* dL_dcolors, const float* sh_features, const float* positions,
                           const int32_t* inverse, int64_t M, int64_t N, int32_t K, const float* camera_pos,
                           const float* jacobian, float* d_sh_features, float* d_positions, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || N < 0 || M > N) return GSR_ERR_INVALID_ARGUMENT;
-  if (K != 1 && K != 4 && K != 9 && K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!gsr_sh_degree_ok(K)) return GSR_ERR_UNSUPPORTED;
   if (N == 0) return GSR_OK;
   if (!inverse && M != N) return GSR_ERR_INVALID_ARGUMENT;          // identity map only when every row is visible
   if (!sh_features || !positions || !camera_pos || !d_sh_features || (M > 0 && !dL_dcolors)) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(N, 256);
-  switch (K) {
-    case 1: sh_bwd_dense_kernel<1><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, inverse, N, camera_pos, d_sh_features, d_positions, jacobian); break;
-    case 4: sh_bwd_dense_kernel<4><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, inverse, N, camera_pos, d_sh_features, d_positions, jacobian); break;
-    case 9: sh_bwd_dense_kernel<9><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, inverse, N, camera_pos, d_sh_features, d_positions, jacobian); break;
-    default: sh_bwd_dense_kernel<16><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, inverse, N, camera_pos, d_sh_features, d_positions, jacobian); break;
-  }
+  gsr_pick_sh(K, [&](auto k) {
+    sh_bwd_dense_kernel<decltype(k)::value><<<g, 256, 0, stream>>>(dL_dcolors, sh_features, positions, inverse, N, camera_pos,
+                                                                  d_sh_features, d_positions, jacobian);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
@@ -1349,28 +1305,25 @@ int gsr_sh_backward_dense(const float* dL_dcolors, const float* sh_features, con
 int gsr_sh_backward_multi(const float* dL_dcolors_dense, int64_t dense_stride, const float* camera_positions,
                           int64_t camera_stride, int32_t num_cameras, const float* sh_features, const float* positions, int64_t N, int32_t K, float* d_sh_features,
                           float* d_positions, int32_t accumulate, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0 || num_cameras < 0 || dense_stride < 3 * N || camera_stride < 3) return GSR_ERR_INVALID_ARGUMENT;
-  if (K != 1 && K != 4 && K != 9 && K != 16) return GSR_ERR_UNSUPPORTED;
+  if (!gsr_sh_degree_ok(K)) return GSR_ERR_UNSUPPORTED;
   if (N == 0 || (num_cameras == 0 && accumulate)) return GSR_OK;
   if (!dL_dcolors_dense || !camera_positions || !sh_features || !positions || !d_sh_features) return GSR_ERR_INVALID_ARGUMENT;
   const unsigned g = grid_for(N, 256);
   if (!accumulate && !d_positions && num_cameras > 0) {            // overwrite, no position term: the streaming form
-    switch (K) {
-      case 1: sh_bwd_multi_stream_kernel<1><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, positions, N, d_sh_features); break;
-      case 4: sh_bwd_multi_stream_kernel<4><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, positions, N, d_sh_features); break;
-      case 9: sh_bwd_multi_stream_kernel<9><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, positions, N, d_sh_features); break;
-      default: sh_bwd_multi_stream_kernel<16><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, positions, N, d_sh_features); break;
-    }
+    gsr_pick_sh(K, [&](auto k) {
+      sh_bwd_multi_stream_kernel<decltype(k)::value><<<g, 256, 0, stream>>>(
+          dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, positions, N, d_sh_features);
+    });
     GSR_CHECK_LAUNCH();
     return GSR_OK;
   }
-  switch (K) {
-    case 1: sh_bwd_multi_kernel<1><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, sh_features, positions, N, d_sh_features, d_positions, accumulate); break;
-    case 4: sh_bwd_multi_kernel<4><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, sh_features, positions, N, d_sh_features, d_positions, accumulate); break;
-    case 9: sh_bwd_multi_kernel<9><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, sh_features, positions, N, d_sh_features, d_positions, accumulate); break;
-    default: sh_bwd_multi_kernel<16><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions, camera_stride, num_cameras, sh_features, positions, N, d_sh_features, d_positions, accumulate); break;
-  }
+  gsr_pick_sh(K, [&](auto k) {
+    sh_bwd_multi_kernel<decltype(k)::value><<<g, 256, 0, stream>>>(dL_dcolors_dense, dense_stride, camera_positions,
+                                                                  camera_stride, num_cameras, sh_features, positions, N,
+                                                                  d_sh_features, d_positions, accumulate);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

@@ -8,18 +8,6 @@
 
 #define GSR_WAVE 64
 
-#define GSR_OK 0
-#define GSR_ERR_INVALID_ARGUMENT -1
-#define GSR_ERR_WORKSPACE_TOO_SMALL -2
-#define GSR_ERR_LAUNCH_FAILED -3
-#define GSR_ERR_UNSUPPORTED -4
-
-#define GSR_CHECK_LAUNCH()                                   \
-  do {                                                       \
-    hipError_t e__ = hipGetLastError();                      \
-    if (e__ != hipSuccess) return GSR_ERR_LAUNCH_FAILED;     \
-  } while (0)
-
 // Orders this wave's LDS accesses across its lanes (one wave per workgroup exchanges data through LDS without
 // s_barrier): a wavefront-scope fence + wave barrier.  Emits no instruction -- LDS operations of one wave execute in
 // order -- but keeps the compiler from moving the reads above the writes (or the next writes above the reads).

@@ -22,7 +22,7 @@
 // fixed-range call with that (lo, hi) does.
 #include "gsr_device.h"
 #include "gsr_histogram.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -311,7 +311,7 @@ size_t gsr_histogram_workspace_bytes(void) {
 int gsr_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows, int64_t M, const float* weight,
                   float eps, int32_t mode, float min_value, float lo, float hi, int32_t num_bins, int32_t auto_range,
                   int32_t trim, int64_t* counts, double* stats, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!counts || !stats || N < 0 || M < 0 || C < 1 || mode < 0 || mode > 2 || num_bins < 1 ||
       num_bins > GSR_HISTOGRAM_MAX_BINS || N > GSR_NEIGHBOURS_MAX_N || C > 65536)
     return GSR_ERR_INVALID_ARGUMENT;
@@ -351,15 +351,11 @@ int gsr_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows
   double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + replica_bytes);
   if (hipMemsetAsync(workspace, 0, replica_bytes, stream) != hipSuccess) return GSR_ERR_LAUNCH_FAILED;
   const int blocks = hist_blocks(in.W);
-  if (vec == 4) {
-    if (auto_range) hist_range_kernel<4><<<blocks, HB, 0, stream>>>(in, workspace);
-    hist_bin_kernel<4><<<blocks, HB, 0, stream>>>(in, lo, hi, auto_range ? 1 : 0, (int)num_bins, (int)trim, workspace,
-                                                  partials);
-  } else {
-    if (auto_range) hist_range_kernel<1><<<blocks, HB, 0, stream>>>(in, workspace);
-    hist_bin_kernel<1><<<blocks, HB, 0, stream>>>(in, lo, hi, auto_range ? 1 : 0, (int)num_bins, (int)trim, workspace,
-                                                  partials);
-  }
+  gsr_pick<1, 4>(vec, [&](auto v) {
+    if (auto_range) hist_range_kernel<decltype(v)::value><<<blocks, HB, 0, stream>>>(in, workspace);
+    hist_bin_kernel<decltype(v)::value><<<blocks, HB, 0, stream>>>(in, lo, hi, auto_range ? 1 : 0, (int)num_bins, (int)trim,
+                                                                   workspace, partials);
+  });
   GSR_CHECK_LAUNCH();
   hist_finalize_kernel<<<1, HB, 0, stream>>>(workspace, partials, blocks, (int)num_bins,
                                              reinterpret_cast<unsigned long long*>(counts), stats);

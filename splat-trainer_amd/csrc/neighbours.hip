@@ -19,7 +19,7 @@
 //                      then a fixed DPP tree, divided by the count; an empty cluster keeps its centroid.
 #include "gsr_device.h"
 #include "gsr_neighbours.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -30,7 +30,6 @@ constexpr int64_t KNN_MIN_SEGMENT = 1024;
 constexpr int KNN_MAX_SEGMENTS = 16;
 constexpr int KM_CH = 16;                   // sorted points per chunk of the centroid sums
 
-inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- kNN --------------------------------------------------------------------------------------------------------
@@ -307,25 +306,21 @@ size_t gsr_knn_workspace_bytes(int64_t N, int32_t k) {
 
 int gsr_knn(const float* points, int64_t N, int32_t k, float* dist2_out, int64_t* idx_out, float* scale_out,
             void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!points || !dist2_out || !idx_out || k < 1 || k > GSR_KNN_MAX_K || N < k + 1 || N > GSR_NEIGHBOURS_MAX_N)
     return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_knn_workspace_bytes(N, k)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   const int n = (int)N;
-  switch (k) {
-#define GSR_KNN_CASE(KK) \
-  case KK: return knn_launch<KK>(points, n, dist2_out, idx_out, scale_out, workspace, stream);
-    GSR_KNN_CASE(1) GSR_KNN_CASE(2) GSR_KNN_CASE(3) GSR_KNN_CASE(4) GSR_KNN_CASE(5) GSR_KNN_CASE(6) GSR_KNN_CASE(7)
-    GSR_KNN_CASE(8) GSR_KNN_CASE(9) GSR_KNN_CASE(10) GSR_KNN_CASE(11) GSR_KNN_CASE(12) GSR_KNN_CASE(13) GSR_KNN_CASE(14)
-    GSR_KNN_CASE(15) GSR_KNN_CASE(16)
-#undef GSR_KNN_CASE
-    default: return GSR_ERR_INVALID_ARGUMENT;
-  }
+  int rc = GSR_ERR_INVALID_ARGUMENT;
+  gsr_pick<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(k, [&](auto kk) {
+    rc = knn_launch<decltype(kk)::value>(points, n, dist2_out, idx_out, scale_out, workspace, stream);
+  });
+  return rc;
 }
 
 int gsr_assign_clusters(const float* x, int64_t N, const float* centroids, int64_t K, int64_t* labels_out,
                         void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!km_args_ok(x, N, centroids, K) || !labels_out) return GSR_ERR_INVALID_ARGUMENT;
   km_assign_kernel<<<grid_for(N, NB_BLOCK), NB_BLOCK, 0, stream>>>(x, (int)N, centroids, (int)K, labels_out, nullptr);
   GSR_CHECK_LAUNCH();
@@ -339,7 +334,7 @@ size_t gsr_kmeans_workspace_bytes(int64_t N, int64_t K) {
 
 int gsr_kmeans_iter(const float* x, int64_t N, float* centroids, int64_t K, int32_t iters, int64_t* labels_out,
                     void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!km_args_ok(x, N, centroids, K) || !labels_out || iters < 1) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_kmeans_workspace_bytes(N, K)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   const KmWork w = km_layout(N, K, workspace);

@@ -21,7 +21,7 @@
 #include <stdint.h>
 
 #include "gsr_device.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -202,11 +202,11 @@ extern "C" {
 int gsr_opt_point_weights(const int64_t* indexes, const float* visibility, int64_t M, float* step, float* vis_avg,
                           float beta1, float beta2, float vis_beta, float vis_smooth, int32_t bias_correction,
                           float* row_scale, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!indexes || !step || !row_scale || (visibility && !vis_avg)) return GSR_ERR_INVALID_ARGUMENT;
-  const unsigned blocks = (unsigned)((M + 255) / 256);
+  const unsigned blocks = grid_for(M, 256);
   opt_point_weights_kernel<<<blocks, 256, 0, stream>>>(indexes, visibility, M, step, vis_avg, beta1, beta2, vis_beta,
                                                        vis_smooth, bias_correction,
                                                        reinterpret_cast<float4*>(row_scale));
@@ -220,53 +220,39 @@ int gsr_opt_point_weights(const int64_t* indexes, const float* visibility, int64
 int gsr_opt_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* indexes,
                  const float* row_scale, const float* basis, int64_t M, int32_t D, int32_t type, int32_t algo, float lr,
                  float beta1, float beta2, float eps, float grad_clip, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || D < 1 || type < 0 || type > 2 || algo < 0 || algo > 1) return GSR_ERR_INVALID_ARGUMENT;
   if (type == OPT_LOCAL_VECTOR && (D != 3 || !basis)) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!param || !grad || !exp_avg || !exp_avg_sq || !indexes || !row_scale) return GSR_ERR_INVALID_ARGUMENT;
   OptArgs a{lr, beta1, beta2, eps, grad_clip, algo};
   const float4* rs = reinterpret_cast<const float4*>(row_scale);
-  const unsigned nb = (unsigned)((M + 255) / 256);
-#define GSR_OPT_NARROW(D_, T_)                                                                                         \
-  opt_step_narrow_kernel<D_, T_><<<nb, 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, indexes, rs, basis, M, a)
+  const unsigned nb = grid_for(M, 256);
+  const auto narrow = [&](auto d, auto t) {
+    opt_step_narrow_kernel<decltype(d)::value, decltype(t)::value><<<nb, 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq,
+                                                                                          indexes, rs, basis, M, a);
+  };
   if (type == OPT_LOCAL_VECTOR) {
-    GSR_OPT_NARROW(3, OPT_LOCAL_VECTOR);
+    narrow(std::integral_constant<int, 3>{}, std::integral_constant<int, OPT_LOCAL_VECTOR>{});
   } else if (D <= 4) {
-    if (type == OPT_SCALAR) {
-      switch (D) {
-        case 1: GSR_OPT_NARROW(1, OPT_SCALAR); break;
-        case 2: GSR_OPT_NARROW(2, OPT_SCALAR); break;
-        case 3: GSR_OPT_NARROW(3, OPT_SCALAR); break;
-        default: GSR_OPT_NARROW(4, OPT_SCALAR); break;
-      }
-    } else {
-      switch (D) {
-        case 1: GSR_OPT_NARROW(1, OPT_VECTOR); break;
-        case 2: GSR_OPT_NARROW(2, OPT_VECTOR); break;
-        case 3: GSR_OPT_NARROW(3, OPT_VECTOR); break;
-        default: GSR_OPT_NARROW(4, OPT_VECTOR); break;
-      }
-    }
+    gsr_pick<OPT_SCALAR, OPT_VECTOR>(type, [&](auto t) { gsr_pick<1, 2, 3, 4>(D, [&](auto d) { narrow(d, t); }); });
   } else {
-    const unsigned wb = (unsigned)((M + 15) / 16);
-    if (type == OPT_SCALAR)
-      opt_step_wide_kernel<OPT_SCALAR><<<wb, 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, indexes, rs, M, D, a);
-    else
-      opt_step_wide_kernel<OPT_VECTOR><<<wb, 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, indexes, rs, M, D, a);
+    const unsigned wb = grid_for(M, 16);
+    gsr_pick<OPT_SCALAR, OPT_VECTOR>(type, [&](auto t) {
+      opt_step_wide_kernel<decltype(t)::value><<<wb, 256, 0, stream>>>(param, grad, exp_avg, exp_avg_sq, indexes, rs, M, D, a);
+    });
   }
-#undef GSR_OPT_NARROW
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
 
 int gsr_point_basis(const float* log_scaling, const float* rotation_xyzw, const int64_t* indexes, int64_t M, float eps,
                     float* basis_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (M == 0) return GSR_OK;
   if (!log_scaling || !rotation_xyzw || !basis_out) return GSR_ERR_INVALID_ARGUMENT;
-  point_basis_kernel<<<(unsigned)((M + 255) / 256), 256, 0, stream>>>(log_scaling, rotation_xyzw, indexes, M, eps, basis_out);
+  point_basis_kernel<<<grid_for(M, 256), 256, 0, stream>>>(log_scaling, rotation_xyzw, indexes, M, eps, basis_out);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

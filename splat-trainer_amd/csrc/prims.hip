@@ -7,7 +7,7 @@
 //   (2) the O tile instances, emitted in depth order, by tile id (ceil(log2 tiles) bits, 2 passes)
 // so the big array moves through 2 passes instead of the 6 a fused 48-bit (tile|depth) key would need.
 #include "gsr_device.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -389,14 +389,6 @@ size_t sort_ws_bytes(int64_t n) {
   return 2 * hist + 5 * RS_MAX_BINS * sizeof(uint32_t) + 256;    // counts + offsets tables + digit totals
 }
 
-template <bool TWO, int ROUNDS, int BITS>
-void rs_launch_scatter(uint32_t nb, hipStream_t stream, const uint32_t* kin, const uint32_t* vin, const uint32_t* v2in,
-                       uint32_t* kout, uint32_t* vout, uint32_t* v2out, uint32_t n, int bit, uint32_t mask,
-                       const uint32_t* hist, const uint32_t* offs, const uint32_t* totals, const uint32_t* n_dev) {
-  rs_scatter_kernel<TWO, ROUNDS, BITS><<<nb, RS_THREADS, 0, stream>>>(kin, vin, v2in, kout, vout, v2out, n, bit, mask, hist,
-                                                                      offs, totals, nb, n_dev);
-}
-
 template <int BITS>
 int sort_passes(uint32_t* keys_a, uint32_t* vals_a, uint32_t* vals2_a, uint32_t* keys_b, uint32_t* vals_b,
                 uint32_t* vals2_b, int64_t n, int vals_are_iota, int begin_bit, int end_bit, void* workspace,
@@ -427,13 +419,12 @@ int sort_passes(uint32_t* keys_a, uint32_t* vals_a, uint32_t* vals2_a, uint32_t*
     GSR_CHECK_LAUNCH();
     rs_digit_scan_kernel<<<BINS, RS_THREADS, 0, stream>>>(hist, offs, nb, tot);
     GSR_CHECK_LAUNCH();
-    if (two) {
-      if (rounds == 4) rs_launch_scatter<true, 4, BITS>(nb, stream, kin, vin, v2in, kout, vout, v2out, (uint32_t)n, bit, mask, hist, offs, tot, n_dev);
-      else rs_launch_scatter<true, 16, BITS>(nb, stream, kin, vin, v2in, kout, vout, v2out, (uint32_t)n, bit, mask, hist, offs, tot, n_dev);
-    } else {
-      if (rounds == 4) rs_launch_scatter<false, 4, BITS>(nb, stream, kin, vin, v2in, kout, vout, v2out, (uint32_t)n, bit, mask, hist, offs, tot, n_dev);
-      else rs_launch_scatter<false, 16, BITS>(nb, stream, kin, vin, v2in, kout, vout, v2out, (uint32_t)n, bit, mask, hist, offs, tot, n_dev);
-    }
+    gsr_pick_bool(two, [&](auto tw) {
+      gsr_pick<4, 16>(rounds == 4 ? 4 : 16, [&](auto r) {
+        rs_scatter_kernel<decltype(tw)::value, decltype(r)::value, BITS><<<nb, RS_THREADS, 0, stream>>>(
+            kin, vin, v2in, kout, vout, v2out, (uint32_t)n, bit, mask, hist, offs, tot, nb, n_dev);
+      });
+    });
     GSR_CHECK_LAUNCH();
     where ^= 1;
     if (where == 1) { kin = keys_b; vin = vals_b; v2in = vals2_b; kout = keys_a; vout = vals_a; v2out = vals2_a; }
@@ -450,11 +441,12 @@ int sort_impl(uint32_t* keys_a, uint32_t* vals_a, uint32_t* vals2_a, uint32_t* k
   if (n > 0 && (!keys_a || !vals_a || !keys_b || !vals_b || (two && !vals2_b))) return GSR_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < sort_ws_bytes(n) || !workspace) return GSR_ERR_WORKSPACE_TOO_SMALL;
   if (n == 0) return 0;
-  if (rs_digit_bits(end_bit - begin_bit) == 9)
-    return sort_passes<9>(keys_a, vals_a, vals2_a, keys_b, vals_b, vals2_b, n, vals_are_iota, begin_bit, end_bit, workspace,
-                          n_dev, stream);
-  return sort_passes<8>(keys_a, vals_a, vals2_a, keys_b, vals_b, vals2_b, n, vals_are_iota, begin_bit, end_bit, workspace,
-                        n_dev, stream);
+  int where = 0;
+  gsr_pick<8, 9>(rs_digit_bits(end_bit - begin_bit) == 9 ? 9 : 8, [&](auto bits) {
+    where = sort_passes<decltype(bits)::value>(keys_a, vals_a, vals2_a, keys_b, vals_b, vals2_b, n, vals_are_iota, begin_bit,
+                                               end_bit, workspace, n_dev, stream);
+  });
+  return where;
 }
 
 }  // namespace
@@ -465,7 +457,7 @@ size_t gsr_scan_workspace_bytes(int64_t n) { return scan_ws_bytes((uint64_t)(n <
 
 int gsr_exclusive_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total_dev, void* workspace,
                            size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (n < 0 || n > 0xFFFFFFFFll) return GSR_ERR_INVALID_ARGUMENT;
   if (n > 0 && (!in || !out)) return GSR_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < scan_ws_bytes((uint64_t)n) || (n > SCAN_TILE && !workspace)) return GSR_ERR_WORKSPACE_TOO_SMALL;
@@ -474,7 +466,7 @@ int gsr_exclusive_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_
 
 int gsr_exclusive_scan_u32_checked(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total_dev,
                                    uint32_t* overflow_dev, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (n < 0 || n > 0xFFFFFFFFll || !overflow_dev) return GSR_ERR_INVALID_ARGUMENT;
   if (n > 0 && (!in || !out)) return GSR_ERR_INVALID_ARGUMENT;
   if (workspace_bytes < scan_ws_bytes((uint64_t)n) || (n > SCAN_TILE && !workspace)) return GSR_ERR_WORKSPACE_TOO_SMALL;
@@ -490,7 +482,7 @@ int gsr_sort_pairs_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uin
                        int vals_are_iota, int begin_bit, int end_bit, void* workspace, size_t workspace_bytes,
                        const uint32_t* n_dev, void* stream_) {
   return sort_impl(keys_a, vals_a, nullptr, keys_b, vals_b, nullptr, n, vals_are_iota, begin_bit, end_bit, workspace,
-                   workspace_bytes, n_dev, reinterpret_cast<hipStream_t>(stream_));
+                   workspace_bytes, n_dev, gsr_stream(stream_));
 }
 
 // Same, carrying a second value array (vals2) along with every key.
@@ -499,7 +491,7 @@ int gsr_sort_pairs2_u32(uint32_t* keys_a, uint32_t* vals_a, uint32_t* vals2_a, u
                         size_t workspace_bytes, const uint32_t* n_dev, void* stream_) {
   if (n > 0 && !vals2_a) return GSR_ERR_INVALID_ARGUMENT;
   return sort_impl(keys_a, vals_a, vals2_a, keys_b, vals_b, vals2_b, n, vals_are_iota, begin_bit, end_bit, workspace,
-                   workspace_bytes, n_dev, reinterpret_cast<hipStream_t>(stream_));
+                   workspace_bytes, n_dev, gsr_stream(stream_));
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //             plain read-modify-write).  visibility is a constant.
 #include "gsr_device.h"
 #include "gsr_dpp_reduce.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -227,7 +227,7 @@ size_t gsr_reg_workspace_bytes(int64_t M) {
 
 int gsr_reg_forward(const GsrReg* args, float* loss_out, float* terms_out, void* workspace, size_t workspace_bytes,
                     void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!reg_args_ok(args) || !loss_out || !terms_out) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_reg_workspace_bytes(args->M)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   const int blocks = reg_blocks(args->M);
@@ -243,10 +243,10 @@ int gsr_reg_forward(const GsrReg* args, float* loss_out, float* terms_out, void*
 
 int gsr_reg_backward(const GsrReg* args, const float* terms, const float* d_loss, float* d_opacity, float* d_depths,
                      float* d_specular, float* d_log_scaling, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!reg_args_ok(args) || !terms || !d_loss) return GSR_ERR_INVALID_ARGUMENT;
   if (args->M == 0) return GSR_OK;
-  reg_bwd_kernel<<<(unsigned)((args->M + REG_BLOCK - 1) / REG_BLOCK), REG_BLOCK, 0, stream>>>(
+  reg_bwd_kernel<<<grid_for(args->M, REG_BLOCK), REG_BLOCK, 0, stream>>>(
       *args, terms, d_loss, d_opacity, d_depths, d_specular, d_log_scaling);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
@@ -254,11 +254,11 @@ int gsr_reg_backward(const GsrReg* args, const float* terms, const float* d_loss
 
 int gsr_scene_post_step(float* rotation_xyzw, float* log_scaling, int64_t N, float eps, float lo, float hi,
                         void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (N < 0) return GSR_ERR_INVALID_ARGUMENT;
   if (N == 0) return GSR_OK;
   if (!rotation_xyzw || !log_scaling || (reinterpret_cast<uintptr_t>(rotation_xyzw) & 15)) return GSR_ERR_INVALID_ARGUMENT;
-  scene_post_step_kernel<<<(unsigned)((N + REG_BLOCK - 1) / REG_BLOCK), REG_BLOCK, 0, stream>>>(
+  scene_post_step_kernel<<<grid_for(N, REG_BLOCK), REG_BLOCK, 0, stream>>>(
       reinterpret_cast<float4*>(rotation_xyzw), log_scaling, N, eps, lo, hi);
   GSR_CHECK_LAUNCH();
   return GSR_OK;

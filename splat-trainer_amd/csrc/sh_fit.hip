@@ -17,7 +17,7 @@
 //                           j from its lane with a shuffle.  16 x 16 doubles per thread would not fit in registers.
 #include "gsr_device.h"
 #include "gsr_sh_fit.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -116,52 +116,39 @@ __global__ __launch_bounds__(SHF_SOLVE_BLOCK) void sh_fit_solve_kernel(const dou
   if (live && l == 0) weight[n] = (float)W;
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 }  // namespace
 
 extern "C" {
 
 int gsr_sh_fit_row_doubles(int32_t K) {
-  return (K == 1 || K == 4 || K == 9 || K == 16) ? gsr_shf_row_doubles(K) : 0;
+  return gsr_sh_degree_ok(K) ? gsr_shf_row_doubles(K) : 0;
 }
 
 int gsr_sh_fit_accumulate(const float* positions, int64_t N, const int64_t* indexes, int64_t M, const float* colors,
                           const float* weights, const float* camera_pos, int32_t K, double* acc, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!positions || !indexes || !colors || !weights || !camera_pos || !acc || N < 1 || N > GSR_NEIGHBOURS_MAX_N ||
       M < 1 || M > N || !gsr_sh_fit_row_doubles(K))
     return GSR_ERR_INVALID_ARGUMENT;
   const unsigned grid = grid_for(M, SHF_ACC_BLOCK / SHF_GROUP);
-#define GSR_SHF_ACC(KK)                                                                                               \
-  sh_fit_accumulate_kernel<KK><<<grid, SHF_ACC_BLOCK, 0, stream>>>(positions, N, indexes, M, colors, weights,          \
-                                                                   camera_pos, acc)
-  switch (K) {
-    case 1: GSR_SHF_ACC(1); break;
-    case 4: GSR_SHF_ACC(4); break;
-    case 9: GSR_SHF_ACC(9); break;
-    default: GSR_SHF_ACC(16); break;
-  }
-#undef GSR_SHF_ACC
+  gsr_pick_sh(K, [&](auto k) {
+    sh_fit_accumulate_kernel<decltype(k)::value><<<grid, SHF_ACC_BLOCK, 0, stream>>>(positions, N, indexes, M, colors, weights,
+                                                                                    camera_pos, acc);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }
 
 int gsr_sh_fit_solve(const double* acc, int64_t N, int32_t K, float ridge, float* sh_out, float* weight_out,
                      void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!acc || !sh_out || !weight_out || N < 1 || N > GSR_NEIGHBOURS_MAX_N || !gsr_sh_fit_row_doubles(K) ||
       !(ridge >= GSR_SHF_MIN_RIDGE) || !(ridge < INFINITY))
     return GSR_ERR_INVALID_ARGUMENT;
   const unsigned grid = grid_for(N, SHF_SOLVE_BLOCK / SHF_GROUP);
-#define GSR_SHF_SOLVE(KK) sh_fit_solve_kernel<KK><<<grid, SHF_SOLVE_BLOCK, 0, stream>>>(acc, N, ridge, sh_out, weight_out)
-  switch (K) {
-    case 1: GSR_SHF_SOLVE(1); break;
-    case 4: GSR_SHF_SOLVE(4); break;
-    case 9: GSR_SHF_SOLVE(9); break;
-    default: GSR_SHF_SOLVE(16); break;
-  }
-#undef GSR_SHF_SOLVE
+  gsr_pick_sh(K, [&](auto k) {
+    sh_fit_solve_kernel<decltype(k)::value><<<grid, SHF_SOLVE_BLOCK, 0, stream>>>(acc, N, ridge, sh_out, weight_out);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

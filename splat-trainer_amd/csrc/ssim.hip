@@ -8,7 +8,7 @@
 // Forward reads 2 and writes 3 planes, backward reads 5 and writes 1.
 // The mean is reduced without atomics: per-block partial sums in a fixed order, then one block adds them in order.
 #include "gsr_device.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -491,7 +491,7 @@ size_t gsr_ssim_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
 int gsr_ssim_forward(const float* img1, const float* img2, const int64_t* strides1_host, const int64_t* strides2_host,
                      int32_t B, int32_t C, int32_t H, int32_t W, int32_t crop, float* mean_out, float* dm_dmu1,
                      float* dm_dm11, float* dm_dm12, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || crop < 0 || !img1 || !img2 || !mean_out || !strides1_host || !strides2_host)
     return GSR_ERR_INVALID_ARGUMENT;
   if (W - 2 * crop <= 0 || H - 2 * crop <= 0) return GSR_ERR_INVALID_ARGUMENT;
@@ -504,12 +504,11 @@ int gsr_ssim_forward(const float* img1, const float* img2, const int64_t* stride
   const float inv_count = 1.f / ((float)B * C * (H - 2 * crop) * (float)(W - 2 * crop));
   float* block_sums = reinterpret_cast<float*>(workspace);
   const Gauss11 g = make_gauss();
-  if (train)
-    ssim_fwd_kernel<true><<<grid, 256, 0, stream>>>(img1, img2, s1, s2, C, H, W, crop, 0.01f * 0.01f, 0.03f * 0.03f,
-                                                   inv_count, g, block_sums, dm_dmu1, dm_dm11, dm_dm12);
-  else
-    ssim_fwd_kernel<false><<<grid, 256, 0, stream>>>(img1, img2, s1, s2, C, H, W, crop, 0.01f * 0.01f, 0.03f * 0.03f,
-                                                    inv_count, g, block_sums, nullptr, nullptr, nullptr);
+  gsr_pick_bool(train, [&](auto tr) {                          // without all three maps none is written
+    ssim_fwd_kernel<decltype(tr)::value><<<grid, 256, 0, stream>>>(
+        img1, img2, s1, s2, C, H, W, crop, 0.01f * 0.01f, 0.03f * 0.03f, inv_count, g, block_sums,
+        train ? dm_dmu1 : nullptr, train ? dm_dm11 : nullptr, train ? dm_dm12 : nullptr);
+  });
   GSR_CHECK_LAUNCH();
   ssim_finish_kernel<<<1, 256, 0, stream>>>(block_sums, nblocks, inv_count, mean_out);
   GSR_CHECK_LAUNCH();
@@ -521,7 +520,7 @@ int gsr_ssim_backward(const float* img1, const float* img2, const int64_t* strid
                       const int64_t* strides_out_host, int32_t B, int32_t C, int32_t H, int32_t W, const float* dm_dmu1,
                       const float* dm_dm11, const float* dm_dm12, const float* grad_scale_dev, float* d_img1,
                       void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !dm_dmu1 || !dm_dm11 || !dm_dm12 || !grad_scale_dev ||
       !d_img1 || !strides1_host || !strides2_host || !strides_out_host)
     return GSR_ERR_INVALID_ARGUMENT;
@@ -544,7 +543,7 @@ size_t gsr_msloss_workspace_bytes(int32_t H, int32_t W, int32_t C, int32_t level
 int gsr_msloss_forward(const float* image, const float* target, int32_t H, int32_t W, int32_t C, int32_t levels,
                        float w_l1, float w_mse, float w_ssim, float lo, float hi, float* metrics_out, void* workspace,
                        size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!ms_args_ok(H, W, C, levels) || !image || !target || !metrics_out || !(lo <= hi)) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_msloss_workspace_bytes(H, W, C, levels)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   uint8_t* base = reinterpret_cast<uint8_t*>(workspace);
@@ -586,7 +585,7 @@ int gsr_msloss_forward(const float* image, const float* target, int32_t H, int32
 int gsr_msloss_backward(const float* image, const float* target, int32_t H, int32_t W, int32_t C, int32_t levels,
                         float w_l1, float w_mse, float w_ssim, float lo, float hi, const float* grad_scale_dev,
                         void* workspace, size_t workspace_bytes, float* d_image, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!ms_args_ok(H, W, C, levels) || !image || !target || !grad_scale_dev || !d_image) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_msloss_workspace_bytes(H, W, C, levels)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   uint8_t* base = reinterpret_cast<uint8_t*>(workspace);
@@ -620,15 +619,16 @@ size_t gsr_pixel_loss_workspace_bytes(int64_t n) {
 // loss_out[0] = mean(f(clamp(image, lo, hi) - target)), f = square (kind 0) or abs (kind 1); image / target contiguous.
 int gsr_pixel_loss_forward(const float* image, const float* target, int64_t n, int32_t kind, float lo, float hi,
                            float* loss_out, void* workspace, size_t workspace_bytes, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (n <= 0 || !image || !target || !loss_out || (kind != 0 && kind != 1) || !(lo <= hi)) return GSR_ERR_INVALID_ARGUMENT;
   if (!workspace || workspace_bytes < gsr_pixel_loss_workspace_bytes(n)) return GSR_ERR_WORKSPACE_TOO_SMALL;
   if ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(target)) & 15) return GSR_ERR_INVALID_ARGUMENT;
   const int64_t want = (n + (int64_t)PL_THREADS * 4 - 1) / ((int64_t)PL_THREADS * 4);
   const int blocks = (int)(want < 1024 ? want : 1024);
   float* sums = reinterpret_cast<float*>(workspace);
-  if (kind == 0) pixel_loss_fwd_kernel<0><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, sums);
-  else pixel_loss_fwd_kernel<1><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, sums);
+  gsr_pick<0, 1>(kind, [&](auto k) {
+    pixel_loss_fwd_kernel<decltype(k)::value><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, sums);
+  });
   pixel_loss_finish_kernel<<<1, 256, 0, stream>>>(sums, blocks, 1.f / (float)n, loss_out);
   GSR_CHECK_LAUNCH();
   return GSR_OK;
@@ -637,12 +637,14 @@ int gsr_pixel_loss_forward(const float* image, const float* target, int64_t n, i
 // d_image = grad_scale_dev[0] * d loss / d image (zero where the clamp is active).
 int gsr_pixel_loss_backward(const float* image, const float* target, int64_t n, int32_t kind, float lo, float hi,
                             const float* grad_scale_dev, float* d_image, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (n <= 0 || !image || !target || !grad_scale_dev || !d_image || (kind != 0 && kind != 1)) return GSR_ERR_INVALID_ARGUMENT;
   const int64_t want = (n + PL_THREADS - 1) / PL_THREADS;
   const int blocks = (int)(want < 8192 ? want : 8192);
-  if (kind == 0) pixel_loss_bwd_kernel<0><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, 1.f / (float)n, grad_scale_dev, d_image);
-  else pixel_loss_bwd_kernel<1><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, 1.f / (float)n, grad_scale_dev, d_image);
+  gsr_pick<0, 1>(kind, [&](auto k) {
+    pixel_loss_bwd_kernel<decltype(k)::value><<<blocks, PL_THREADS, 0, stream>>>(image, target, n, lo, hi, 1.f / (float)n,
+                                                                                grad_scale_dev, d_image);
+  });
   GSR_CHECK_LAUNCH();
   return GSR_OK;
 }

@@ -15,7 +15,7 @@
 //   vf_finish_kernel      one wave per cluster: its slots lane-strided, then the fixed DPP tree; an empty cluster gives 0.
 #include "gsr_device.h"
 #include "gsr_visibility.h"
-#include "../../include/gsplat_hip.h"
+#include "gsr_host.h"
 
 namespace {
 
@@ -23,8 +23,6 @@ constexpr int VIS_BLOCK = 256;
 constexpr int FR_PPL = 4;                   // points per lane
 constexpr int FR_STEP = 4;                  // cameras per step of the sweep
 constexpr int FR_TILE = 64;                 // cameras per block-level combine (one per lane)
-
-inline unsigned grid_for(int64_t n, int64_t block) { return (unsigned)((n + block - 1) / block); }
 
 __global__ __launch_bounds__(VIS_BLOCK) void frustum_counts_kernel(const float* __restrict__ p, int N,
                                                                     const float* __restrict__ rec, int V, float depth_below,
@@ -179,7 +177,7 @@ extern "C" {
 
 int gsr_frustum_counts(const float* points, int64_t N, const float* records, int64_t V, float depth_below,
                        int32_t* point_counts_out, int32_t* camera_counts_out, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (!points || !records || N < 1 || N > GSR_NEIGHBOURS_MAX_N || V < 1 || V > GSR_VISIBILITY_MAX_CAMERAS)
     return GSR_ERR_INVALID_ARGUMENT;
   if (!point_counts_out && !camera_counts_out) return GSR_ERR_INVALID_ARGUMENT;
@@ -195,7 +193,7 @@ int gsr_view_features(const int64_t* point_idx, const float* point_vis, int64_t 
                       const uint32_t* sorted_labels, const uint32_t* sorted_points, const uint32_t* cluster_range,
                       int64_t N, int64_t K, float* dense_scratch, float* slot_scratch, float* features_out,
                       int32_t* point_visible, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipStream_t stream = gsr_stream(stream_);
   if (M < 0 || M > GSR_NEIGHBOURS_MAX_N || (M > 0 && (!point_idx || !point_vis)) || !sorted_labels || !sorted_points ||
       !cluster_range || N < 1 || N > GSR_NEIGHBOURS_MAX_N || K < 1 || K > GSR_NEIGHBOURS_MAX_N || !dense_scratch ||
       !slot_scratch || !features_out)

@@ -146,3 +146,91 @@ def test_inverse_map_edges():
     want = torch.full((n,), -1, dtype=torch.int32)
     want[torch.tensor(rows, dtype=torch.int64)] = torch.arange(len(rows), dtype=torch.int32)
     assert torch.equal(inv.cpu(), want), (n, rows[:5])
+
+
+def _colour_jacobian(sh, pos, idx, cam_pos):
+  """The oracle's colours (M,3) and d colour / d position (M,9), row-major 3 x 3 per splat, in fp64."""
+  pos = pos.double().requires_grad_(True)
+  col = oracle.evaluate_sh_at(sh.double(), pos, idx, cam_pos.double())
+  if not col.requires_grad:                                  # degree 0: the colour does not depend on the position
+    return col, torch.zeros(idx.numel(), 9, dtype=torch.float64)
+  rows = [torch.autograd.grad(col[:, c].sum(), pos, retain_graph=True)[0][idx] for c in range(3)]
+  return col.detach(), torch.stack(rows, dim=1).reshape(idx.numel(), 9)
+
+
+@pytest.mark.parametrize("K", [1, 4, 9, 16])
+def test_sh_arms_only_the_c_abi_reaches(K):
+  """Dispatch arms no Python path asks for: gsr_sh_backward with accumulate = 0 (the listed rows are written over stale
+  contents, the others left alone) and gsr_sh_forward with a Jacobian buffer at K = 1 (degree 0 has no view dependence:
+  zeros); the forward runs with and without the buffer.  64 visible splats; the oracle and tolerance of
+  test_evaluate_sh_at_matches_oracle."""
+  from splat_trainer_amd import _lib
+  lib, st, p = _lib.load(), _lib.current_stream_ptr(), _lib.ptr
+  torch.manual_seed(K)
+  N, M = 96, 64
+  sh, pos, cam = torch.randn(N, 3, K), torch.randn(N, 3) * 2, torch.tensor([0.3, -0.2, 4.0])
+  idx = torch.randperm(N)[:M].sort().values
+  g = torch.randn(M, 3)
+  sho, poso = sh.double().requires_grad_(True), pos.double().requires_grad_(True)
+  want = oracle.evaluate_sh_at(sho, poso, idx, cam.double())
+  (want * g.double()).sum().backward()
+  shd, posd, camd, idxd, gd = sh.cuda(), pos.cuda(), cam.cuda(), idx.cuda(), g.cuda()
+  col, plain = torch.empty(M, 3, device="cuda"), torch.empty(M, 3, device="cuda")
+  jac = torch.full((M, 9), 7.0, device="cuda")
+  _lib.check(lib.gsr_sh_forward(p(shd), p(posd), p(idxd), M, K, p(camd), p(plain), None, None, st), "gsr_sh_forward")
+  _lib.check(lib.gsr_sh_forward(p(shd), p(posd), p(idxd), M, K, p(camd), p(col), p(jac), None, st), "gsr_sh_forward")
+  assert rel_err(col, want) < TOL and rel_err(plain, want) < TOL
+  if K == 1:
+    assert jac.abs().max().item() == 0
+  else:
+    assert rel_err(jac, _colour_jacobian(sh, pos, idx, cam)[1]) < TOL
+  d_sh = torch.full((N, 3, K), 7.0, device="cuda")
+  d_pos = torch.full((N, 3), 7.0, device="cuda")
+  _lib.check(lib.gsr_sh_backward(p(gd), p(shd), p(posd), p(idxd), M, K, p(camd), p(jac), p(d_sh), p(d_pos), 0, st),
+             "gsr_sh_backward")
+  unseen = torch.ones(N, dtype=torch.bool)
+  unseen[idx] = False
+  assert rel_err(d_sh.cpu()[idx], sho.grad[idx]) < TOL
+  assert (d_sh.cpu()[unseen] == 7.0).all() and (d_pos.cpu()[unseen] == 7.0).all()
+  if K > 1:
+    assert rel_err(d_pos.cpu()[idx], poso.grad[idx]) < TOL
+  else:
+    assert d_pos.cpu()[idx].abs().max().item() == 0
+
+
+@pytest.mark.parametrize("K", [1, 4, 9, 16])
+def test_fused_projection_with_and_without_a_jacobian_buffer(K):
+  """gsr_project_sh_forward called directly, with and without a Jacobian buffer (the frame never asks for one at K = 1,
+  so only a direct call reaches that instantiation).  One frame of 64 splats on 32 x 32: the rows and screen scales of
+  the two forms are equal bit for bit (the render tests hold the frame's rows against the oracle), the colours and the
+  Jacobian match the oracle's evaluate_sh_at at the tolerance of this file; at K = 1 the Jacobian is zero."""
+  import ctypes as C
+  from splat_trainer_amd import _lib
+  lib, st, p = _lib.load(), _lib.current_stream_ptr(), _lib.ptr
+  g, cam = small_scene(64, 32, 32, sh_degree=int(round(K ** 0.5)) - 1)
+  camd = cam.to("cuda")
+  f32 = lambda t: t.detach().float().contiguous().cuda()
+  pos, ls, rot, al, sh = (f32(t) for t in (g.position, g.log_scaling, g.rotation, g.alpha_logit, g.feature))
+  T, proj, cam_pos = f32(camd.T_camera_world), f32(camd.projection), f32(camd.camera_position)
+  N = pos.shape[0]
+  assert (N, sh.shape[2]) == (64, K)
+  idx = torch.arange(N, dtype=torch.int64, device="cuda")
+  params = _lib.raster_params(sta.RasterConfig())
+
+  def run(jac):
+    rows, scale = torch.full((N, 16), 7.0, device="cuda"), torch.full((N, 2), 7.0, device="cuda")
+    _lib.check(lib.gsr_project_sh_forward(p(pos), p(ls), p(rot), p(al), p(sh), K, p(idx), N, p(T), p(proj), p(cam_pos),
+                                          C.byref(params), p(rows), p(scale), p(jac), None, None, 0, 0, st),
+               "gsr_project_sh_forward")
+    return rows.cpu(), scale.cpu()
+
+  plain = run(None)
+  jac = torch.full((N, 9), 7.0, device="cuda")
+  with_jac = run(jac)
+  assert torch.equal(plain[0], with_jac[0]) and torch.equal(plain[1], with_jac[1])
+  want_col, want_jac = _colour_jacobian(g.feature, g.position, idx.cpu(), cam.camera_position)
+  assert rel_err(with_jac[0][:, 7:10], want_col) < TOL
+  if K == 1:
+    assert jac.abs().max().item() == 0
+  else:
+    assert rel_err(jac, want_jac) < TOL

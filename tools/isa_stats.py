@@ -23,12 +23,13 @@ CSRC = os.path.join(ROOT, "splat-trainer_amd", "csrc")
 TRANS = ("v_exp_f32", "v_log_f32", "v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_sin_f32", "v_cos_f32")
 
 
-def compile_isa(source: str = "composite.hip") -> str:
+def compile_isa(source: str = "composite.hip", csrc: str = CSRC) -> str:
+  """gfx950 assembly of one source of `csrc` (this tree's csrc/, or the same directory of another checkout)."""
   hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
   with tempfile.TemporaryDirectory() as tmp:
     out = os.path.join(tmp, "k.s")
     subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value",
-                    "-Wno-unused-command-line-argument", "-o", out, source], check=True, cwd=CSRC,
+                    "-Wno-unused-command-line-argument", "-o", out, source], check=True, cwd=csrc,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return open(out).read()
 
