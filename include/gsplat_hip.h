@@ -901,6 +901,20 @@ int gsr_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows
                   float eps, int32_t mode, float min_value, float lo, float hi, int32_t num_bins, int32_t auto_range,
                   int32_t trim, int64_t* counts, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- area resize of uint8 images (the loader's cv2.resize(..., INTER_AREA); csrc/image.hip) ------------- */
+/* src (B, Hs, Ws, C) -> dst (B, Hd, Wd, C), both contiguous with interleaved channels, C in {1, 3}, Hd <= Hs, Wd <= Ws.
+ * The exact area mean in integers (csrc/gsr_image.h is the one statement of the arithmetic, shared with the host shim):
+ * on an axis of Ws Wd units source pixel i covers [i Wd, (i + 1) Wd) and destination pixel j covers [j Ws, (j + 1) Ws);
+ * wx(j, i) is the length of their overlap, wy likewise, S = sum_y sum_x wy wx src, D = Ws Hs and
+ * out = floor((2 S + D) / (2 D)): round half up.  No floating point: the result is a function of the input alone, the
+ * same bits on every run.  Equal sizes give a copy.
+ * Checked before any HIP call, in this order: a negative size is GSR_ERR_INVALID_ARGUMENT; C outside {1, 3}, or Ws or Hs
+ * above 32768, GSR_ERR_UNSUPPORTED; Wd > Ws, Hd > Hs (upscaling is left to the caller) or a zero destination size with a
+ * non-zero source GSR_ERR_INVALID_ARGUMENT; B == 0 or an empty image is GSR_OK with no launch and dst untouched; a NULL
+ * src or dst, looked at last, GSR_ERR_INVALID_ARGUMENT.  Neither pointer needs any alignment. */
+int gsr_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, uint8_t* dst, int32_t Hd,
+                             int32_t Wd, void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -31,6 +31,9 @@ from .camera_table import (Camera, CameraRigTable, CameraTable, Cameras, Label, 
                            check_indices, pose_adjacency, pose_matrices)
 from .normalization import Normalization, NormalizationConfig, median_knn
 from .histogram import Histogram, tensor_histogram
+from .image import resize_area
+from .colmap_io import read_model, write_model
+from .colmap import COLMAPDataset, export_colmap
 from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
                      StepValue)
 from .dataset import Dataset, ImageView, PointCloud, TensorDataset, expand_index, partition_stride, split_every
@@ -63,4 +66,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "PointCloud", "TensorDataset", "split_every", "partition_stride", "expand_index", "CloudInitConfig",
            "from_pointcloud", "from_scaled_pointcloud", "to_pointcloud", "get_initial_gaussians", "TargetOverlapConfig",
            "TargetOverlap", "TrainConfig", "TrainerState", "TrainingException", "NaNParameterException",
-           "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer"]
+           "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer",
+           "resize_area", "read_model", "write_model", "COLMAPDataset", "export_colmap"]

@@ -18,6 +18,7 @@
 #include "gsr_color.h"
 #include "gsr_eval.h"
 #include "gsr_histogram.h"
+#include "gsr_image.h"
 
 extern "C" {
 
@@ -653,6 +654,43 @@ int hm_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows,
     }
   }
   return 0;
+}
+
+// ---- area resize of uint8 images (gsr_image.h) ----
+int hm_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, uint8_t* dst, int32_t Hd,
+                            int32_t Wd) {
+  int launch = 0;
+  const int rc = gsr_image_check(src, B, Hs, Ws, C, dst, Hd, Wd, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrImageDivisor dv = gsr_image_divisor(Ws, Hs);
+  const int64_t n_el = (int64_t)Wd * C;
+  uint64_t* acc = new uint64_t[n_el];
+  for (int64_t b = 0; b < B; ++b) {
+    for (int32_t d = 0; d < Hd; ++d) {
+      for (int64_t e = 0; e < n_el; ++e) acc[e] = 0;
+      for (int32_t y = gsr_area_first(d, Hs, Hd); y <= gsr_area_last(d, Hs, Hd); ++y) {
+        const uint64_t wy = gsr_area_weight(d, y, Hs, Hd);
+        const uint8_t* row = src + ((b * Hs + y) * (int64_t)Ws) * C;
+        for (int32_t j = 0; j < Wd; ++j) {
+          const int32_t i_lo = gsr_area_first(j, Ws, Wd), i_hi = gsr_area_last(j, Ws, Wd);
+          for (int32_t c = 0; c < C; ++c) {
+            uint32_t h = 0;
+            for (int32_t i = i_lo; i <= i_hi; ++i) h += gsr_area_weight(j, i, Ws, Wd) * row[(int64_t)i * C + c];
+            acc[(int64_t)j * C + c] += wy * h;
+          }
+        }
+      }
+      uint8_t* out = dst + (b * Hd + d) * n_el;
+      for (int64_t e = 0; e < n_el; ++e) out[e] = (uint8_t)gsr_image_round_div(acc[e], dv.m, dv.D, dv.shift);
+    }
+  }
+  delete[] acc;
+  return GSR_OK;
+}
+
+void hm_image_round_div(const uint64_t* sum, int64_t n, int32_t Ws, int32_t Hs, uint32_t* out) {
+  const GsrImageDivisor dv = gsr_image_divisor(Ws, Hs);
+  for (int64_t i = 0; i < n; ++i) out[i] = gsr_image_round_div(sum[i], dv.m, dv.D, dv.shift);
 }
 
 }  // extern "C"

@@ -129,6 +129,14 @@ int hm_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows,
 /* key [n] uint32 of x [n] and back [n] = unkey(key) */
 void hm_hist_keys(const float* x, int64_t n, uint32_t* key, float* back);
 
+/* ---- area resize of uint8 images (gsr_image.h): the device's arithmetic in a plain loop ---- */
+/* gsr_image_resize_area_u8 on host memory, with its argument checks and its codes.  (Every name of this header starts
+ * with hm_, the prefix its reader takes; the package calls this one when a dataset has no GPU.) */
+int hm_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, uint8_t* dst, int32_t Hd,
+                            int32_t Wd);
+/* out [n] = floor((2 sum[i] + D) / (2 D)) by the multiply-shift of gsr_image_divisor(Ws, Hs); sum[i] <= 255 Ws Hs */
+void hm_image_round_div(const uint64_t* sum, int64_t n, int32_t Ws, int32_t Hs, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """The data interfaces the trainer is written against (the reference's ``dataset/dataset.py``, ``dataset/util.py`` and
 ``util/pointcloud.py``): ``ImageView``, the abstract ``Dataset``, ``PointCloud``, the split helpers, and ``TensorDataset``,
-a dataset held in memory.  The reference's file loaders (COLMAP, scan) need packages this project does not depend on
-and are not here: a user fills a ``TensorDataset`` or subclasses ``Dataset``.
+a dataset held in memory.  The COLMAP loader is ``colmap.COLMAPDataset``; the reference's scan loader needs a package
+this project does not depend on and is not here: for other sources a user fills a ``TensorDataset`` or subclasses
+``Dataset``.
 """
 from __future__ import annotations
 
