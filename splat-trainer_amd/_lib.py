@@ -224,3 +224,27 @@ def check(code: int, what: str) -> int:
     msg = load().gsr_error_string(code).decode()
     raise GsplatHipError(f"{what} failed: {msg} ({code})")
   return code
+
+
+def call(name: str, *args, note: str = "", lib=None) -> int:
+  """Calls the status-returning entry point ``name`` and returns its non-negative code; a negative one raises through
+  ``check`` under that same name, with ``note`` behind it (``"(depth)"``: which of a wrapper's several calls it was).
+  ``lib``: the library that holds ``name`` when it is not this one (the host-maths shim).  Calls that return a size
+  (``*_workspace_bytes``, ``gsr_camera_grad_partial_rows``) have no status: they go through ``load()`` directly."""
+  return check(getattr(lib or load(), name)(*args), name + note)
+
+
+def workspace(nbytes: int, device) -> torch.Tensor:
+  """A scratch buffer of ``nbytes`` bytes, at least one: the native wrappers refuse a NULL workspace even where they
+  need no byte of it (``!workspace`` comes before the size test), and ``ptr`` of an empty tensor is NULL.  Pass it as
+  ``ptr(ws), ws.numel()``."""
+  return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
+
+class on_device(torch.cuda.device):
+  """``with on_device(dev) as stream``: ``torch.cuda.device(dev)`` that hands out the raw handle of the stream current
+  there.  For the entry points that may be called with another device current; the frame path does not scope."""
+
+  def __enter__(self) -> int:
+    super().__enter__()
+    return current_stream_ptr()

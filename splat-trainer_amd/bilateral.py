@@ -21,7 +21,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import ptr as _ptr
+from ._args import f32
+from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 MIN_GRID, MAX_GRID = 2, 64
 
@@ -42,35 +43,30 @@ def _grid_shape(grids: torch.Tensor) -> Tuple[int, int, int, int]:
 class _SliceFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, grids, image, k):
-    lib = _lib.load()
     N, L, GH, GW = grids.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]
     H, W = image.shape[0], image.shape[1]
     out = torch.empty_like(image)
-    _lib.check(lib.gsr_bilagrid_slice_forward(_ptr(grids), N, L, GH, GW, k, _ptr(image), H, W, _ptr(out),
-                                              _lib.current_stream_ptr()), "gsr_bilagrid_slice_forward")
+    _lib.call("gsr_bilagrid_slice_forward", _ptr(grids), N, L, GH, GW, k, _ptr(image), H, W, _ptr(out), _stream())
     ctx.save_for_backward(grids, image)
     ctx.k = k
     return out
 
   @staticmethod
   def backward(ctx, g):
-    lib = _lib.load()
     grids, image = ctx.saved_tensors
     want_grids, want_image = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     if not (want_grids or want_image):
       return None, None, None
     N, L, GH, GW = grids.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]
     H, W = image.shape[0], image.shape[1]
-    go = g if (g.dtype is torch.float32 and g.is_contiguous()) else g.to(torch.float32).contiguous()
+    go = f32(g)
     d_image = torch.empty_like(image) if want_image else None
-    d_grids, ws, ws_bytes = None, None, 0
+    d_grids, ws = None, None
     if want_grids:
       d_grids = torch.zeros_like(grids)          # the kernels write slice k; the other images get no gradient
-      ws_bytes = lib.gsr_bilagrid_workspace_bytes(L, GH, GW)
-      ws = torch.empty(ws_bytes, dtype=torch.uint8, device=grids.device)
-    _lib.check(lib.gsr_bilagrid_slice_backward(_ptr(grids), N, L, GH, GW, ctx.k, _ptr(image), H, W, _ptr(go),
-                                               _ptr(d_image), _ptr(d_grids), _ptr(ws), ws_bytes,
-                                               _lib.current_stream_ptr()), "gsr_bilagrid_slice_backward")
+      ws = _lib.workspace(_lib.load().gsr_bilagrid_workspace_bytes(L, GH, GW), grids.device)
+    _lib.call("gsr_bilagrid_slice_backward", _ptr(grids), N, L, GH, GW, ctx.k, _ptr(image), H, W, _ptr(go), _ptr(d_image),
+              _ptr(d_grids), _ptr(ws), ws.numel() if want_grids else 0, _stream())
     return d_grids, d_image, None
 
 
@@ -95,18 +91,16 @@ def bilateral_correct(grids: torch.Tensor, image_idx: int, image: torch.Tensor) 
   k = int(image_idx)
   if not 0 <= k < N:
     raise ValueError(f"image_idx {k} outside [0, {N})")
-  x = image if (image.dtype is torch.float32 and image.is_contiguous()) else image.to(torch.float32).contiguous()
-  return _SliceFn.apply(grids, x, k)
+  return _SliceFn.apply(grids, f32(image, detach=False), k)
 
 
 class _TVFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, grids):
-    lib = _lib.load()
     N, L, GH, GW = grids.shape[0], grids.shape[2], grids.shape[3], grids.shape[4]
     tv = torch.empty(1, dtype=torch.float32, device=grids.device)
     d = torch.empty_like(grids) if ctx.needs_input_grad[0] else None
-    _tv_launch(lib, grids, N, L, GH, GW, 1.0, tv, d, False)
+    _tv_launch(grids, N, L, GH, GW, 1.0, tv, d, False)
     ctx.save_for_backward(d)
     return tv[0]
 
@@ -116,11 +110,10 @@ class _TVFn(torch.autograd.Function):
     return d * g.to(torch.float32)
 
 
-def _tv_launch(lib, grids, N, L, GH, GW, weight, tv, d, accumulate):
-  ws_bytes = lib.gsr_bilagrid_workspace_bytes(L, GH, GW)
-  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=grids.device)
-  _lib.check(lib.gsr_bilagrid_tv(_ptr(grids), N, L, GH, GW, float(weight), _ptr(tv), _ptr(d), 1 if accumulate else 0,
-                                 _ptr(ws), ws_bytes, _lib.current_stream_ptr()), "gsr_bilagrid_tv")
+def _tv_launch(grids, N, L, GH, GW, weight, tv, d, accumulate):
+  ws = _lib.workspace(_lib.load().gsr_bilagrid_workspace_bytes(L, GH, GW), grids.device)
+  _lib.call("gsr_bilagrid_tv", _ptr(grids), N, L, GH, GW, float(weight), _ptr(tv), _ptr(d), 1 if accumulate else 0,
+            _ptr(ws), ws.numel(), _stream())
 
 
 def bilateral_tv_loss(grids: torch.Tensor) -> torch.Tensor:
@@ -216,7 +209,7 @@ class BilateralCorrector:
       grids.grad = torch.empty_like(grids)
     elif not grids.grad.is_contiguous():
       grids.grad = grids.grad.contiguous()
-    _tv_launch(_lib.load(), grids.detach(), N, L, GH, GW, self.config.tv_weight, tv, grids.grad, accumulate)
+    _tv_launch(grids.detach(), N, L, GH, GW, self.config.tv_weight, tv, grids.grad, accumulate)
     self.bil_grid_optimizer.step()
     self.zero_grad()
     return tv[0]

@@ -30,9 +30,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
+from ._args import f32, on_one_device, require
+from ._lib import ptr as _ptr
 from .data_types import CameraParams
-
-_ptr = _lib.ptr
 
 
 class Label(Flag):
@@ -106,14 +106,14 @@ def check_indices(device: Optional[torch.device] = None) -> None:
       raise _lib.GsplatHipError(f"a pose table on cuda:{key} was indexed outside its rows (the launch read row 0 instead)")
 
 
-def _table_args(q: torch.Tensor, t: torch.Tensor, name: str):
-  if q.dim() != 2 or q.shape[1] != 4 or t.dim() != 2 or t.shape[1] != 3 or q.shape[0] != t.shape[0]:
-    raise ValueError(f"{name}: q must be (A, 4) and t (A, 3), got {tuple(q.shape)} and {tuple(t.shape)}")
-  if q.dtype is not torch.float32 or t.dtype is not torch.float32:
-    raise ValueError(f"{name}: q and t must be float32, got {q.dtype} and {t.dtype}")
-  if not (q.is_cuda and t.is_cuda):
-    raise _lib.GsplatHipError(f"{name} is on {q.device}: pose tables run on the HIP device only (there is no CPU "
-                              "fallback)")
+def _pose_table(q: torch.Tensor, t: torch.Tensor, name: str):
+  """The two tensors of a pose table: both shapes, then both dtypes, then the device, then the table's own row limit."""
+  tensors = {f"{name}'s q": q, f"{name}'s t": t}
+  require(f"{name}'s q", q, shape=("A", 4))
+  require(f"{name}'s t", t, shape=(q.shape[0], 3))
+  for label, x in tensors.items():
+    require(label, x, dtype=torch.float32)
+  on_one_device(tensors, what="a pose table")
   if not 1 <= q.shape[0] <= _lib.CONSTANTS["GSR_POSE_MAX_ROWS"]:
     raise ValueError(f"{name} must hold 1..{_lib.CONSTANTS['GSR_POSE_MAX_ROWS']} rows, got {q.shape[0]}")
 
@@ -137,17 +137,15 @@ def _index(indices: Any, rows: int, device: torch.device, name: str) -> torch.Te
 class _PoseFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, q_l, t_l, idx_l, q_r, t_r, idx_r):
-    lib = _lib.load()
     q_l, t_l = q_l.detach().contiguous(), t_l.detach().contiguous()
     rig = q_r is not None
     if rig:
       q_r, t_r = q_r.detach().contiguous(), t_r.detach().contiguous()
     B = idx_l.shape[0]
-    with torch.cuda.device(q_l.device):
+    with _lib.on_device(q_l.device) as stream:
       T = torch.empty((B, 4, 4), dtype=torch.float32, device=q_l.device)
-      _lib.check(lib.gsr_pose_forward(_ptr(q_l), _ptr(t_l), q_l.shape[0], _ptr(idx_l), _ptr(q_r), _ptr(t_r),
-                                      q_r.shape[0] if rig else 0, _ptr(idx_r), B, _ptr(T),
-                                      _status_word(q_l.device).data_ptr(), _lib.current_stream_ptr()), "gsr_pose_forward")
+      _lib.call("gsr_pose_forward", _ptr(q_l), _ptr(t_l), q_l.shape[0], _ptr(idx_l), _ptr(q_r), _ptr(t_r),
+                q_r.shape[0] if rig else 0, _ptr(idx_r), B, _ptr(T), _status_word(q_l.device).data_ptr(), stream)
     ctx.save_for_backward(*((q_l, t_l, idx_l, q_r, t_r, idx_r) if rig else (q_l, t_l, idx_l)))
     ctx.rig = rig
     return T
@@ -159,15 +157,13 @@ class _PoseFn(torch.autograd.Function):
     q_r, t_r, idx_r = saved[3:] if ctx.rig else (None, None, None)
     want_l = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
     want_r = ctx.rig and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
-    lib = _lib.load()
-    with torch.cuda.device(q_l.device):
-      G = G.detach().to(torch.float32).contiguous()
+    with _lib.on_device(q_l.device) as stream:
+      G = f32(G)
       d_q_l, d_t_l = (torch.empty_like(q_l), torch.empty_like(t_l)) if want_l else (None, None)
       d_q_r, d_t_r = (torch.empty_like(q_r), torch.empty_like(t_r)) if want_r else (None, None)
-      _lib.check(lib.gsr_pose_backward(_ptr(q_l), _ptr(t_l), q_l.shape[0], _ptr(idx_l), _ptr(q_r), _ptr(t_r),
-                                       q_r.shape[0] if ctx.rig else 0, _ptr(idx_r), idx_l.shape[0], _ptr(G), _ptr(d_q_l),
-                                       _ptr(d_t_l), _ptr(d_q_r), _ptr(d_t_r), _status_word(q_l.device).data_ptr(),
-                                       _lib.current_stream_ptr()), "gsr_pose_backward")
+      _lib.call("gsr_pose_backward", _ptr(q_l), _ptr(t_l), q_l.shape[0], _ptr(idx_l), _ptr(q_r), _ptr(t_r),
+                q_r.shape[0] if ctx.rig else 0, _ptr(idx_r), idx_l.shape[0], _ptr(G), _ptr(d_q_l), _ptr(d_t_l), _ptr(d_q_r),
+                _ptr(d_t_r), _status_word(q_l.device).data_ptr(), stream)
     return d_q_l, d_t_l, None, d_q_r, d_t_r, None
 
 
@@ -175,11 +171,11 @@ def pose_matrices(q: torch.Tensor, t: torch.Tensor, indices: torch.Tensor, q_rig
                   t_right: Optional[torch.Tensor] = None, indices_right: Optional[torch.Tensor] = None) -> torch.Tensor:
   """(B, 4, 4) transforms of rows ``indices`` of the table ``(q (A, 4), t (A, 3))`` and, with a right table, the
   products ``left[indices] @ right[indices_right]``: one autograd node over the two native launches."""
-  _table_args(q, t, "the pose table")
+  _pose_table(q, t, "the pose table")
   idx = _index(indices, q.shape[0], q.device, "indices")
   if q_right is None:
     return _PoseFn.apply(q, t, idx, None, None, None)
-  _table_args(q_right, t_right, "the right pose table")
+  _pose_table(q_right, t_right, "the right pose table")
   if q_right.device != q.device:
     raise ValueError(f"pose tables on different devices: {q.device} and {q_right.device}")
   idx_r = _index(indices_right, q_right.shape[0], q.device, "indices_right")

@@ -14,12 +14,13 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._args import on_one_device, require
+from ._lib import ptr as _ptr
 
 SUPPORTED = "hidden_features = 32, hidden_layers in {1, 2}, sh_degree in 2..5, 1 <= glo_features + point_features <= 64, " \
             "color_channels = 3"
@@ -111,23 +112,17 @@ def _check_config(config: ColorModelConfig, glo_features: int, point_features: i
                      f"{point_features}, color_channels={config.color_channels}; supported: {SUPPORTED}")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-  return None if t is None else t.data_ptr()
-
-
 class _ColorFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, model_c, L, pf, pos, cam, glo, *params):
     M = pos.shape[0]
-    lib = _lib.load()
     dev = pos.device
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev) as stream:
       diffuse = torch.empty((M, 3), dtype=torch.float32, device=dev)
       specular = torch.empty((M, 3), dtype=torch.float32, device=dev)
-      ws_bytes = lib.gsr_color_forward_workspace_bytes(C.byref(model_c))
-      ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-      _lib.check(lib.gsr_color_forward(C.byref(model_c), _ptr(pf), _ptr(pos), _ptr(cam), _ptr(glo), M, _ptr(diffuse),
-                                       _ptr(specular), _ptr(ws), ws_bytes, _lib.current_stream_ptr()), "gsr_color_forward")
+      ws = _lib.workspace(_lib.load().gsr_color_forward_workspace_bytes(C.byref(model_c)), dev)
+      _lib.call("gsr_color_forward", C.byref(model_c), _ptr(pf), _ptr(pos), _ptr(cam), _ptr(glo), M, _ptr(diffuse),
+                _ptr(specular), _ptr(ws), ws.numel(), stream)
     ctx.model_c = model_c
     ctx.L = L
     ctx.set_materialize_grads(False)         # an unused output's gradient arrives as None: that branch is skipped
@@ -139,8 +134,7 @@ class _ColorFn(torch.autograd.Function):
     pf, pos, cam, glo, *params = ctx.saved_tensors
     M = pos.shape[0]
     dev = pos.device
-    lib = _lib.load()
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev) as stream:
       dd = None if d_diffuse is None else d_diffuse.float().contiguous()
       ds = None if d_specular is None else d_specular.float().contiguous()
       d_pf = torch.empty_like(pf)
@@ -154,11 +148,9 @@ class _ColorFn(torch.autograd.Function):
         grads.d_bias[layer] = d_params[2 * i + 1].data_ptr()
       grads.d_glo = d_glo.data_ptr()
       grads.d_cam_pos = _ptr(d_cam)
-      ws_bytes = lib.gsr_color_backward_workspace_bytes(C.byref(ctx.model_c), M)
-      ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-      _lib.check(lib.gsr_color_backward(C.byref(ctx.model_c), _ptr(pf), _ptr(pos), _ptr(cam), _ptr(glo), M, _ptr(dd),
-                                        _ptr(ds), _ptr(d_pf), C.byref(grads), _ptr(ws), ws_bytes,
-                                        _lib.current_stream_ptr()), "gsr_color_backward")
+      ws = _lib.workspace(_lib.load().gsr_color_backward_workspace_bytes(C.byref(ctx.model_c), M), dev)
+      _lib.call("gsr_color_backward", C.byref(ctx.model_c), _ptr(pf), _ptr(pos), _ptr(cam), _ptr(glo), M, _ptr(dd), _ptr(ds),
+                _ptr(d_pf), C.byref(grads), _ptr(ws), ws.numel(), stream)
     return (None, None, d_pf if ctx.needs_input_grad[2] else None, None, d_cam,
             d_glo if ctx.needs_input_grad[5] else None, *d_params)
 
@@ -189,15 +181,10 @@ class ColorModel(nn.Module):
     return base + [self.directional_model.encode_dir.mlp.layers[0]] + dirm
 
   def _check_inputs(self, point_features, positions, cam_pos, glo_feature):
-    for name, t in (("point_features", point_features), ("positions", positions), ("cam_pos", cam_pos),
-                    ("glo_feature", glo_feature)):
-      if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
-      if not t.is_cuda:
-        raise _lib.GsplatHipError(f"{name} is on {t.device}: the colour model runs on the HIP device only "
-                                  "(there is no CPU fallback)")
-      if t.dtype is not torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
+    inputs = dict(point_features=point_features, positions=positions, cam_pos=cam_pos, glo_feature=glo_feature)
+    for name, t in inputs.items():
+      require(name, t, what="the colour model")             # (this module looks at the device before the dtype)
+      require(name, t, dtype=torch.float32)
     M = positions.shape[0]
     if point_features.dim() != 2 or point_features.shape != (M, self.point_features):
       raise ValueError(f"point_features must be (M, {self.point_features}) with M = {M}, got {tuple(point_features.shape)}")
@@ -207,13 +194,9 @@ class ColorModel(nn.Module):
       raise ValueError(f"cam_pos must hold 3 values, got {tuple(cam_pos.shape)}")
     if glo_feature.dim() != 2 or glo_feature.shape != (1, self.glo_features):
       raise ValueError(f"glo_feature must be (1, {self.glo_features}), got {tuple(glo_feature.shape)}")
-    devs = {t.device for t in (point_features, positions, cam_pos, glo_feature)}
-    for p in self.parameters():
-      devs.add(p.device)
-      if p.dtype is not torch.float32:
-        raise ValueError(f"colour model parameters must be float32, got {p.dtype}")
-    if len(devs) != 1:
-      raise ValueError(f"inputs and parameters on different devices: {sorted(map(str, devs))}")
+    for i, p in enumerate(self.parameters()):
+      inputs[f"parameter {i}"] = require("colour model parameters", p, dtype=torch.float32)
+    on_one_device(inputs)
 
   def forward(self, point_features: torch.Tensor, positions: torch.Tensor, cam_pos: torch.Tensor,
               glo_feature: torch.Tensor) -> Colors:

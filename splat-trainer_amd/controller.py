@@ -27,14 +27,14 @@ from __future__ import annotations
 
 from abc import ABCMeta, abstractmethod
 from dataclasses import dataclass, fields
-from typing import Any, Callable, Optional, Tuple, Union
+from typing import Callable, Optional, Tuple, Union
 
 import torch
 
 from . import _lib
+from ._args import on_one_device, require
+from ._lib import ptr as _ptr
 from .controller_math import PointState, find_split_prune_indexes, take_n
-
-_ptr = _lib.ptr
 
 Schedule = Union[float, int, Callable[[float], float]]
 GATE_MARGIN = 16.0                # soft_lt(opacity, threshold / 2, margin=16.0), mcmc_controller.py:95
@@ -268,19 +268,6 @@ class TargetController(Controller):
 
 
 # ----------------------------------------------------------------------------------------------------------------- mcmc
-def _check_rows(name: str, t: Any, shape: tuple, dtype: torch.dtype, device=None):
-  if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-    raise ValueError(f"{name} must be a tensor of shape {shape}, got "
-                     f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-  if t.dtype is not dtype:
-    raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-  if not t.is_cuda:
-    raise _lib.GsplatHipError(f"{name} is on {t.device}: the MCMC noise step runs on the HIP device only "
-                              "(there is no CPU fallback)")
-  if device is not None and t.device != device:
-    raise ValueError(f"inputs on different devices: {device}, {t.device}")
-
-
 def _u64(name: str, v) -> int:
   v = int(v)
   if not 0 <= v < 2 ** 64:
@@ -303,14 +290,14 @@ def mcmc_noise(position: torch.Tensor, log_scaling: torch.Tensor, rotation: torc
   underflows (opaque points) are not written.  One launch on the current stream, no host wait.  ``log_scaling`` (N, 3),
   ``rotation`` (N, 4) xyzw, ``alpha_logit`` (N, 1) or (N,) float32, ``points_in_view`` (N,) int16; contiguous device
   tensors, there is no CPU fallback."""
-  n = int(position.shape[0]) if isinstance(position, torch.Tensor) and position.dim() == 2 else -1
-  _check_rows("position", position, (n, 3), torch.float32)
+  n = int(require("position", position, shape=("N", 3)).shape[0])
+  f32 = torch.float32
+  for name, t, shape, dtype in (("position", position, (n, 3), f32), ("log_scaling", log_scaling, (n, 3), f32),
+                                ("rotation", rotation, (n, 4), f32), ("alpha_logit", alpha_logit, [(n, 1), (n,)], f32),
+                                ("points_in_view", points_in_view, (n,), torch.int16)):
+    require(name, t, shape=shape, dtype=dtype, what="the MCMC noise step")
+    on_one_device({"position": position, name: t})
   dev = position.device
-  _check_rows("log_scaling", log_scaling, (n, 3), torch.float32, dev)
-  _check_rows("rotation", rotation, (n, 4), torch.float32, dev)
-  flat = isinstance(alpha_logit, torch.Tensor) and alpha_logit.dim() == 1
-  _check_rows("alpha_logit", alpha_logit, (n,) if flat else (n, 1), torch.float32, dev)
-  _check_rows("points_in_view", points_in_view, (n,), torch.int16, dev)
   opacity_threshold, margin, noise_level, scale_eps = (float(opacity_threshold), float(margin), float(noise_level),
                                                        float(scale_eps))
   if not (opacity_threshold > 0 and margin >= 0 and noise_level >= 0 and scale_eps >= 0):
@@ -322,10 +309,9 @@ def mcmc_noise(position: torch.Tensor, log_scaling: torch.Tensor, rotation: torc
   if n == 0:
     return position
   ls, rot, a, views = (t.detach().contiguous() for t in (log_scaling, rotation, alpha_logit, points_in_view))
-  with torch.cuda.device(dev):
-    _lib.check(_lib.load().gsr_mcmc_noise(_ptr(position.detach()), _ptr(ls), _ptr(rot), _ptr(a), _ptr(views), n,
-                                          int(min_views), opacity_threshold, margin, noise_level, scale_eps, seed, step,
-                                          _lib.current_stream_ptr()), "gsr_mcmc_noise")
+  with _lib.on_device(dev) as stream:
+    _lib.call("gsr_mcmc_noise", _ptr(position.detach()), _ptr(ls), _ptr(rot), _ptr(a), _ptr(views), n, int(min_views),
+              opacity_threshold, margin, noise_level, scale_eps, seed, step, stream)
   return position
 
 
@@ -336,12 +322,11 @@ def mcmc_draws(num_points: int, seed: int, step: int, device="cuda") -> Tuple[to
   dev = torch.device(device)
   if dev.type != "cuda":
     raise _lib.GsplatHipError(f"mcmc_draws runs on the HIP device only, got {dev} (there is no CPU fallback)")
-  with torch.cuda.device(dev):
+  with _lib.on_device(dev) as stream:
     dev = torch.device("cuda", torch.cuda.current_device())
     words = torch.empty(n, 4, dtype=torch.int32, device=dev)
     normals = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().gsr_mcmc_draws(n, _u64("seed", seed), _u64("step", step), _ptr(words), _ptr(normals),
-                                          _lib.current_stream_ptr()), "gsr_mcmc_draws")
+    _lib.call("gsr_mcmc_draws", n, _u64("seed", seed), _u64("step", step), _ptr(words), _ptr(normals), stream)
   return words, normals
 
 

@@ -17,28 +17,26 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import current_stream_ptr as _stream, ptr as _p
+from ._args import f32
+from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 
 def select_n(values: torch.Tensor, n: int, descending: bool = False) -> torch.Tensor:
   """Bool mask with exactly ``min(n, N)`` entries set: the n smallest (``descending=False``) or largest values; among
   equal values the lowest indexes win (a stable argsort's choice); NaN orders above +inf."""
-  lib = _lib.load()
   if not values.is_cuda:
     raise _lib.GsplatHipError("select_n runs only on a HIP device (got a CPU tensor); there is no CPU fallback")
   if values.dim() != 1:
     raise ValueError("select_n takes a 1-D tensor")
   if n < 0:
     raise ValueError(f"n must be >= 0, got {n}")
-  v = values.detach().to(torch.float32).contiguous()
+  v = f32(values)
   N = v.shape[0]
   mask = torch.empty(N, dtype=torch.bool, device=v.device)
   if N == 0:
     return mask
-  ws_bytes = lib.gsr_select_workspace_bytes(N)
-  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device)
-  _lib.check(lib.gsr_select_n(_p(v), N, int(n), 1 if descending else 0, _p(mask), _p(ws), ws_bytes, _stream()),
-             "gsr_select_n")
+  ws = _lib.workspace(_lib.load().gsr_select_workspace_bytes(N), v.device)
+  _lib.call("gsr_select_n", _ptr(v), N, int(n), 1 if descending else 0, _ptr(mask), _ptr(ws), ws.numel(), _stream())
   return mask
 
 
@@ -47,7 +45,6 @@ def compact_rows(keep_mask: torch.Tensor, columns: Sequence[Tuple[torch.Tensor, 
   """For every ``(column, tail)``: ``cat([column[keep_mask], tail])`` -- ``tail = None`` appends ``n_tail`` zero rows.
   All columns move in ONE gather launch (after one count + scan and one read-back of the kept count, which sizes the
   outputs).  Columns are 4-byte-element tensors with N rows; a tail has the column's row shape."""
-  lib = _lib.load()
   if not keep_mask.is_cuda or keep_mask.dtype != torch.bool or keep_mask.dim() != 1:
     raise _lib.GsplatHipError("compact_rows needs a 1-D CUDA bool mask (no CPU fallback)")
   N = keep_mask.shape[0]
@@ -71,11 +68,9 @@ def compact_rows(keep_mask: torch.Tensor, columns: Sequence[Tuple[torch.Tensor, 
   blocks = max((N + 255) // 256, 1)
   offsets = torch.empty(blocks, dtype=torch.int32, device=dev)
   total = torch.empty(1, dtype=torch.int32, device=dev)
-  ws_bytes = lib.gsr_compact_workspace_bytes(N)
-  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+  ws = _lib.workspace(_lib.load().gsr_compact_workspace_bytes(N), dev)
   stream = _stream()
-  _lib.check(lib.gsr_compact_offsets(_p(keep), N, _p(offsets), _p(total), _p(ws), ws_bytes, stream),
-             "gsr_compact_offsets")
+  _lib.call("gsr_compact_offsets", _ptr(keep), N, _ptr(offsets), _ptr(total), _ptr(ws), ws.numel(), stream)
   kept = int(total.item())                  # the one host sync: the outputs' size is data dependent
   outs = [torch.empty((kept + n_tail,) + tuple(col.shape[1:]), dtype=col.dtype, device=dev) for col, _ in cols]
   if kept + n_tail == 0 or not cols:
@@ -88,8 +83,7 @@ def compact_rows(keep_mask: torch.Tensor, columns: Sequence[Tuple[torch.Tensor, 
     arr[i] = _lib.GsrColumnC(src=col.data_ptr() if N else None, dst=out.data_ptr(),
                              tail=tail.data_ptr() if (tail is not None and n_tail) else None,
                              width_dwords=max(width, 1))
-  _lib.check(lib.gsr_compact_columns(_p(keep), N, _p(offsets), kept, n_tail, arr, len(cols), stream),
-             "gsr_compact_columns")
+  _lib.call("gsr_compact_columns", _ptr(keep), N, _ptr(offsets), kept, n_tail, arr, len(cols), stream)
   return outs
 
 
@@ -108,7 +102,6 @@ def point_state_update(state, idx, screen_scale=None, visibility=None, split_sco
   """The fused update with every input group optional (``None`` leaves that part of the state alone); ``idx = None``:
   the rows are the points 0..M-1.  The data-parallel exchange uses it to replay only the two order-dependent EMAs per
   camera (distributed.exchange_point_stats)."""
-  lib = _lib.load()
   given = [t for t in (screen_scale, visibility, split_score, prune_cost) if t is not None]
   if not given:
     return state
@@ -116,9 +109,7 @@ def point_state_update(state, idx, screen_scale=None, visibility=None, split_sco
   if M == 0:
     return state
   # (float32 contiguous inputs -- what the renderer delivers -- pass through untouched: this runs once per camera)
-  f32 = lambda t: t if (t is None or (t.dtype is torch.float32 and t.is_contiguous())) else \
-      t.detach().to(torch.float32).contiguous()
-  scale = f32(screen_scale)
+  scale, vis, split, prune = (None if t is None else f32(t) for t in (screen_scale, visibility, split_score, prune_cost))
   cols = 2 if (scale is not None and scale.dim() == 2) else 1
   for t in (state.prune_cost, state.split_score, state.max_scale_px, state.visibility):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
@@ -128,12 +119,10 @@ def point_state_update(state, idx, screen_scale=None, visibility=None, split_sco
   if visible_sum is not None and not (visible_sum.is_cuda and visible_sum.dtype == torch.float32 and
                                       visible_sum.is_contiguous() and visible_sum.shape == state.visibility.shape):
     raise ValueError("visible_sum must be a contiguous float32 CUDA tensor shaped like state.visibility")
-  _lib.check(lib.gsr_point_state_add(_p(idx if idx.is_contiguous() else idx.contiguous()) if idx is not None else None, _p(scale), cols,
-                                     _p(f32(visibility)), _p(f32(split_score)), _p(f32(prune_cost)), M,
-                                     float(split_alpha), float(prune_alpha), _p(state.prune_cost), _p(state.split_score),
-                                     _p(state.max_scale_px), _p(state.points_in_view), _p(state.visibility),
-                                     _p(visible_sum), _stream()),
-             "gsr_point_state_add")
+  _lib.call("gsr_point_state_add", _ptr(idx if idx.is_contiguous() else idx.contiguous()) if idx is not None else None,
+            _ptr(scale), cols, _ptr(vis), _ptr(split), _ptr(prune), M, float(split_alpha), float(prune_alpha),
+            _ptr(state.prune_cost), _ptr(state.split_score), _ptr(state.max_scale_px), _ptr(state.points_in_view),
+            _ptr(state.visibility), _ptr(visible_sum), _stream())
   return state
 
 
@@ -155,7 +144,6 @@ def dp_pack(block: torch.Tensor, num_points: int, idx: torch.Tensor, d_colour: t
   M = int(idx.shape[0])
   if block.numel() != dp_block_floats(N) or block.dtype != torch.float32 or not block.is_contiguous():
     raise ValueError("dp_pack: block must be a contiguous float32 tensor of 6 N + 3 elements")
-  f32 = lambda t: t.detach().to(torch.float32).contiguous()
   scale = f32(screen_scale)
   if not block.is_cuda:
     block[:3 * N] = 0
@@ -170,13 +158,11 @@ def dp_pack(block: torch.Tensor, num_points: int, idx: torch.Tensor, d_colour: t
       sums[:N].index_add_(0, idx, f32(visibility))
       sums[N:].index_add_(0, idx, (visibility > 0).to(torch.float32))
     return block
-  lib = _lib.load()
   cols = 2 if scale.dim() == 2 else 1
-  _lib.check(lib.gsr_dp_pack(_p(idx.contiguous()) if M < N else None, _p(f32(d_colour)), _p(f32(split_score)),
-                             _p(f32(prune_cost)), _p(scale), cols, _p(f32(camera_pos)), M, N, _p(block),
-                             _p(f32(visibility)) if visibility is not None else None,
-                             _p(sums[:N]) if visibility is not None else None,
-                             _p(sums[N:]) if visibility is not None else None, _stream()), "gsr_dp_pack")
+  _lib.call("gsr_dp_pack", _ptr(idx.contiguous()) if M < N else None, _ptr(f32(d_colour)), _ptr(f32(split_score)),
+            _ptr(f32(prune_cost)), _ptr(scale), cols, _ptr(f32(camera_pos)), M, N, _ptr(block),
+            _ptr(f32(visibility)) if visibility is not None else None, _ptr(sums[:N]) if visibility is not None else None,
+            _ptr(sums[N:]) if visibility is not None else None, _stream())
   return block
 
 
@@ -202,12 +188,11 @@ def dp_replay(state, blocks: torch.Tensor, slots: torch.Tensor, num_points: int,
       state.visibility += sums[:N]
       state.points_in_view += sums[N:].to(state.points_in_view.dtype)
     return state
-  lib = _lib.load()
-  _lib.check(lib.gsr_dp_replay(_p(blocks), int(blocks.shape[1]), _p(slots), int(slots.shape[0]), N, float(split_alpha),
-                               float(prune_alpha), _p(state.split_score), _p(state.prune_cost), _p(state.max_scale_px),
-                               _p(sums[:N]) if sums is not None else None, _p(sums[N:]) if sums is not None else None,
-                               _p(state.visibility) if sums is not None else None,
-                               _p(state.points_in_view) if sums is not None else None, _stream()), "gsr_dp_replay")
+  _lib.call("gsr_dp_replay", _ptr(blocks), int(blocks.shape[1]), _ptr(slots), int(slots.shape[0]), N, float(split_alpha),
+            float(prune_alpha), _ptr(state.split_score), _ptr(state.prune_cost), _ptr(state.max_scale_px),
+            _ptr(sums[:N]) if sums is not None else None, _ptr(sums[N:]) if sums is not None else None,
+            _ptr(state.visibility) if sums is not None else None, _ptr(state.points_in_view) if sums is not None else None,
+            _stream())
   return state
 
 
@@ -230,7 +215,6 @@ def dp_pack_sharded(factors: torch.Tensor, scores: torch.Tensor, scale_max: torc
   G, cpr, _, L = scores.shape
   if (factors is not None and factors.numel() != 3 * N + 3) or L != dp_slice_len(N, G) or scale_max.numel() != N:
     raise ValueError("dp_pack_sharded: buffer shapes do not match (N, ranks)")
-  f32 = lambda t: t.detach().to(torch.float32).contiguous()
   scale = f32(screen_scale)
   if not scores.is_cuda:
     if factors is not None:                 # (None: the block was packed earlier, dp_pack_factors_rows)
@@ -247,12 +231,11 @@ def dp_pack_sharded(factors: torch.Tensor, scores: torch.Tensor, scale_max: torc
       sums[N:].index_add_(0, idx, (visibility > 0).to(torch.float32))
     return
   cols = 2 if scale.dim() == 2 else 1
-  _lib.check(_lib.load().gsr_dp_pack_sharded(
-      _p(idx.contiguous()) if M < N else None, _p(f32(d_colour)) if factors is not None else None, _p(f32(split_score)),
-      _p(f32(prune_cost)), _p(scale), cols, _p(f32(camera_pos)), M, N, int(G), int(cpr), int(slot), _p(factors), _p(scores),
-      _p(scale_max),
-      _p(f32(visibility)) if visibility is not None else None, _p(sums[:N]) if visibility is not None else None,
-      _p(sums[N:]) if visibility is not None else None, _stream()), "gsr_dp_pack_sharded")
+  _lib.call("gsr_dp_pack_sharded", _ptr(idx.contiguous()) if M < N else None,
+            _ptr(f32(d_colour)) if factors is not None else None, _ptr(f32(split_score)), _ptr(f32(prune_cost)), _ptr(scale),
+            cols, _ptr(f32(camera_pos)), M, N, int(G), int(cpr), int(slot), _ptr(factors), _ptr(scores), _ptr(scale_max),
+            _ptr(f32(visibility)) if visibility is not None else None, _ptr(sums[:N]) if visibility is not None else None,
+            _ptr(sums[N:]) if visibility is not None else None, _stream())
 
 
 def dp_pack_factors_rows(factors: torch.Tensor, num_points: int, idx: torch.Tensor, grad_rows: torch.Tensor,
@@ -267,8 +250,8 @@ def dp_pack_factors_rows(factors: torch.Tensor, num_points: int, idx: torch.Tens
     factors[:3 * N].view(N, 3).index_copy_(0, idx, grad_rows[:, 8:11].to(torch.float32))
     factors[3 * N:] = camera_pos.to(torch.float32)
     return
-  _lib.check(_lib.load().gsr_dp_pack_factors_rows(_p(idx.contiguous()), _p(grad_rows), _p(camera_pos.detach().to(torch.float32).contiguous()),
-                                                  M, N, _p(factors), _stream()), "gsr_dp_pack_factors_rows")
+  _lib.call("gsr_dp_pack_factors_rows", _ptr(idx.contiguous()), _ptr(grad_rows), _ptr(f32(camera_pos)), M, N, _ptr(factors),
+            _stream())
 
 
 def dp_replay_slice(state, recv: torch.Tensor, rank: int, num_cameras: int, num_points: int, slice_out: torch.Tensor,
@@ -291,9 +274,8 @@ def dp_replay_slice(state, recv: torch.Tensor, rank: int, num_cameras: int, num_
       p[seen] = exp_lerp(prune_alpha, p[seen], cell[1, :count][seen])
     slice_out[0, :count], slice_out[1, :count] = s, p
     return
-  _lib.check(_lib.load().gsr_dp_replay_slice(_p(recv), int(G), int(cpr), N, int(rank), int(num_cameras), float(split_alpha),
-                                             float(prune_alpha), _p(state.split_score), _p(state.prune_cost),
-                                             _p(slice_out), _stream()), "gsr_dp_replay_slice")
+  _lib.call("gsr_dp_replay_slice", _ptr(recv), int(G), int(cpr), N, int(rank), int(num_cameras), float(split_alpha),
+            float(prune_alpha), _ptr(state.split_score), _ptr(state.prune_cost), _ptr(slice_out), _stream())
 
 
 def dp_finish(state, gathered: torch.Tensor, num_points: int, scale_max: Optional[torch.Tensor] = None,
@@ -312,9 +294,8 @@ def dp_finish(state, gathered: torch.Tensor, num_points: int, scale_max: Optiona
       state.visibility += sums[:N]
       state.points_in_view += sums[N:].to(state.points_in_view.dtype)
     return state
-  _lib.check(_lib.load().gsr_dp_finish(_p(gathered), int(G), N, _p(state.split_score), _p(state.prune_cost),
-                                       _p(scale_max), _p(state.max_scale_px) if scale_max is not None else None,
-                                       _p(sums[:N]) if sums is not None else None, _p(sums[N:]) if sums is not None else None,
-                                       _p(state.visibility) if sums is not None else None,
-                                       _p(state.points_in_view) if sums is not None else None, _stream()), "gsr_dp_finish")
+  _lib.call("gsr_dp_finish", _ptr(gathered), int(G), N, _ptr(state.split_score), _ptr(state.prune_cost), _ptr(scale_max),
+            _ptr(state.max_scale_px) if scale_max is not None else None, _ptr(sums[:N]) if sums is not None else None,
+            _ptr(sums[N:]) if sums is not None else None, _ptr(state.visibility) if sums is not None else None,
+            _ptr(state.points_in_view) if sums is not None else None, _stream())
   return state

@@ -113,10 +113,8 @@ def _rebuild_sh_gradient(blocks: torch.Tensor, width: int, sh_features, position
   from . import _lib
   N, _, K = sh_features.shape
   base = blocks.data_ptr()
-  _lib.check(_lib.load().gsr_sh_backward_multi(base, width, base + 4 * 3 * N, width, blocks.shape[0],
-                                               sh_features.data_ptr(), positions.data_ptr(), N, K, d_sh.data_ptr(),
-                                               None if d_pos is None else d_pos.data_ptr(), int(accumulate),
-                                               _lib.current_stream_ptr()), "gsr_sh_backward_multi")
+  _lib.call("gsr_sh_backward_multi", base, width, base + 4 * 3 * N, width, blocks.shape[0], sh_features.data_ptr(),
+            positions.data_ptr(), N, K, d_sh.data_ptr(), _lib.ptr(d_pos), int(accumulate), _lib.current_stream_ptr())
 
 
 def exchange_sh_factors(collector, camera_slots: Sequence[int], cameras_per_rank: int, sh_features: torch.Tensor,

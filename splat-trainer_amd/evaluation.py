@@ -22,7 +22,8 @@ from typing import Any, Dict, Iterable, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import current_stream_ptr as _stream, ptr as _ptr
+from ._args import f32
+from ._lib import ptr as _ptr
 
 __all__ = ["mse_to_psnr", "compute_psnr", "fit_colors", "fit_colors_batch", "image_metrics", "Evaluation",
            "evaluate_scene"]
@@ -34,14 +35,6 @@ def mse_to_psnr(mse):
 
 def compute_psnr(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
   return mse_to_psnr(torch.nn.functional.mse_loss(a, b))
-
-
-def _plain(t: torch.Tensor) -> torch.Tensor:
-  """float32, contiguous and 16-byte aligned, without a copy when it already is."""
-  t = t.detach()
-  if t.dtype is not torch.float32 or not t.is_contiguous():
-    t = t.to(torch.float32).contiguous()
-  return t.clone() if t.data_ptr() & 15 else t
 
 
 def fit_colors_batch(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps: float = 0.5 / 255) -> torch.Tensor:
@@ -57,15 +50,12 @@ def fit_colors_batch(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, e
     raise ValueError("fit_colors needs at least one pixel")
   if not (0 <= int(num_iters) <= 64) or not (0.0 <= float(eps) < 0.5):
     raise ValueError("num_iters must be in 0..64 and eps in [0, 0.5)")
-  lib = _lib.load()
-  x, r = _plain(img), _plain(ref)
+  x, r = f32(img, align16=True), f32(ref, align16=True)
   P = x.numel() // 3
-  with torch.cuda.device(x.device):
+  with _lib.on_device(x.device) as stream:
     out = torch.empty_like(x)
-    ws_bytes = lib.gsr_color_fit_workspace_bytes(P)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    _lib.check(lib.gsr_color_fit(_ptr(x), _ptr(r), P, int(num_iters), float(eps), _ptr(out), _ptr(ws), ws_bytes,
-                                 _stream()), "gsr_color_fit")
+    ws = _lib.workspace(_lib.load().gsr_color_fit_workspace_bytes(P), x.device)
+    _lib.call("gsr_color_fit", _ptr(x), _ptr(r), P, int(num_iters), float(eps), _ptr(out), _ptr(ws), ws.numel(), stream)
   return out
 
 
@@ -88,13 +78,10 @@ def image_metrics(image: torch.Tensor, source: torch.Tensor, out: Optional[torch
     out = torch.empty(3, dtype=torch.float32, device=image.device)
   elif (out.shape != (3,) or out.dtype is not torch.float32 or not out.is_contiguous() or out.device != image.device):
     raise ValueError("out must be a contiguous float32 tensor of three elements on the images' device")
-  lib = _lib.load()
-  x, s = _plain(image), _plain(source)
-  with torch.cuda.device(x.device):
-    ws_bytes = lib.gsr_image_metrics_workspace_bytes(H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    _lib.check(lib.gsr_image_metrics(_ptr(x), _ptr(s), H, W, _ptr(out), _ptr(ws), ws_bytes, _stream()),
-               "gsr_image_metrics")
+  x, s = f32(image, align16=True), f32(source, align16=True)
+  with _lib.on_device(x.device) as stream:
+    ws = _lib.workspace(_lib.load().gsr_image_metrics_workspace_bytes(H, W), x.device)
+    _lib.call("gsr_image_metrics", _ptr(x), _ptr(s), H, W, _ptr(out), _ptr(ws), ws.numel(), stream)
   return out
 
 

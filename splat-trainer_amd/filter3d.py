@@ -24,10 +24,10 @@ from typing import Any
 import torch
 
 from . import _lib
+from ._args import f32, on_one_device, require
+from ._lib import ptr as _ptr
 from .data_types import Gaussians3D
 from .visibility import _query_args
-
-_ptr = _lib.ptr
 
 
 def sampling_rate(cameras: Any, points: torch.Tensor, margin: float = 0.15, unseen: str = "min") -> torch.Tensor:
@@ -42,13 +42,11 @@ def sampling_rate(cameras: Any, points: torch.Tensor, margin: float = 0.15, unse
   if not margin >= 0.0:
     raise ValueError(f"margin must be >= 0, got {margin}")
   cams, p = _query_args(cameras, points)
-  lib = _lib.load()
-  with torch.cuda.device(p.device):
+  with _lib.on_device(p.device) as stream:
     rec = cams.records()
     focal = cams.intrinsics[:, :2].max(dim=1).values.contiguous()
     rate = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
-    _lib.check(lib.gsr_sampling_rate(_ptr(p), p.shape[0], _ptr(rec), _ptr(focal), rec.shape[0], margin, _ptr(rate),
-                                     _lib.current_stream_ptr()), "gsr_sampling_rate")
+    _lib.call("gsr_sampling_rate", _ptr(p), p.shape[0], _ptr(rec), _ptr(focal), rec.shape[0], margin, _ptr(rate), stream)
     if unseen == "min":
       seen = rate > 0
       lowest = torch.where(seen, rate, rate.new_full((), float("inf"))).min()          # inf when nothing is sampled
@@ -56,22 +54,14 @@ def sampling_rate(cameras: Any, points: torch.Tensor, margin: float = 0.15, unse
   return rate
 
 
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-  """``t`` detached, contiguous and 16-byte aligned (the kernels move four rows at a time)."""
-  t = t.detach().contiguous()
-  return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 class _Filter3dFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, log_scaling, alpha_logit, rate, strength):
-    lib = _lib.load()
-    ls, a = _aligned(log_scaling), _aligned(alpha_logit)
-    N = ls.shape[0]
-    with torch.cuda.device(ls.device):
+    ls, a = f32(log_scaling, align16=True), f32(alpha_logit, align16=True)     # (the kernels move four rows at a time)
+    with _lib.on_device(ls.device) as stream:
       out_ls, out_a = torch.empty_like(ls), torch.empty_like(a)
-      _lib.check(lib.gsr_filter3d_forward(_ptr(ls), _ptr(a), _ptr(rate), N, strength, _ptr(out_ls), _ptr(out_a),
-                                          _lib.current_stream_ptr()), "gsr_filter3d_forward")
+      _lib.call("gsr_filter3d_forward", _ptr(ls), _ptr(a), _ptr(rate), ls.shape[0], strength, _ptr(out_ls), _ptr(out_a),
+                stream)
     ctx.save_for_backward(ls, a, rate)
     ctx.strength = strength
     return out_ls, out_a
@@ -79,12 +69,11 @@ class _Filter3dFn(torch.autograd.Function):
   @staticmethod
   def backward(ctx, g_ls, g_a):
     ls, a, rate = ctx.saved_tensors
-    lib = _lib.load()
-    with torch.cuda.device(ls.device):
-      g_ls, g_a = _aligned(g_ls), _aligned(g_a)         # (an unused output arrives as zeros)
+    with _lib.on_device(ls.device) as stream:
+      g_ls, g_a = f32(g_ls, align16=True), f32(g_a, align16=True)         # (an unused output arrives as zeros)
       d_ls, d_a = torch.empty_like(ls), torch.empty_like(a)
-      _lib.check(lib.gsr_filter3d_backward(_ptr(ls), _ptr(a), _ptr(rate), ls.shape[0], ctx.strength, _ptr(g_ls), _ptr(g_a),
-                                           _ptr(d_ls), _ptr(d_a), _lib.current_stream_ptr()), "gsr_filter3d_backward")
+      _lib.call("gsr_filter3d_backward", _ptr(ls), _ptr(a), _ptr(rate), ls.shape[0], ctx.strength, _ptr(g_ls), _ptr(g_a),
+                _ptr(d_ls), _ptr(d_a), stream)
     return d_ls, d_a, None, None
 
 
@@ -97,24 +86,12 @@ def smooth_gaussians(gaussians: Gaussians3D, rate: torch.Tensor, strength: float
   if not strength >= 0.0:
     raise ValueError(f"strength must be >= 0, got {strength}")
   ls, a = gaussians.log_scaling, gaussians.alpha_logit
-  N = int(ls.shape[0])
-  if ls.dim() != 2 or ls.shape[1] != 3 or tuple(a.shape) != (N, 1):
-    raise ValueError(f"log_scaling must be (N, 3) and alpha_logit (N, 1), got {tuple(ls.shape)} and {tuple(a.shape)}")
-  if ls.dtype is not torch.float32 or a.dtype is not torch.float32:
-    raise ValueError(f"log_scaling and alpha_logit must be float32, got {ls.dtype} and {a.dtype}")
-  if not isinstance(rate, torch.Tensor) or tuple(rate.shape) != (N,):
-    raise ValueError(f"rate must be a tensor of shape ({N},), got "
-                     f"{tuple(rate.shape) if isinstance(rate, torch.Tensor) else type(rate).__name__}")
-  if rate.dtype is not torch.float32:
-    raise ValueError(f"rate must be float32, got {rate.dtype}")
-  for name, t in (("log_scaling", ls), ("alpha_logit", a), ("rate", rate)):
-    if not t.is_cuda:
-      raise _lib.GsplatHipError(f"{name} is on {t.device}: the 3-D smoothing filter runs on the HIP device only "
-                                "(there is no CPU fallback)")
-  if not ls.device == a.device == rate.device:
-    raise ValueError(f"inputs on different devices: {ls.device}, {a.device}, {rate.device}")
+  N = int(require("log_scaling", ls, shape=("N", 3), dtype=torch.float32).shape[0])
+  require("alpha_logit", a, shape=(N, 1), dtype=torch.float32)
+  require("rate", rate, shape=(N,), dtype=torch.float32)
+  on_one_device(dict(log_scaling=ls, alpha_logit=a, rate=rate), what="the 3-D smoothing filter")
   if strength == 0.0 or N == 0:
     return gaussians
-  out_ls, out_a = _Filter3dFn.apply(ls, a, _aligned(rate), strength)
+  out_ls, out_a = _Filter3dFn.apply(ls, a, f32(rate, align16=True), strength)
   return Gaussians3D(position=gaussians.position, rotation=gaussians.rotation, log_scaling=out_ls, alpha_logit=out_a,
                      feature=gaussians.feature)

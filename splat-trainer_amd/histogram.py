@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import f32
 
 MAX_BINS = _lib.CONSTANTS["GSR_HISTOGRAM_MAX_BINS"]
 MODES = {None: 0, "drop": 1, "clamp": 2}
@@ -47,14 +48,10 @@ def _check_range(range) -> Optional[Tuple[float, float]]:
 
 def _rows_2d(values: torch.Tensor) -> torch.Tensor:
   """``values`` as float32 (N, C) contiguous: integer and half inputs are converted, 0-d and 1-d become one column."""
-  v = values.detach()
-  if v.dtype is not torch.float32:
-    v = v.to(torch.float32)
+  v = f32(values)
   if v.dim() < 2:
-    v = v.reshape(-1, 1)
-  elif v.dim() > 2:
-    v = v.reshape(v.shape[0], -1)
-  return v.contiguous()
+    return v.reshape(-1, 1)
+  return v.reshape(v.shape[0], -1) if v.dim() > 2 else v
 
 
 def _host_histogram(v: np.ndarray, rows, weight, eps: float, mode: int, min_value: float, range, num_bins: int,
@@ -109,7 +106,7 @@ def _host_histogram(v: np.ndarray, rows, weight, eps: float, mode: int, min_valu
 def _workspace(device: torch.device, stream: int) -> torch.Tensor:
   key = (device.index, stream)
   if key not in _workspaces:
-    _workspaces[key] = torch.empty(_lib.load().gsr_histogram_workspace_bytes(), dtype=torch.uint8, device=device)
+    _workspaces[key] = _lib.workspace(_lib.load().gsr_histogram_workspace_bytes(), device)
   return _workspaces[key]
 
 
@@ -258,15 +255,12 @@ def tensor_histogram(values: torch.Tensor, num_bins: int = 64, range=None, rows:
                                     num_bins, bool(trim))
     buffer = torch.from_numpy(np.concatenate([counts, stats.view(np.int64)]))
     return Histogram._of(buffer, fixed)
-  lib = _lib.load()
-  with torch.cuda.device(v.device):
-    stream = _lib.current_stream_ptr()
+  with _lib.on_device(v.device) as stream:
     workspace = _workspace(v.device, stream)
     buffer = torch.empty(num_bins + 8, dtype=torch.int64, device=v.device)
     lo, hi = fixed or (0., 0.)
-    _lib.check(lib.gsr_histogram(_lib.ptr(v), N, C, None if rows is None else rows.data_ptr(),
-                                 0 if rows is None else rows.shape[0], _lib.ptr(weight), float(eps), mode, float(min_value),
-                                 lo, hi, num_bins, int(fixed is None), int(bool(trim)), buffer.data_ptr(),
-                                 buffer.data_ptr() + 8 * num_bins, workspace.data_ptr(), workspace.numel(), stream),
-               "gsr_histogram")
+    _lib.call("gsr_histogram", _lib.ptr(v), N, C, None if rows is None else rows.data_ptr(),
+              0 if rows is None else rows.shape[0], _lib.ptr(weight), float(eps), mode, float(min_value), lo, hi, num_bins,
+              int(fixed is None), int(bool(trim)), buffer.data_ptr(), buffer.data_ptr() + 8 * num_bins,
+              workspace.data_ptr(), workspace.numel(), stream)
   return Histogram._of(buffer, fixed)

@@ -21,24 +21,25 @@ from . import _lib
 HOST_LIB_PATH = os.path.join(_lib.PKG_DIR, "libgsr_hostmath.so")
 HOST_HEADER_PATH = os.path.join(_lib.PKG_DIR, "csrc", "hostmath_shim.h")
 MAX_SIDE = 32768
-_host_fn = None
+_host_lib = None
 _lock = threading.Lock()
 
 
-def _host_resize():
-  """``hm_image_resize_area_u8`` of the host library, bound from its header's declaration (once)."""
-  global _host_fn
+def _host():
+  """The host library with ``hm_image_resize_area_u8`` bound from its header's declaration (once)."""
+  global _host_lib
   with _lock:
-    if _host_fn is None:
+    if _host_lib is None:
       if not os.path.exists(HOST_LIB_PATH):
         raise _lib.GsplatHipError(f"{HOST_LIB_PATH} not found: build it with `python splat-trainer_amd/build.py`")
       with open(HOST_HEADER_PATH) as f:
         functions = _lib.parse_header(f.read(), prefix="hm_", filename="hostmath_shim.h")[2]
       name = "hm_image_resize_area_u8"
-      fn = getattr(C.CDLL(HOST_LIB_PATH), name)
+      lib = C.CDLL(HOST_LIB_PATH)
+      fn = getattr(lib, name)
       fn.restype, fn.argtypes = _lib.make_prototypes({name: functions[name]}, {})[name]
-      _host_fn = fn
-  return _host_fn
+      _host_lib = lib
+  return _host_lib
 
 
 def resize_area(images: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
@@ -56,10 +57,10 @@ def resize_area(images: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     raise ValueError(f"size {(Hd, Wd)} must be non-empty and no larger than the images' {(Hs, Ws)}: only downscaling")
   dst = torch.empty((B, Hd, Wd, channels), dtype=torch.uint8, device=src.device)
   if dst.numel() > 0:
+    args = (src.data_ptr(), B, Hs, Ws, channels, dst.data_ptr(), Hd, Wd)
     if src.is_cuda:
-      with torch.cuda.device(src.device):
-        _lib.check(_lib.load().gsr_image_resize_area_u8(src.data_ptr(), B, Hs, Ws, channels, dst.data_ptr(), Hd, Wd,
-                                                        _lib.current_stream_ptr()), "gsr_image_resize_area_u8")
+      with _lib.on_device(src.device) as stream:
+        _lib.call("gsr_image_resize_area_u8", *args, stream)
     else:
-      _lib.check(_host_resize()(src.data_ptr(), B, Hs, Ws, channels, dst.data_ptr(), Hd, Wd), "hm_image_resize_area_u8")
+      _lib.call("hm_image_resize_area_u8", *args, lib=_host())
   return dst if images.dim() == 4 else dst[0]

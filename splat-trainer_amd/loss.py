@@ -15,6 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._args import f32
 from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 
@@ -25,35 +26,29 @@ def _strides(t: torch.Tensor):
 class _SSIMFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, img1, img2, crop, train):
-    lib = _lib.load()
     x = img1.detach().to(torch.float32)
     y = img2.detach().to(torch.float32)
     B, Cc, H, W = x.shape
     dev = x.device
     mean = torch.empty(1, dtype=torch.float32, device=dev)
     maps = torch.empty(3, B, Cc, H, W, dtype=torch.float32, device=dev) if train else None
-    ws_bytes = lib.gsr_ssim_workspace_bytes(B, Cc, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.load().gsr_ssim_workspace_bytes(B, Cc, H, W), dev)
     m = (maps[0], maps[1], maps[2]) if train else (None, None, None)
-    _lib.check(lib.gsr_ssim_forward(_ptr(x), _ptr(y), _strides(x), _strides(y), B, Cc, H, W, crop, _ptr(mean),
-                                    _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), _ptr(ws), ws_bytes, _stream()),
-               "gsr_ssim_forward")
+    _lib.call("gsr_ssim_forward", _ptr(x), _ptr(y), _strides(x), _strides(y), B, Cc, H, W, crop, _ptr(mean), _ptr(m[0]),
+              _ptr(m[1]), _ptr(m[2]), _ptr(ws), ws.numel(), _stream())
     ctx.save_for_backward(x, y, maps)
     ctx.in_dtype = img1.dtype
     return mean[0]
 
   @staticmethod
   def backward(ctx, g):
-    lib = _lib.load()
     x, y, maps = ctx.saved_tensors
     if maps is None:
       raise _lib.GsplatHipError("fused_ssim(train=False) result cannot be back-propagated")
     B, Cc, H, W = x.shape
-    gs = g if (g.dtype is torch.float32 and g.is_contiguous()) else g.detach().to(torch.float32).contiguous()   # one scalar
     d = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
-    _lib.check(lib.gsr_ssim_backward(_ptr(x), _ptr(y), _strides(x), _strides(y), _strides(d), B, Cc, H, W,
-                                     _ptr(maps[0]), _ptr(maps[1]), _ptr(maps[2]), _ptr(gs), _ptr(d), _stream()),
-               "gsr_ssim_backward")
+    _lib.call("gsr_ssim_backward", _ptr(x), _ptr(y), _strides(x), _strides(y), _strides(d), B, Cc, H, W, _ptr(maps[0]),
+              _ptr(maps[1]), _ptr(maps[2]), _ptr(f32(g)), _ptr(d), _stream())                   # (g: one scalar)
     return d.to(ctx.in_dtype), None, None, None
 
 
@@ -74,29 +69,22 @@ def fused_ssim(img1: torch.Tensor, img2: torch.Tensor, padding: str = "same", tr
 class _PixelLossFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, image, target, kind, lo, hi):
-    lib = _lib.load()
-    plain = lambda a: a.dtype is torch.float32 and a.is_contiguous()
-    x = image.detach() if plain(image) else image.detach().to(torch.float32).contiguous()
-    t = target if (plain(target) and target.shape == x.shape) else target.detach().to(torch.float32).expand_as(x).contiguous()
+    x = f32(image)
+    t = f32(target if target.shape == x.shape else target.detach().to(torch.float32).expand_as(x))
     n = x.numel()
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    ws_bytes = lib.gsr_pixel_loss_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    _lib.check(lib.gsr_pixel_loss_forward(_ptr(x), _ptr(t), n, kind, lo, hi, _ptr(out), _ptr(ws), ws_bytes, _stream()),
-               "gsr_pixel_loss_forward")
+    ws = _lib.workspace(_lib.load().gsr_pixel_loss_workspace_bytes(n), x.device)
+    _lib.call("gsr_pixel_loss_forward", _ptr(x), _ptr(t), n, kind, lo, hi, _ptr(out), _ptr(ws), ws.numel(), _stream())
     ctx.save_for_backward(x, t)
     ctx.args = (kind, lo, hi, image.dtype)
     return out[0]
 
   @staticmethod
   def backward(ctx, g):
-    lib = _lib.load()
     x, t = ctx.saved_tensors
     kind, lo, hi, dtype = ctx.args
-    gs = g.detach().to(torch.float32).reshape(1).contiguous()
     d = torch.empty_like(x)
-    _lib.check(lib.gsr_pixel_loss_backward(_ptr(x), _ptr(t), x.numel(), kind, lo, hi, _ptr(gs), _ptr(d), _stream()),
-               "gsr_pixel_loss_backward")
+    _lib.call("gsr_pixel_loss_backward", _ptr(x), _ptr(t), x.numel(), kind, lo, hi, _ptr(f32(g)), _ptr(d), _stream())
     return d.to(dtype), None, None, None, None
 
 
@@ -123,30 +111,26 @@ class _MSLossFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, image, target, weights, levels, lo, hi):
-    lib = _lib.load()
     x = image.detach()
     t = target.detach()
     H, W, Cc = x.shape
-    ws_bytes = lib.gsr_msloss_workspace_bytes(H, W, Cc, levels)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace(_lib.load().gsr_msloss_workspace_bytes(H, W, Cc, levels), x.device)
     metrics = torch.empty(3 + levels, dtype=torch.float32, device=x.device)
-    _lib.check(lib.gsr_msloss_forward(_ptr(x), _ptr(t), H, W, Cc, levels, weights[0], weights[1], weights[2], lo, hi,
-                                      _ptr(metrics), _ptr(ws), ws_bytes, _stream()), "gsr_msloss_forward")
+    _lib.call("gsr_msloss_forward", _ptr(x), _ptr(t), H, W, Cc, levels, weights[0], weights[1], weights[2], lo, hi,
+              _ptr(metrics), _ptr(ws), ws.numel(), _stream())
     ctx.save_for_backward(x, t, ws)
-    ctx.args = (weights, levels, lo, hi, ws_bytes)
+    ctx.args = (weights, levels, lo, hi)
     ctx.mark_non_differentiable(metrics)
     return metrics[0], metrics
 
   @staticmethod
   def backward(ctx, g, _g_metrics):
-    lib = _lib.load()
     x, t, ws = ctx.saved_tensors
-    weights, levels, lo, hi, ws_bytes = ctx.args
+    weights, levels, lo, hi = ctx.args
     H, W, Cc = x.shape
-    gs = g.detach().to(torch.float32).reshape(1).contiguous()
     d = torch.empty_like(x)
-    _lib.check(lib.gsr_msloss_backward(_ptr(x), _ptr(t), H, W, Cc, levels, weights[0], weights[1], weights[2], lo, hi,
-                                       _ptr(gs), _ptr(ws), ws_bytes, _ptr(d), _stream()), "gsr_msloss_backward")
+    _lib.call("gsr_msloss_backward", _ptr(x), _ptr(t), H, W, Cc, levels, weights[0], weights[1], weights[2], lo, hi,
+              _ptr(f32(g)), _ptr(ws), ws.numel(), _ptr(d), _stream())
     return d, None, None, None, None, None
 
 

@@ -16,42 +16,32 @@ from typing import Any, Tuple
 import torch
 
 from . import _lib
+from ._args import require
+from ._lib import ptr as _ptr
 
 
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
-def _points(x: Any, name: str) -> torch.Tensor:
-  if not isinstance(x, torch.Tensor):
-    raise ValueError(f"{name} must be a torch.Tensor of shape (N, 3), got {type(x).__name__}")
-  if x.dim() != 2 or x.shape[1] != 3:
-    raise ValueError(f"{name} must have shape (N, 3), got {tuple(x.shape)}")
-  if x.dtype is not torch.float32:
-    raise ValueError(f"{name} must be float32, got {x.dtype}")
-  if not x.is_cuda:
-    raise ValueError(f"{name} must be on the HIP device (cuda); there is no CPU fallback")
+def _cloud(x: Any, name: str) -> torch.Tensor:
+  """``x`` as the searches take it: (N, 3) float32 on the HIP device (ValueError otherwise), 1..NEIGHBOURS_MAX_N rows,
+  contiguous."""
+  require(name, x, shape=("N", 3), dtype=torch.float32, what="the neighbour search", device_error=ValueError)
   if not 1 <= x.shape[0] <= _lib.NEIGHBOURS_MAX_N:
     raise ValueError(f"{name} must hold 1..{_lib.NEIGHBOURS_MAX_N} points, got {x.shape[0]}")
   return x if x.is_contiguous() else x.contiguous()
 
 
 def _knn(points: torch.Tensor, k: int, want_scale: bool):
-  p = _points(points, "points")
+  p = _cloud(points, "points")
   N = p.shape[0]
   if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.KNN_MAX_K:
     raise ValueError(f"k must be an int in 1..{_lib.KNN_MAX_K}, got {k!r}")
   if N < k + 1:
     raise ValueError(f"kNN with k={k} needs at least k + 1 = {k + 1} points, got {N}")
-  lib = _lib.load()
-  with torch.cuda.device(p.device):
+  with _lib.on_device(p.device) as stream:
     dist2 = torch.empty((N, k), dtype=torch.float32, device=p.device)
     idx = torch.empty((N, k), dtype=torch.int64, device=p.device)
     scale = torch.empty(N, dtype=torch.float32, device=p.device) if want_scale else None
-    ws_bytes = lib.gsr_knn_workspace_bytes(N, k)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=p.device)
-    _lib.check(lib.gsr_knn(_ptr(p), N, k, _ptr(dist2), _ptr(idx), _ptr(scale), _ptr(ws), ws_bytes,
-                           _lib.current_stream_ptr()), "gsr_knn")
+    ws = _lib.workspace(_lib.load().gsr_knn_workspace_bytes(N, k), p.device)
+    _lib.call("gsr_knn", _ptr(p), N, k, _ptr(dist2), _ptr(idx), _ptr(scale), _ptr(ws), ws.numel(), stream)
   return dist2, idx, scale
 
 
@@ -71,7 +61,7 @@ def estimate_scale(pointcloud: Any, num_neighbors: int = 3) -> torch.Tensor:
 
 
 def _centroids(centroids: Any, x: torch.Tensor) -> torch.Tensor:
-  c = _points(centroids, "centroids")
+  c = _cloud(centroids, "centroids")
   if c.device != x.device:
     raise ValueError(f"x on {x.device} and centroids on {c.device}")
   return c
@@ -80,13 +70,11 @@ def _centroids(centroids: Any, x: torch.Tensor) -> torch.Tensor:
 def assign_clusters(x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
   """The nearest centroid of every point, (N,) int64: argmin over j of the squared distance, ties to the lowest j; a
   point whose distances are all NaN gets 0."""
-  xp = _points(x, "x")
+  xp = _cloud(x, "x")
   c = _centroids(centroids, xp)
-  lib = _lib.load()
-  with torch.cuda.device(xp.device):
+  with _lib.on_device(xp.device) as stream:
     labels = torch.empty(xp.shape[0], dtype=torch.int64, device=xp.device)
-    _lib.check(lib.gsr_assign_clusters(_ptr(xp), xp.shape[0], _ptr(c), c.shape[0], _ptr(labels),
-                                       _lib.current_stream_ptr()), "gsr_assign_clusters")
+    _lib.call("gsr_assign_clusters", _ptr(xp), xp.shape[0], _ptr(c), c.shape[0], _ptr(labels), stream)
   return labels
 
 
@@ -94,18 +82,15 @@ def kmeans_iter(x: torch.Tensor, centroids: torch.Tensor, iters: int = 100) -> T
   """``iters`` Lloyd iterations, enqueued by one native call: assign every point, then set each centroid to the float32
   mean of its points (an empty cluster keeps its centroid).  Updates ``centroids`` in place and returns
   ``(labels, centroids)``; the labels are those of the last assignment, made before the last update."""
-  xp = _points(x, "x")
+  xp = _cloud(x, "x")
   c = _centroids(centroids, xp)           # a copy when centroids is not contiguous: written back below
   if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= 2**31 - 1:
     raise ValueError(f"iters must be an int >= 1, got {iters!r}")
   N, K = xp.shape[0], centroids.shape[0]
-  lib = _lib.load()
-  with torch.cuda.device(xp.device):
+  with _lib.on_device(xp.device) as stream:
     labels = torch.empty(N, dtype=torch.int64, device=xp.device)
-    ws_bytes = lib.gsr_kmeans_workspace_bytes(N, K)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xp.device)
-    _lib.check(lib.gsr_kmeans_iter(_ptr(xp), N, _ptr(c), K, iters, _ptr(labels), _ptr(ws), ws_bytes,
-                                   _lib.current_stream_ptr()), "gsr_kmeans_iter")
+    ws = _lib.workspace(_lib.load().gsr_kmeans_workspace_bytes(N, K), xp.device)
+    _lib.call("gsr_kmeans_iter", _ptr(xp), N, _ptr(c), K, iters, _ptr(labels), _ptr(ws), ws.numel(), stream)
     if c is not centroids:
       centroids.copy_(c)
   return labels, centroids
@@ -114,7 +99,7 @@ def kmeans_iter(x: torch.Tensor, centroids: torch.Tensor, iters: int = 100) -> T
 def kmeans(x: torch.Tensor, k: int = 10, iters: int = 100) -> Tuple[torch.Tensor, torch.Tensor]:
   """k-means from k distinct points of ``x`` chosen as the reference does: ``x[torch.randperm(N)[:k]]`` on the CPU
   default generator (the same rows under the same seed).  Returns ``(labels, centroids)``."""
-  xp = _points(x, "x")
+  xp = _cloud(x, "x")
   if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= xp.shape[0]:
     raise ValueError(f"k must be an int in 1..N = {xp.shape[0]}, got {k!r}")
   centroid_idx = torch.randperm(xp.shape[0])[:k]

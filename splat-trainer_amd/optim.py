@@ -14,13 +14,14 @@ and appending.  There is no CPU fallback: ``step`` needs the HIP library and CUD
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib
+from ._args import f32
+from ._lib import ptr as _ptr
 from .tensor_rows import TensorRows
 
 SCALAR, VECTOR, LOCAL_VECTOR = "scalar", "vector", "local_vector"
@@ -53,23 +54,18 @@ class VisibilityAwareLaProp(VisibilityOptimizer, SparseLaProp):
   visibility_aware = True
 
 
-def _ptr(t: Optional[torch.Tensor]):
-  return None if t is None else t.data_ptr()     # plain int: the prototypes declare c_void_p
-
-
 def point_basis_rows(log_scaling: torch.Tensor, rotation: torch.Tensor, indexes: Optional[torch.Tensor] = None,
                      eps: float = 1e-4) -> torch.Tensor:
   """``point_basis(log_scaling[indexes], rotation[indexes])`` (splat_trainer/gaussians/split.py:16-20) as one launch:
   (M,3,3) = R(normalised xyzw quaternion) with columns scaled by ``clamp_min(exp(log_scaling), eps)`` -- the ``basis``
   argument of ``ParameterClass.step`` (mlp_scene.py:219-230).  ``indexes`` None: all rows."""
-  ls = log_scaling.detach().to(torch.float32).contiguous()
-  rot = rotation.detach().to(torch.float32).contiguous()
+  ls, rot = f32(log_scaling), f32(rotation)
   if not (ls.is_cuda and rot.is_cuda):
     raise _lib.GsplatHipError("point_basis_rows runs only on a HIP device; there is no CPU fallback")
   M = int(indexes.shape[0]) if indexes is not None else int(ls.shape[0])
   out = torch.empty(M, 3, 3, dtype=torch.float32, device=ls.device)
-  _lib.check(_lib.load().gsr_point_basis(_ptr(ls), _ptr(rot), _ptr(indexes.contiguous()) if indexes is not None else None,
-                                         M, float(eps), _ptr(out), _lib.current_stream_ptr()), "gsr_point_basis")
+  _lib.call("gsr_point_basis", _ptr(ls), _ptr(rot), _ptr(indexes.contiguous()) if indexes is not None else None, M,
+            float(eps), _ptr(out), _lib.current_stream_ptr())
   return out
 
 
@@ -158,7 +154,6 @@ class ParameterClass:
   def step(self, indexes: torch.Tensor, visibility: Optional[torch.Tensor] = None, basis: Optional[torch.Tensor] = None):
     """One optimizer step on the rows ``indexes`` (unique, int64).  ``visibility`` (M,) weights the rows for
     visibility-aware optimizers; ``basis`` (M,3,3) is needed by ``local_vector`` groups (mlp_scene.py:219-230)."""
-    lib = _lib.load()
     opt, o = self.optimizer, self.options
     if indexes.dtype != torch.int64 or not indexes.is_cuda:
       raise ValueError("indexes must be a CUDA int64 tensor")
@@ -168,15 +163,14 @@ class ParameterClass:
     if M == 0:
       return
     indexes = indexes.contiguous()
-    vis = visibility.to(torch.float32).contiguous() if (opt.visibility_aware and visibility is not None) else None
+    vis = f32(visibility) if (opt.visibility_aware and visibility is not None) else None
     if vis is not None and vis.shape[0] != M:
       raise ValueError("visibility and indexes differ in length")
     stream = _lib.current_stream_ptr()
     row_scale = torch.empty(M, 4, dtype=torch.float32, device=indexes.device)
     st = self._state
-    _lib.check(lib.gsr_opt_point_weights(_ptr(indexes), _ptr(vis), M, _ptr(st["step"]), _ptr(st["vis_avg"]),
-                                         o["betas"][0], o["betas"][1], o["vis_beta"], o["vis_smooth"],
-                                         int(o["bias_correction"]), _ptr(row_scale), stream), "gsr_opt_point_weights")
+    _lib.call("gsr_opt_point_weights", _ptr(indexes), _ptr(vis), M, _ptr(st["step"]), _ptr(st["vis_avg"]), o["betas"][0],
+              o["betas"][1], o["vis_beta"], o["vis_smooth"], int(o["bias_correction"]), _ptr(row_scale), stream)
     algo = 1 if opt.algo == "laprop" else 0
     clip = float(o["grad_clip"]) if o["grad_clip"] else 0.0
     for k, grp in self.parameter_groups.items():
@@ -185,17 +179,17 @@ class ParameterClass:
         continue
       if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
         raise ValueError(f"{k}: parameters must be contiguous float32 CUDA tensors")
-      g = p.grad.to(torch.float32).contiguous()
+      g = f32(p.grad)
       b = None
       if grp["type"] == LOCAL_VECTOR:
         if basis is None or tuple(basis.shape) != (M, 3, 3):
           raise ValueError(f"{k}: local_vector groups need basis of shape ({M}, 3, 3)")
-        b = basis.to(torch.float32).contiguous()
+        b = f32(basis)
       gs = st["groups"][k]
       D = int(math.prod(p.shape[1:]))
-      _lib.check(lib.gsr_opt_step(_ptr(p), _ptr(g), _ptr(gs["exp_avg"]), _ptr(gs["exp_avg_sq"]), _ptr(indexes),
-                                  _ptr(row_scale), _ptr(b), M, D, _TYPE_ID[grp["type"]], algo, grp["lr"],
-                                  o["betas"][0], o["betas"][1], o["eps"], clip, stream), f"gsr_opt_step({k})")
+      _lib.call("gsr_opt_step", _ptr(p), _ptr(g), _ptr(gs["exp_avg"]), _ptr(gs["exp_avg_sq"]), _ptr(indexes),
+                _ptr(row_scale), _ptr(b), M, D, _TYPE_ID[grp["type"]], algo, grp["lr"], o["betas"][0], o["betas"][1],
+                o["eps"], clip, stream, note=f"({k})")
 
   # ----------------------------------------------------------------------------------- densify / prune support
   def _like(self, tensors, state) -> "ParameterClass":

@@ -10,18 +10,17 @@ the device.  There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Mapping, Optional
+from typing import Mapping
 
 import torch
 
 from . import _lib
+from ._args import on_one_device, require
+from ._lib import ptr as _ptr
 from .data_types import RenderedPoints
 
 TERMS = ("scale", "opacity", "aspect", "specular")        # order of GsrReg.weight and of the terms buffer
-
-
-def _ptr(t: Optional[torch.Tensor]):
-  return None if t is None else t.data_ptr()
+WHAT = "the regulariser"
 
 
 def _args(idx, log_scaling, depths, opacity, specular, visibility, weights, visibility_weighted) -> "_lib.GsrReg":
@@ -36,19 +35,15 @@ def _args(idx, log_scaling, depths, opacity, specular, visibility, weights, visi
 class _RegFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, opacity, depths, specular, log_scaling, idx, visibility, weights, visibility_weighted):
-    lib = _lib.load()
     dev = opacity.device
-    M = int(idx.shape[0])
     tensors = [t.detach().contiguous() for t in (opacity, depths, log_scaling)]
     spec = None if specular is None else specular.detach().contiguous()
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev) as stream:
       loss = torch.empty((), dtype=torch.float32, device=dev)
       terms = torch.empty(5, dtype=torch.float32, device=dev)
-      ws_bytes = lib.gsr_reg_workspace_bytes(M)
-      ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+      ws = _lib.workspace(_lib.load().gsr_reg_workspace_bytes(int(idx.shape[0])), dev)
       a = _args(idx, tensors[2], tensors[1], tensors[0], spec, visibility, weights, visibility_weighted)
-      _lib.check(lib.gsr_reg_forward(C.byref(a), _ptr(loss), _ptr(terms), _ptr(ws), ws_bytes, _lib.current_stream_ptr()),
-                 "gsr_reg_forward")
+      _lib.call("gsr_reg_forward", C.byref(a), _ptr(loss), _ptr(terms), _ptr(ws), ws.numel(), stream)
     ctx.save_for_backward(*tensors, idx, visibility, terms, *(() if spec is None else (spec,)))
     ctx.has_specular = spec is not None
     ctx.weights, ctx.visibility_weighted = weights, visibility_weighted
@@ -59,37 +54,16 @@ class _RegFn(torch.autograd.Function):
   def backward(ctx, d_loss, _d_terms):
     opacity, depths, log_scaling, idx, visibility, terms, *rest = ctx.saved_tensors
     spec = rest[0] if ctx.has_specular else None
-    lib = _lib.load()
-    dev = opacity.device
     need_op, need_dep, need_spec, need_ls = ctx.needs_input_grad[:4]
-    with torch.cuda.device(dev):
+    with _lib.on_device(opacity.device) as stream:
       d_op = torch.empty_like(opacity) if need_op else None
       d_dep = torch.empty_like(depths) if need_dep else None
       d_spec = torch.empty_like(spec) if (need_spec and spec is not None) else None
       d_ls = torch.zeros_like(log_scaling) if need_ls else None       # the kernel adds into the rows of idx
       a = _args(idx, log_scaling, depths, opacity, spec, visibility, ctx.weights, ctx.visibility_weighted)
-      _lib.check(lib.gsr_reg_backward(C.byref(a), _ptr(terms), _ptr(d_loss.float().contiguous()), _ptr(d_op), _ptr(d_dep),
-                                      _ptr(d_spec), _ptr(d_ls), _lib.current_stream_ptr()), "gsr_reg_backward")
+      _lib.call("gsr_reg_backward", C.byref(a), _ptr(terms), _ptr(d_loss.float().contiguous()), _ptr(d_op), _ptr(d_dep),
+                _ptr(d_spec), _ptr(d_ls), stream)
     return d_op, d_dep, d_spec, d_ls, None, None, None, None
-
-
-def _check(name: str, t, shape, dtype=torch.float32):
-  if not isinstance(t, torch.Tensor):
-    raise ValueError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
-  if t.dtype is not dtype:
-    raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-  if tuple(t.shape) not in shape:
-    raise ValueError(f"{name} must be {' or '.join(str(s) for s in shape)}, got {tuple(t.shape)}")
-
-
-def _require_device(**tensors):
-  for name, t in tensors.items():
-    if t is not None and not t.is_cuda:
-      raise _lib.GsplatHipError(f"{name.replace('__', '.')} is on {t.device}: the regulariser runs on the HIP device only "
-                                "(there is no CPU fallback)")
-  devs = {t.device for t in tensors.values() if t is not None}
-  if len(devs) > 1:
-    raise ValueError(f"inputs on different devices: {sorted(map(str, devs))}")
 
 
 def reg_loss(points: RenderedPoints, log_scaling: torch.Tensor, weights: Mapping[str, float],
@@ -122,19 +96,21 @@ def reg_loss(points: RenderedPoints, log_scaling: torch.Tensor, weights: Mapping
   if not isinstance(idx, torch.Tensor) or idx.dim() != 1:
     raise ValueError("points.idx must be an (M,) tensor")
   M = int(idx.shape[0])
-  _check("points.idx", idx, [(M,)], torch.int64)
-  _check("points.opacity", points.opacity, [(M,)])
-  _check("points.depths", points.depths, [(M, 1), (M,)])
-  _check("points.visibility", visibility, [(M,)])
+  f32 = torch.float32
+  require("points.idx", idx, dtype=torch.int64)
+  require("points.opacity", points.opacity, shape=(M,), dtype=f32)
+  require("points.depths", points.depths, shape=[(M, 1), (M,)], dtype=f32)
+  require("points.visibility", visibility, shape=(M,), dtype=f32)
   if specular is not None:
-    _check("points.attributes.specular", specular, [(M, 3)])
+    require("points.attributes.specular", specular, shape=(M, 3), dtype=f32)
   if not isinstance(log_scaling, torch.Tensor) or log_scaling.dim() != 2:
     raise ValueError("log_scaling must be an (N, 3) tensor")
-  _check("log_scaling", log_scaling, [(int(log_scaling.shape[0]), 3)])
+  require("log_scaling", log_scaling, shape=(int(log_scaling.shape[0]), 3), dtype=f32)
   if M > 0 and log_scaling.shape[0] == 0:
     raise ValueError("log_scaling has no rows but points has some")
-  _require_device(points__idx=idx, points__opacity=points.opacity, points__depths=points.depths,
-                  points__visibility=visibility, points__attributes__specular=specular, log_scaling=log_scaling)
+  on_one_device({"points.idx": idx, "points.opacity": points.opacity, "points.depths": points.depths,
+                 "points.visibility": visibility, "points.attributes.specular": specular, "log_scaling": log_scaling},
+                what=WHAT)
   loss, terms = _RegFn.apply(points.opacity, points.depths, specular, log_scaling, idx.contiguous(),
                              visibility.detach().contiguous(), w, bool(visibility_weighted))
   return (loss, terms) if return_terms else loss
@@ -146,11 +122,10 @@ def scene_post_step(rotation: torch.Tensor, log_scaling: torch.Tensor, eps: floa
   """mlp_scene.py:236-237 in one launch, in place: ``rotation = F.normalize(rotation, dim=1)`` (eps 1e-12) and
   ``log_scaling.clamp_(-8, 8)``."""
   N = int(rotation.shape[0])
-  _check("rotation", rotation, [(N, 4)])
-  _check("log_scaling", log_scaling, [(N, 3)])
+  require("rotation", rotation, shape=(N, 4), dtype=torch.float32)
+  require("log_scaling", log_scaling, shape=(N, 3), dtype=torch.float32)
   if not (rotation.is_contiguous() and log_scaling.is_contiguous()):
     raise ValueError("rotation and log_scaling must be contiguous")
-  _require_device(rotation=rotation, log_scaling=log_scaling)
-  with torch.cuda.device(rotation.device):
-    _lib.check(_lib.load().gsr_scene_post_step(_ptr(rotation), _ptr(log_scaling), N, float(eps), float(lo), float(hi),
-                                               _lib.current_stream_ptr()), "gsr_scene_post_step")
+  on_one_device(dict(rotation=rotation, log_scaling=log_scaling), what=WHAT)
+  with _lib.on_device(rotation.device) as stream:
+    _lib.call("gsr_scene_post_step", _ptr(rotation), _ptr(log_scaling), N, float(eps), float(lo), float(hi), stream)

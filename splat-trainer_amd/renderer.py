@@ -25,6 +25,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._args import f32
 from ._lib import current_stream_ptr as _stream, ptr as _ptr
 from .data_types import CameraParams, Gaussians3D, RasterConfig, RenderedPoints, Rendering
 from . import sh as _sh
@@ -100,20 +101,6 @@ def _require_device(*tensors: torch.Tensor):
       raise TypeError(f"unsupported dtype {t.dtype}; the path computes in float32 (half inputs are widened)")
 
 
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-  if t.dtype is torch.float32 and t.is_contiguous():
-    return t.detach()
-  return t.detach().to(torch.float32).contiguous()
-
-
-def _f32c_camera(t: torch.Tensor) -> torch.Tensor:
-  """_f32c for T_camera_world / projection, keeping their autograd graph: the camera gradient the nodes below return
-  flows back through the cast, in the caller's dtype."""
-  if t.dtype is torch.float32 and t.is_contiguous():
-    return t
-  return t.to(torch.float32).contiguous()
-
-
 def _wants_camera_grad(camera_params: CameraParams) -> bool:
   return torch.is_grad_enabled() and (camera_params.T_camera_world.requires_grad or
                                       camera_params.projection.requires_grad)
@@ -137,22 +124,19 @@ def _camera_scratch(count: int, dev):
 # ------------------------------------------------------------------------------------------- K1 + K2
 def frustum_cull(position: torch.Tensor, camera_params: CameraParams, config: RasterConfig) -> torch.Tensor:
   """K1: ascending int64 indices of the points whose centre lies in the margin-expanded frustum."""
-  lib = _lib.load()
   _require_device(position)
-  pos = _f32c(position)
+  pos = f32(position)
   N = pos.shape[0]
   dev = pos.device
   W, H = camera_params.image_size
-  T = _f32c(camera_params.T_camera_world)
-  proj = _f32c(camera_params.projection)
+  T = f32(camera_params.T_camera_world)
+  proj = f32(camera_params.projection)
   indexes = torch.empty(N, dtype=torch.int64, device=dev)
   count = torch.empty(1, dtype=torch.int32, device=dev)
-  ws_bytes = lib.gsr_cull_workspace_bytes(N)
-  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-  _lib.check(lib.gsr_frustum_cull(_ptr(pos), N, _ptr(T), _ptr(proj), int(W), int(H),
-                                  float(camera_params.near_plane), float(camera_params.far_plane),
-                                  float(config.margin_tiles * config.tile_size), _ptr(indexes), _ptr(count),
-                                  _ptr(ws), ws_bytes, _stream()), "gsr_frustum_cull")
+  ws = _lib.workspace(_lib.load().gsr_cull_workspace_bytes(N), dev)
+  _lib.call("gsr_frustum_cull", _ptr(pos), N, _ptr(T), _ptr(proj), int(W), int(H), float(camera_params.near_plane),
+            float(camera_params.far_plane), float(config.margin_tiles * config.tile_size), _ptr(indexes), _ptr(count),
+            _ptr(ws), ws.numel(), _stream())
   M = int(count.item())          # host sync #1: the index tensor's size is data dependent
   return indexes[:M]
 
@@ -323,24 +307,22 @@ class _ProjectFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, position, log_scaling, rotation, alpha_logit, T, proj, cull_args, params, grad_out, prefetch):
-    lib = _lib.load()
-    pos, ls, rot, al = _f32c(position), _f32c(log_scaling), _f32c(rotation), _f32c(alpha_logit)
+    pos, ls, rot, al = f32(position), f32(log_scaling), f32(rotation), f32(alpha_logit)
     N, dev = pos.shape[0], pos.device
     W, H, near, far, margin = cull_args
     stream = _stream()
     indexes_full = torch.empty(N, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    ws_bytes = lib.gsr_cull_workspace_bytes(N)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(_lib.load().gsr_cull_workspace_bytes(N), dev)
     g2d_full = torch.empty(N, 6, dtype=torch.float32, device=dev)
     depth_full = torch.empty(N, 1, dtype=torch.float32, device=dev)
     keys_full = _u32(N, dev) if prefetch is not None else None     # the depth sort's keys, when the caller rasterizes next
     key_range = _depth_key_range(near, far)
-    _lib.check(lib.gsr_frustum_cull(_ptr(pos), N, _ptr(T), _ptr(proj), W, H, near, far, margin, _ptr(indexes_full),
-                                    _ptr(count), _ptr(ws), ws_bytes, stream), "gsr_frustum_cull")
-    _lib.check(lib.gsr_project_forward(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes_full), N, _ptr(T),
-                                       _ptr(proj), C.byref(params), _ptr(g2d_full), _ptr(depth_full), _ptr(count),
-                                       _ptr(keys_full), key_range[0], key_range[1], stream), "gsr_project_forward")
+    _lib.call("gsr_frustum_cull", _ptr(pos), N, _ptr(T), _ptr(proj), W, H, near, far, margin, _ptr(indexes_full),
+              _ptr(count), _ptr(ws), ws.numel(), stream)
+    _lib.call("gsr_project_forward", _ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes_full), N, _ptr(T), _ptr(proj),
+              C.byref(params), _ptr(g2d_full), _ptr(depth_full), _ptr(count), _ptr(keys_full), key_range[0], key_range[1],
+              stream)
     wait = _start_readback(count)  # host sync #1 (K2 is already running)
     sh_job = prefetch.pop("sh", None) if prefetch is not None else None
     if sh_job is not None and N > 0:
@@ -365,7 +347,6 @@ class _ProjectFn(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, d_g2d, d_depth, _d_indexes):
-    lib = _lib.load()
     pos, ls, rot, al, indexes, T, proj = ctx.saved_tensors
     M, N = indexes.shape[0], pos.shape[0]
     go = ctx.grad_out
@@ -377,20 +358,15 @@ class _ProjectFn(torch.autograd.Function):
     want_cam = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
     d_camera = None
     if live:
-      dg = _f32c(d_g2d) if d_g2d is not None else torch.zeros(M, 6, dtype=torch.float32, device=pos.device)
-      dd = _f32c(d_depth) if d_depth is not None else None
+      dg = f32(d_g2d) if d_g2d is not None else torch.zeros(M, 6, dtype=torch.float32, device=pos.device)
+      dd = f32(d_depth) if d_depth is not None else None
+      args = (_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T), _ptr(proj), C.byref(ctx.params),
+              _ptr(dg), _ptr(dd), _ptr(d_pos), _ptr(d_ls), _ptr(d_rot), _ptr(d_al), int(dest.accumulate))
       if want_cam:
         partials, d_camera = _camera_scratch(M, pos.device)
-        _lib.check(lib.gsr_project_backward_camera(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
-                                                   _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
-                                                   _ptr(d_ls), _ptr(d_rot), _ptr(d_al), int(dest.accumulate),
-                                                   _ptr(partials), _ptr(d_camera), _stream()),
-                   "gsr_project_backward_camera")
+        _lib.call("gsr_project_backward_camera", *args, _ptr(partials), _ptr(d_camera), _stream())
       else:
-        _lib.check(lib.gsr_project_backward(_ptr(pos), _ptr(ls), _ptr(rot), _ptr(al), _ptr(indexes), M, _ptr(T),
-                                            _ptr(proj), C.byref(ctx.params), _ptr(dg), _ptr(dd), _ptr(d_pos),
-                                            _ptr(d_ls), _ptr(d_rot), _ptr(d_al), int(dest.accumulate),
-                                            _stream()), "gsr_project_backward")
+        _lib.call("gsr_project_backward", *args, _stream())
     d_T, d_proj = _camera_grads(d_camera, pos.device) if want_cam else (None, None)
     if go is not None:
       return None, None, None, None, d_T, d_proj, None, None, None, None
@@ -407,8 +383,9 @@ def project_to_image(gaussians: Gaussians3D, camera_params: CameraParams, config
   ``prefetch={}``: the depth sort render_projected needs is enqueued right away (it only depends on ``depth``) and handed
   back as ``prefetch["depth_order"]`` for ``render_projected(..., _depth_order=prefetch["depth_order"])``."""
   _require_device(gaussians.position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit)
-  T = _f32c_camera(camera_params.T_camera_world)
-  proj = _f32c_camera(camera_params.projection)
+  # (the pose and the projection keep their graph: the camera gradient the node returns flows back through the cast)
+  T = f32(camera_params.T_camera_world, detach=False)
+  proj = f32(camera_params.projection, detach=False)
   params = _lib.raster_params(config)
   W, H = camera_params.image_size
   cull_args = (int(W), int(H), float(camera_params.near_plane), float(camera_params.far_plane),
@@ -435,9 +412,8 @@ class _RasterState:
     same bits); whoever reads it EARLIER -- a regularizer on ``points.visible`` before ``loss.backward()``,
     mlp_scene.py:268-288 -- triggers the stand-alone reduction here, once."""
     if not self.vis_ready:
-      _lib.check(_lib.load().gsr_reduce_visibility(_ptr(self.vis_partial), _ptr(self.offsets), _ptr(self.count),
-                                                   _ptr(self.order), self.M, _ptr(self.visibility), self.vis_capacity,
-                                                   None, _stream()), "gsr_reduce_visibility")
+      _lib.call("gsr_reduce_visibility", _ptr(self.vis_partial), _ptr(self.offsets), _ptr(self.count), _ptr(self.order),
+                self.M, _ptr(self.visibility), self.vis_capacity, None, _stream())
       self.vis_ready = True
     return self.visibility
 
@@ -456,7 +432,7 @@ def _depth_key_range(near: float, far: float):
   hit = _KEY_RANGES.get(key)
   if hit is None:
     bias, top = C.c_uint32(0), C.c_uint32(0)
-    _lib.check(_lib.load().gsr_depth_key_range(key[0], key[1], C.byref(bias), C.byref(top)), "gsr_depth_key_range")
+    _lib.call("gsr_depth_key_range", key[0], key[1], C.byref(bias), C.byref(top))
     hit = _KEY_RANGES[key] = (bias.value, top.value, max(1, int(top.value).bit_length()))
     if len(_KEY_RANGES) > 4096:
       _KEY_RANGES.clear()
@@ -467,18 +443,16 @@ def _launch_depth_order(depth: Optional[torch.Tensor], M: int, key_range, keys: 
   """depth keys + stable radix sort of the M splats over the keys' significant bits (ties keep ascending index); returns
   order (M,) int32.  ``key_range`` = _depth_key_range(near, far); ``keys``: the keys when K2 has already written them
   (consumed as sort scratch)."""
-  lib = _lib.load()
   dev = keys.device if keys is not None else depth.device
   stream = _stream()
   bias, max_key, key_bits = key_range
   keys_a = keys if keys is not None else _u32(M, dev)
   keys_b, vals_a, vals_b = _u32(M, dev), _u32(M, dev), _u32(M, dev)
-  sort_bytes = lib.gsr_sort_workspace_bytes(M)
-  sort_ws = torch.empty(sort_bytes, dtype=torch.uint8, device=dev)
+  sort_ws = _lib.workspace(_lib.load().gsr_sort_workspace_bytes(M), dev)
   if keys is None:
-    _lib.check(lib.gsr_depth_keys(_ptr(depth), M, bias, max_key, _ptr(keys_a), stream), "gsr_depth_keys")
-  where = _lib.check(lib.gsr_sort_pairs_u32(_ptr(keys_a), _ptr(vals_a), _ptr(keys_b), _ptr(vals_b), M, 1, 0, key_bits,
-                                            _ptr(sort_ws), sort_bytes, None, stream), "gsr_sort_pairs_u32(depth)")
+    _lib.call("gsr_depth_keys", _ptr(depth), M, bias, max_key, _ptr(keys_a), stream)
+  where = _lib.call("gsr_sort_pairs_u32", _ptr(keys_a), _ptr(vals_a), _ptr(keys_b), _ptr(vals_b), M, 1, 0, key_bits,
+                    _ptr(sort_ws), sort_ws.numel(), None, stream, note="(depth)")
   return vals_b if where == 1 else vals_a
 
 
@@ -510,54 +484,44 @@ def _wide_width(C_: int) -> int:
 def _composite_backward_wide(st: _RasterState, d_image: torch.Tensor, d_feat: torch.Tensor, dev) -> torch.Tensor:
   """K7 wide + its per-splat reduction (C >= 4): the packed (M,16) gradient rows with df0..df2 = 0; the feature gradient
   is written straight into ``d_feat`` (M, C).  The forward pass's segments (if any) give every segment its own wave."""
-  lib = _lib.load()
   if st.vis_partial is None:
     raise _lib.GsplatHipError("backward called on a rendering made without gradient state")
   stream = _stream()
-  dimg = _f32c(d_image)
+  dimg = f32(d_image)
   partial = torch.empty(st.O, 8 + _wide_width(st.C), dtype=torch.float32, device=dev)
   timer = KERNEL_TIMER
   if timer is not None:
     timer.begin("composite_backward")
-  _lib.check(lib.gsr_composite_backward_wide_seg(_ptr(st.rows), _ptr(st.feat_rows), _ptr(st.sorted_splat),
-                                                 _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.tile_range), st.W,
-                                                 st.H, st.C, C.byref(st.params), _ptr(st.final_T), _ptr(st.last),
-                                                 _ptr(dimg), _ptr(st.image), _ptr(partial), _seg_ref(st), stream),
-             "gsr_composite_backward_wide_seg")
+  _lib.call("gsr_composite_backward_wide_seg", _ptr(st.rows), _ptr(st.feat_rows), _ptr(st.sorted_splat),
+            _ptr(st.sorted_inst), _ptr(st.pair_vis), _ptr(st.tile_range), st.W, st.H, st.C, C.byref(st.params),
+            _ptr(st.final_T), _ptr(st.last), _ptr(dimg), _ptr(st.image), _ptr(partial), _seg_ref(st), stream)
   if timer is not None:
     timer.end("composite_backward")
   grows = torch.empty(st.M, ROW_FLOATS, dtype=torch.float32, device=dev)
-  _lib.check(lib.gsr_reduce_gradients_wide(_ptr(partial), _ptr(st.vis_partial), _ptr(st.offsets), _ptr(st.count),
-                                           _ptr(st.order), st.M, st.C, _ptr(grows), _ptr(d_feat), stream),
-             "gsr_reduce_gradients_wide")
+  _lib.call("gsr_reduce_gradients_wide", _ptr(partial), _ptr(st.vis_partial), _ptr(st.offsets), _ptr(st.count),
+            _ptr(st.order), st.M, st.C, _ptr(grows), _ptr(d_feat), stream)
   return grows
 
 
-def _composite_backward_rows(st: _RasterState, d_image: Optional[torch.Tensor], dev) -> torch.Tensor:
-  """K7 + the per-splat reduction: the packed (M,16) gradient rows of the frame
-  (du dv dA dB | dC dop prune split | df0 df1 df2 visibility | 0 0 0 0), zeros when nothing was composited."""
-  lib = _lib.load()
-  live = st.M > 0 and st.O > 0 and d_image is not None
-  if not live:
-    return torch.zeros(st.M, ROW_FLOATS, dtype=torch.float32, device=dev)
+def _composite_backward_rows(st: _RasterState, d_image: torch.Tensor, dev) -> torch.Tensor:
+  """K7 + the per-splat reduction: the packed (M,16) gradient rows of a frame that composited something
+  (du dv dA dB | dC dop prune split | df0 df1 df2 visibility | 0 0 0 0)."""
   if st.vis_partial is None:
     raise _lib.GsplatHipError("backward called on a rendering made without gradient state")
   stream = _stream()
-  dimg = _f32c(d_image)
+  dimg = f32(d_image)
   partial = torch.empty(st.O, PARTIAL_FLOATS, dtype=torch.float32, device=dev)
   timer = KERNEL_TIMER
   if timer is not None:
     timer.begin("composite_backward")
-  _lib.check(lib.gsr_composite_backward(_ptr(st.rows), _ptr(st.sorted_splat), _ptr(st.sorted_inst),
-                                        _ptr(st.pair_vis), _ptr(st.tile_range), st.W, st.H, st.C,
-                                        C.byref(st.params), _ptr(st.final_T), _ptr(st.last), _ptr(dimg),
-                                        _ptr(st.image), _ptr(partial), _seg_ref(st), stream),
-             "gsr_composite_backward")
+  _lib.call("gsr_composite_backward", _ptr(st.rows), _ptr(st.sorted_splat), _ptr(st.sorted_inst), _ptr(st.pair_vis),
+            _ptr(st.tile_range), st.W, st.H, st.C, C.byref(st.params), _ptr(st.final_T), _ptr(st.last), _ptr(dimg),
+            _ptr(st.image), _ptr(partial), _seg_ref(st), stream)
   if timer is not None:
     timer.end("composite_backward")
   grows = torch.empty(st.M, ROW_FLOATS, dtype=torch.float32, device=dev)      # every row is written whole
-  _lib.check(lib.gsr_reduce_gradients(_ptr(partial), _ptr(st.vis_partial), _ptr(st.offsets), _ptr(st.count),
-                                      _ptr(st.order), st.M, _ptr(grows), stream), "gsr_reduce_gradients")
+  _lib.call("gsr_reduce_gradients", _ptr(partial), _ptr(st.vis_partial), _ptr(st.offsets), _ptr(st.count),
+            _ptr(st.order), st.M, _ptr(grows), stream)
   return grows
 
 
@@ -575,7 +539,7 @@ class _RasterFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, g2d, feats, depth, st: _RasterState, order):
-    g, f, d = _f32c(g2d), _f32c(feats), _f32c(depth).reshape(-1)
+    g, f, d = f32(g2d), f32(feats), f32(depth).reshape(-1)
     if st.M == 0:
       image = _blank_frame(st, g.device)
     else:
@@ -595,7 +559,6 @@ class _RasterFn(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, d_image):
-    lib = _lib.load()
     st: _RasterState = ctx.st
     dev = d_image.device
     live = st.M > 0 and st.O > 0
@@ -606,9 +569,8 @@ class _RasterFn(torch.autograd.Function):
       wide = st.C >= _lib.WIDE_MIN_FEATURES
       grows = _composite_backward_wide(st, d_image, d_feat, dev) if wide else _composite_backward_rows(st, d_image, dev)
       # prune_cost / split_score (/ visibility) are written straight into the tensors the Rendering already holds
-      _lib.check(lib.gsr_unpack_grad_rows(_ptr(st.rows), _ptr(grows), st.M, st.C, _ptr(d_g2d),
-                                          None if wide else _ptr(d_feat), _ptr(st.prune_cost), _ptr(st.split_score),
-                                          _ptr(_vis_out(st, live)), _stream()), "gsr_unpack_grad_rows")
+      _lib.call("gsr_unpack_grad_rows", _ptr(st.rows), _ptr(grows), st.M, st.C, _ptr(d_g2d), None if wide else _ptr(d_feat),
+                _ptr(st.prune_cost), _ptr(st.split_score), _ptr(_vis_out(st, live)), _stream())
     return d_g2d.to(ctx.in_dtypes[0]), d_feat.to(ctx.in_dtypes[1]), None, None, None
 
 
@@ -640,21 +602,19 @@ def _run_frame(frame: "_lib.GsrFrameC", st: _RasterState, dev, rows_bound: int, 
   """Enqueues one frame through the native driver (csrc/frame.hip) and fills ``st`` with views of its output arena.
   ``rows_bound``: the scene's N (one-call form: the visible count M comes back from the device) or the exact number of
   splats (projected mode).  Returns (out arena, plan, M)."""
-  lib = _lib.load()
   guesses, raw_guess, capacity = _pair_capacity(dev.index, rows_bound)
   plan, res = _lib.GsrFramePlanC(), _lib.GsrFrameResultC()
   timer = KERNEL_TIMER
   N, W, H, C_ = rows_bound, st.W, st.H, st.C
   while True:
     frame.pair_capacity = capacity
-    _lib.check(lib.gsr_frame_plan(C.byref(frame), C.byref(plan)), "gsr_frame_plan")
+    _lib.call("gsr_frame_plan", C.byref(frame), C.byref(plan))
     out = torch.empty(plan.out_bytes, dtype=torch.uint8, device=dev)
     work = torch.empty(plan.work_bytes, dtype=torch.uint8, device=dev)
     ev = timer.pair("composite_forward") if timer is not None else (None, None)
     host, ready, host_words = _readback_slot(dev)
-    _lib.check(lib.gsr_frame_forward(C.byref(frame), C.byref(plan), C.c_void_p(out.data_ptr()),
-                                     C.c_void_p(work.data_ptr()), C.byref(res), C.c_void_p(host.data_ptr()),
-                                     C.c_void_p(ready.cuda_event), ev[0], ev[1], _stream()), "gsr_frame_forward")
+    _lib.call("gsr_frame_forward", C.byref(frame), C.byref(plan), C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()),
+              C.byref(res), C.c_void_p(host.data_ptr()), C.c_void_p(ready.cuda_event), ev[0], ev[1], _stream())
     del work                                   # scratch: the allocator may hand it on (stream order keeps it safe)
     # the frame's only host wait: on the copy the driver issued right behind the scan, with the emit, the tile sort and
     # the composite already enqueued behind it -- the device works on while the host shapes the tensors and moves on
@@ -712,8 +672,8 @@ class _FrameFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, position, log_scaling, rotation, alpha_logit, feature, T, proj, cam_pos, cull_args, st: _RasterState,
               grad_out, sink, want_jac):
-    pos, ls, rot, al = _f32c(position), _f32c(log_scaling), _f32c(rotation), _f32c(alpha_logit)
-    sh, cam = _f32c(feature), _f32c(cam_pos)
+    pos, ls, rot, al = f32(position), f32(log_scaling), f32(rotation), f32(alpha_logit)
+    sh, cam = f32(feature), f32(cam_pos)
     N, K, dev = pos.shape[0], sh.shape[2], pos.device
     W, H, near, far, margin = cull_args
     if N == 0:
@@ -741,7 +701,6 @@ class _FrameFn(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, d_image, d_g2d, d_depth, _d_indexes):
-    lib = _lib.load()
     pos, ls, rot, al, sh, indexes, T, proj, cam = ctx.saved_tensors
     st: _RasterState = ctx.st
     M, N, K, dev = indexes.shape[0], pos.shape[0], sh.shape[2], pos.device
@@ -777,9 +736,9 @@ class _FrameFn(torch.autograd.Function):
       partial = torch.empty(st.O, PARTIAL_FLOATS, dtype=torch.float32, device=dev) if live else None
       grows = torch.empty(M, ROW_FLOATS, dtype=torch.float32, device=dev) if M > 0 else None
       dcol = torch.empty(M, 3, dtype=torch.float32, device=dev) if want_sh else None
-      dimg = _f32c(d_image) if live else None
-      dg = _f32c(d_g2d) if d_g2d is not None else None
-      dd = _f32c(d_depth).reshape(-1) if d_depth is not None else None
+      dimg = f32(d_image) if live else None
+      dg = f32(d_g2d) if d_g2d is not None else None
+      dd = f32(d_depth).reshape(-1) if d_depth is not None else None
       timer = KERNEL_TIMER
       ev = timer.pair("composite_backward") if (timer is not None and live) else (None, None)
       seg = C.addressof(st.segments) if st.segments is not None else None
@@ -801,11 +760,11 @@ class _FrameFn(torch.autograd.Function):
       if early is not None and M > 0:
         # data-parallel: K7 + reduction first; the caller packs the colour-gradient factors straight from the packed rows
         # and starts their all-gather, which then runs next to the sweep enqueued below
-        _lib.check(lib.gsr_frame_backward_stages(C.byref(args), 1, ev[0], ev[1], _stream()), "gsr_frame_backward_stages(1)")
+        _lib.call("gsr_frame_backward_stages", C.byref(args), 1, ev[0], ev[1], _stream(), note="(1)")
         early(indexes, grows, cam)
-        _lib.check(lib.gsr_frame_backward_stages(C.byref(args), 2, None, None, _stream()), "gsr_frame_backward_stages(2)")
+        _lib.call("gsr_frame_backward_stages", C.byref(args), 2, None, None, _stream(), note="(2)")
       else:
-        _lib.check(lib.gsr_frame_backward(C.byref(args), ev[0], ev[1], _stream()), "gsr_frame_backward")
+        _lib.call("gsr_frame_backward", C.byref(args), ev[0], ev[1], _stream())
     else:
       dcol = torch.zeros(0, 3, dtype=torch.float32, device=dev) if want_sh else None
     if collector is not None:              # data-parallel factor exchange: keep only the colour gradient
@@ -928,7 +887,7 @@ def _render_frame(gaussians: Gaussians3D, camera_params: CameraParams, config: R
   else:
     cam_pos = camera_params.camera_position
   image, g2d, depth, indexes = _FrameFn.apply(position, gaussians.log_scaling, gaussians.rotation, gaussians.alpha_logit,
-                                              feature, _f32c_camera(camera_params.T_camera_world),
-                                              _f32c_camera(camera_params.projection), cam_pos, cull_args, st,
+                                              feature, f32(camera_params.T_camera_world, detach=False),
+                                              f32(camera_params.projection, detach=False), cam_pos, cull_args, st,
                                               grad_out, sink, want_pos_grad or cam_grad)
   return _rendering_of(st, image, indexes, g2d, depth, camera_params)

@@ -10,6 +10,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from ._args import f32
 from ._lib import current_stream_ptr as _stream, ptr as _ptr
 
 
@@ -38,8 +39,7 @@ class ShFactorCollector:
 
 def as_kernel_inputs(sh_features, positions, camera_pos):
   """The float32 contiguous views the kernels read (no copies when the caller already holds such tensors)."""
-  return (sh_features.detach().to(torch.float32).contiguous(), positions.detach().to(torch.float32).contiguous(),
-          camera_pos.detach().to(torch.float32).contiguous())
+  return f32(sh_features), f32(positions), f32(camera_pos)
 
 
 class ShSink(NamedTuple):
@@ -130,20 +130,18 @@ def launch_forward_counted(sh_features, positions, camera_pos, indexes_full, cou
   """K3 over an index buffer whose fill count is still on the device: N-sized outputs, rows past the count are left
   unwritten.  render_gaussians enqueues this right behind K1 + K2 so the GPU has work while the host reads the count
   back; the (out, jac) pair it returns is narrowed to M rows and handed to evaluate_sh_at(_precomputed=...)."""
-  lib = _lib.load()
   sh, pos, cam = as_kernel_inputs(sh_features, positions, camera_pos)
   N, K = indexes_full.shape[0], sh.shape[2]
   out = torch.empty(N, 3, dtype=torch.float32, device=sh.device)
   jac = torch.empty(N, 9, dtype=torch.float32, device=sh.device) if (want_pos_grad and K > 1 and N > 0) else None
-  _lib.check(lib.gsr_sh_forward(_ptr(sh), _ptr(pos), _ptr(indexes_full), N, K, _ptr(cam), _ptr(out), _ptr(jac),
-                                _ptr(count_dev), _stream()), "gsr_sh_forward")
+  _lib.call("gsr_sh_forward", _ptr(sh), _ptr(pos), _ptr(indexes_full), N, K, _ptr(cam), _ptr(out), _ptr(jac),
+            _ptr(count_dev), _stream())
   return out, jac
 
 
 class _SHFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, sh_features, positions, indexes, camera_pos, sink, want_pos_grad, precomputed):
-    lib = _lib.load()
     sh, pos, cam = as_kernel_inputs(sh_features, positions, camera_pos)
     idx = indexes.contiguous()
     M, K = idx.shape[0], sh.shape[2]
@@ -155,8 +153,7 @@ class _SHFn(torch.autograd.Function):
       # splat) spares the backward pass a second sweep over the 12K-byte rows
       # (the camera position's gradient is formed from it too)
       jac = torch.empty(M, 9, dtype=torch.float32, device=sh.device) if (want_pos_grad and K > 1 and M > 0) else None
-      _lib.check(lib.gsr_sh_forward(_ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(out), _ptr(jac), None,
-                                    _stream()), "gsr_sh_forward")
+      _lib.call("gsr_sh_forward", _ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(out), _ptr(jac), None, _stream())
     ctx.save_for_backward(sh, pos, idx, cam)
     ctx.jac = jac
     ctx.sink = sink
@@ -165,7 +162,6 @@ class _SHFn(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, d_out):
-    lib = _lib.load()
     sh, pos, idx, cam = ctx.saved_tensors
     N, _, K = sh.shape
     M = idx.shape[0]
@@ -173,9 +169,9 @@ class _SHFn(torch.autograd.Function):
     if sink is not None and sink.collector is not None:    # data-parallel factor exchange: keep only the colour gradient
       # (4th entry False: this node hands on colour gradients only -- the position term of the colour gradient is left to
       # the multi-camera rebuild, which the exchange then runs WITH the position gradient as a target; K = 1 has no term)
-      sink.collector.items.append((idx, d_out.detach().to(torch.float32).contiguous(), cam, K == 1))
+      sink.collector.items.append((idx, f32(d_out), cam, K == 1))
       return None, None, None, None, None, None, None
-    g = d_out.detach().to(torch.float32).contiguous() if M > 0 else None
+    g = f32(d_out) if M > 0 else None
     _, dest = gradient_destinations("evaluate_sh_at.backward", N, M, K, None, sink)
     if sink is not None:                     # fused "+=" into caller-owned buffers (see renderer.GradOut)
       d_sh, d_pos = sink.d_sh, sink.d_pos
@@ -187,23 +183,22 @@ class _SHFn(torch.autograd.Function):
       inv = None
       if M < N:
         inv = torch.empty(N, dtype=torch.int32, device=pos.device)
-        _lib.check(lib.gsr_inverse_map(_ptr(idx), M, N, _ptr(inv), _stream()), "gsr_inverse_map")
-      _lib.check(lib.gsr_sh_backward_dense(_ptr(g), _ptr(sh), _ptr(pos), _ptr(inv), M, N, K, _ptr(cam), _ptr(ctx.jac),
-                                           _ptr(d_sh), _ptr(d_pos), _stream()), "gsr_sh_backward_dense")
+        _lib.call("gsr_inverse_map", _ptr(idx), M, N, _ptr(inv), _stream())
+      _lib.call("gsr_sh_backward_dense", _ptr(g), _ptr(sh), _ptr(pos), _ptr(inv), M, N, K, _ptr(cam), _ptr(ctx.jac),
+                _ptr(d_sh), _ptr(d_pos), _stream())
     else:
       if dest.zero_fill:
         d_sh.zero_()
       if M > 0:
-        _lib.check(lib.gsr_sh_backward(_ptr(g), _ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(ctx.jac),
-                                       _ptr(d_sh), _ptr(d_pos), 1, _stream()), "gsr_sh_backward")
+        _lib.call("gsr_sh_backward", _ptr(g), _ptr(sh), _ptr(pos), _ptr(idx), M, K, _ptr(cam), _ptr(ctx.jac), _ptr(d_sh),
+                  _ptr(d_pos), 1, _stream())
     d_cam = None
     if ctx.needs_input_grad[3]:
       # the colour depends on positions - camera_pos: minus the position term of every splat, summed in a fixed order
       d_cam = torch.empty(3, dtype=torch.float32, device=pos.device)
-      rows = int(lib.gsr_camera_grad_partial_rows(M)) if ctx.jac is not None else 0
+      rows = int(_lib.load().gsr_camera_grad_partial_rows(M)) if ctx.jac is not None else 0
       partials = torch.empty(max(rows, 1) * 20, dtype=torch.float32, device=pos.device)
-      _lib.check(lib.gsr_sh_camera_position_grad(_ptr(g), _ptr(ctx.jac), M, _ptr(partials), _ptr(d_cam), _stream()),
-                 "gsr_sh_camera_position_grad")
+      _lib.call("gsr_sh_camera_position_grad", _ptr(g), _ptr(ctx.jac), M, _ptr(partials), _ptr(d_cam), _stream())
       d_cam = d_cam.to(ctx.in_dtypes[2])
     if sink is not None:
       return None, None, None, d_cam, None, None, None

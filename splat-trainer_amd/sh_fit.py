@@ -22,8 +22,10 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._args import f32, require
+from ._lib import ptr as _ptr
 
-_ptr = _lib.ptr
+WHAT = "the SH fit"
 
 MIN_RIDGE = 1e-6
 # The lowest mean held-out colour error among 1e-3, 1e-2 and 1e-1 over 4, 8, 16 and 32 noisy views of degree-3 colours
@@ -41,18 +43,11 @@ class ShFit:
   def __init__(self, positions: torch.Tensor, sh_degree: int = 2):
     if sh_degree not in (0, 1, 2, 3):
       raise ValueError(f"sh_degree must be 0..3, got {sh_degree!r}")
-    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3:
-      raise ValueError(f"positions must be a tensor of shape (N, 3), got "
-                       f"{tuple(positions.shape) if isinstance(positions, torch.Tensor) else type(positions).__name__}")
-    if not positions.is_cuda:
-      raise _lib.GsplatHipError(f"positions is on {positions.device}: the SH fit runs on the HIP device only "
-                                "(there is no CPU fallback)")
     self.sh_degree = int(sh_degree)
     self.K = (self.sh_degree + 1) ** 2
-    self.positions = positions.detach().to(torch.float32).contiguous()
+    self.positions = f32(require("positions", positions, shape=("N", 3), what=WHAT))
     self.N = int(self.positions.shape[0])
-    lib = _lib.load()
-    assert lib.gsr_sh_fit_row_doubles(self.K) == _row_doubles(self.K)
+    assert _lib.load().gsr_sh_fit_row_doubles(self.K) == _row_doubles(self.K)
     self.acc = torch.zeros(self.N, _row_doubles(self.K), dtype=torch.float64, device=self.positions.device)
 
   @staticmethod
@@ -69,11 +64,8 @@ class ShFit:
     tensors = (("indexes", indexes), ("colors", colors), ("weights", weights), ("camera_position", camera_position))
     for name, t in tensors:
       if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-      if not t.is_cuda:
-        raise _lib.GsplatHipError(f"{name} is on {t.device}: the SH fit runs on the HIP device only "
-                                  "(there is no CPU fallback)")
-      if t.device != self.acc.device:
+        raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")       # (this method's own type for it)
+      if require(name, t, what=WHAT).device != self.acc.device:
         raise ValueError(f"{name} is on {t.device}, the fit on {self.acc.device}")
     if indexes.dtype != torch.int64:
       raise TypeError("indexes must be int64")
@@ -87,13 +79,10 @@ class ShFit:
     if M == 0:
       return
     idx = indexes.contiguous()
-    col = colors.detach().to(torch.float32).contiguous()
-    w = weights.detach().to(torch.float32).contiguous()
-    cam = camera_position.detach().to(torch.float32).reshape(3).contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(self.acc.device):
-      _lib.check(lib.gsr_sh_fit_accumulate(_ptr(self.positions), self.N, _ptr(idx), M, _ptr(col), _ptr(w), _ptr(cam),
-                                           self.K, _ptr(self.acc), _lib.current_stream_ptr()), "gsr_sh_fit_accumulate")
+    col, w, cam = f32(colors), f32(weights), f32(camera_position).reshape(3)
+    with _lib.on_device(self.acc.device) as stream:
+      _lib.call("gsr_sh_fit_accumulate", _ptr(self.positions), self.N, _ptr(idx), M, _ptr(col), _ptr(w), _ptr(cam), self.K,
+                _ptr(self.acc), stream)
 
   def solve(self, ridge: float = DEFAULT_RIDGE) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(sh (N, 3, K) float32, weight (N,) float32)``: the minimiser per point and the sum of its weights.  A point no
@@ -108,10 +97,8 @@ class ShFit:
     weight = torch.empty(self.N, dtype=torch.float32, device=dev)
     if self.N == 0:
       return sh, weight
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-      _lib.check(lib.gsr_sh_fit_solve(_ptr(self.acc), self.N, self.K, ridge, _ptr(sh), _ptr(weight),
-                                      _lib.current_stream_ptr()), "gsr_sh_fit_solve")
+    with _lib.on_device(dev) as stream:
+      _lib.call("gsr_sh_fit_solve", _ptr(self.acc), self.N, self.K, ridge, _ptr(sh), _ptr(weight), stream)
     return sh, weight
 
 

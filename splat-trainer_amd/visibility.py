@@ -34,7 +34,9 @@ import torch.nn.functional as F
 
 from . import _lib
 from .data_types import CameraParams
-from .neighbours import _points, _ptr, assign_clusters, kmeans
+from ._args import require
+from ._lib import ptr as _ptr
+from .neighbours import _cloud, assign_clusters, kmeans
 
 
 # ---- cameras ------------------------------------------------------------------------------------------------------
@@ -63,16 +65,10 @@ class CameraBatch:
 
   def __post_init__(self):
     V = self.camera_t_world.shape[0] if isinstance(self.camera_t_world, torch.Tensor) and self.camera_t_world.dim() else -1
-    for name, shape, floating in (("camera_t_world", (V, 4, 4), True), ("intrinsics", (V, 4), True),
-                                  ("image_sizes", (V, 2), None), ("depth_ranges", (V, 2), True)):
-      t = getattr(self, name)
-      if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
-      if tuple(t.shape) != shape:
-        raise ValueError(f"{name} must have shape {('V',) + shape[1:]} with one V, got {tuple(t.shape)}")
-      if floating and t.dtype is not torch.float32:
-        raise ValueError(f"{name} must be float32, got {t.dtype}")
-      if floating is None and (t.dtype.is_floating_point or t.dtype is torch.bool or t.dtype.is_complex):
+    for name, shape, dtype in (("camera_t_world", ("V", 4, 4), torch.float32), ("intrinsics", (V, 4), torch.float32),
+                               ("image_sizes", (V, 2), None), ("depth_ranges", (V, 2), torch.float32)):
+      t = require(name, getattr(self, name), shape=shape, dtype=dtype)
+      if dtype is None and (t.dtype.is_floating_point or t.dtype is torch.bool or t.dtype.is_complex):
         raise ValueError(f"image_sizes must be an integer tensor, got {t.dtype}")
       if t.device != self.camera_t_world.device:
         raise ValueError(f"{name} on {t.device} and camera_t_world on {self.camera_t_world.device}")
@@ -134,7 +130,7 @@ class CameraBatch:
 
 def _query_args(cameras: Any, points: torch.Tensor) -> Tuple[CameraBatch, torch.Tensor]:
   cams = CameraBatch.of(cameras)
-  p = _points(points, "points")
+  p = _cloud(points, "points")
   if not cams.camera_t_world.is_cuda:
     raise ValueError("cameras must be on the HIP device (cuda); there is no CPU fallback")
   if cams.device != p.device:
@@ -145,14 +141,12 @@ def _query_args(cameras: Any, points: torch.Tensor) -> Tuple[CameraBatch, torch.
 def _frustum(cameras: Any, points: torch.Tensor, depth_below, want_points: bool, want_cameras: bool):
   cams, p = _query_args(cameras, points)
   below = math.inf if depth_below is None else float(depth_below)
-  lib = _lib.load()
-  with torch.cuda.device(p.device):
+  with _lib.on_device(p.device) as stream:
     rec = cams.records()
     V = rec.shape[0]
     pc = torch.empty(p.shape[0], dtype=torch.int32, device=p.device) if want_points else None
     cc = torch.empty(V, dtype=torch.int32, device=p.device) if want_cameras else None
-    _lib.check(lib.gsr_frustum_counts(_ptr(p), p.shape[0], _ptr(rec), V, below, _ptr(pc), _ptr(cc),
-                                      _lib.current_stream_ptr()), "gsr_frustum_counts")
+    _lib.call("gsr_frustum_counts", _ptr(p), p.shape[0], _ptr(rec), V, below, _ptr(pc), _ptr(cc), stream)
   return pc, cc
 
 
@@ -331,22 +325,18 @@ class PointClusters:
     N, K = labels.shape[0], self.num_clusters
     if not 1 <= N <= _lib.NEIGHBOURS_MAX_N or K < 1:
       raise ValueError(f"PointClusters needs 1..{_lib.NEIGHBOURS_MAX_N} points and at least one cluster, got {N}, {K}")
-    lib = _lib.load()
     dev = labels.device
-    with torch.cuda.device(dev):
+    with _lib.on_device(dev) as stream:
       if bool(((labels < 0) | (labels >= K)).any()):
         raise ValueError(f"point_labels must lie in [0, {K})")
       keys_a = labels.to(torch.int32)
       vals_a, keys_b, vals_b = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(3))
-      ws_bytes = lib.gsr_sort_workspace_bytes(N)
-      ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-      stream = _lib.current_stream_ptr()
-      where = _lib.check(lib.gsr_sort_pairs_u32(_ptr(keys_a), _ptr(vals_a), _ptr(keys_b), _ptr(vals_b), N, 1, 0,
-                                                max(1, (K - 1).bit_length()), _ptr(ws), ws_bytes, None, stream),
-                         "gsr_sort_pairs_u32")
+      ws = _lib.workspace(_lib.load().gsr_sort_workspace_bytes(N), dev)
+      where = _lib.call("gsr_sort_pairs_u32", _ptr(keys_a), _ptr(vals_a), _ptr(keys_b), _ptr(vals_b), N, 1, 0,
+                        max(1, (K - 1).bit_length()), _ptr(ws), ws.numel(), None, stream)
       skeys, svals = (keys_b, vals_b) if where else (keys_a, vals_a)
       ranges = torch.zeros((K, 2), dtype=torch.int32, device=dev)
-      _lib.check(lib.gsr_tile_ranges(_ptr(skeys), N, K, _ptr(ranges), None, stream), "gsr_tile_ranges")
+      _lib.call("gsr_tile_ranges", _ptr(skeys), N, K, _ptr(ranges), None, stream)
       dense = torch.empty(N, dtype=torch.float32, device=dev)
       slots = torch.empty(N, dtype=torch.float32, device=dev)
     self._order = (skeys, svals, ranges, dense, slots)
@@ -360,14 +350,7 @@ class PointClusters:
     ``validate=True`` checks range and distinctness (one sync) and raises ValueError."""
     labels = self.point_labels
     for t, name, dtype in ((point_idx, "point_idx", torch.int64), (point_vis, "point_vis", torch.float32)):
-      if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
-      if t.dim() != 1:
-        raise ValueError(f"{name} must have shape (M,), got {tuple(t.shape)}")
-      if t.dtype is not dtype:
-        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-      if not t.is_cuda:
-        raise ValueError(f"{name} must be on the HIP device (cuda); there is no CPU fallback")
+      require(name, t, shape=("M",), dtype=dtype, what="a view's features", device_error=ValueError)
       if isinstance(labels, torch.Tensor) and t.device != labels.device:
         raise ValueError(f"{name} on {t.device} and point_labels on {labels.device}")
     if point_idx.shape != point_vis.shape:
@@ -383,16 +366,15 @@ class PointClusters:
         raise ValueError(f"point_visible must be a contiguous ({N},) int32 tensor on {labels.device}")
     idx = point_idx.contiguous()
     vis = point_vis.detach().contiguous()
-    with torch.cuda.device(labels.device):
+    with _lib.on_device(labels.device) as stream:
       if validate and M > 0:
         ordered = idx.sort().values
         bad = (ordered[0] < 0) | (ordered[-1] >= N) | (ordered[1:] == ordered[:-1]).any()
         if bool(bad):
           raise ValueError(f"point_idx must hold distinct indices in [0, {N})")
       out = torch.empty(K, dtype=torch.float32, device=labels.device)
-      _lib.check(_lib.load().gsr_view_features(_ptr(idx), _ptr(vis), M, float(vis_threshold), _ptr(skeys), _ptr(svals),
-                                               _ptr(ranges), N, K, _ptr(dense), _ptr(slots), _ptr(out),
-                                               _ptr(point_visible), _lib.current_stream_ptr()), "gsr_view_features")
+      _lib.call("gsr_view_features", _ptr(idx), _ptr(vis), M, float(vis_threshold), _ptr(skeys), _ptr(svals), _ptr(ranges),
+                N, K, _ptr(dense), _ptr(slots), _ptr(out), _ptr(point_visible), stream)
     return out
 
   def rendering_features(self, rendering: Any, vis_threshold: float = 0.01,
