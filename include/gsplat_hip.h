@@ -915,6 +915,43 @@ int gsr_histogram(const float* values, int64_t N, int64_t C, const int64_t* rows
 int gsr_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, uint8_t* dst, int32_t Hd,
                              int32_t Wd, void* stream);
 
+/* ---- lens undistortion (the scan loader's cv2.undistort; csrc/undistort.hip) ---------------------------- */
+/* Two calls: the map of a distorted camera onto a pinhole target, once per camera, and the bilinear remap of images
+ * through a map.  csrc/gsr_undistort.h is the one statement of the arithmetic of both, shared with the host shim.
+ * Pixel centres sit at integer coordinates (OpenCV's convention; COLMAP's are half a pixel further).
+ *
+ * gsr_undistort_map.  source_host [9] = fx fy cx cy k1 k2 p1 p2 k3 (OpenCV's five-coefficient model) and target_host [4]
+ * = fx' fy' cx' cy' are HOST memory, read before the call returns.  map_out [Hd, Wd, 2] int32, device memory, 8-byte
+ * aligned: for destination pixel (u, v) the source position (X, Y) in units of 1/32 pixel.  In fp64, every product and
+ * sum rounded on its own, in this order (ifx' = 1 / fx', ify' = 1 / fy' formed once on the host):
+ *   x = (u - cx') * ifx'            y = (v - cy') * ify'
+ *   xx = x*x   yy = y*y   xy = x*y   r2 = xx + yy
+ *   t = r2*k3; t = k2 + t; t = r2*t; t = k1 + t; t = r2*t; rad = 1 + t
+ *   a = (2*p1)*xy; b = 2*xx; b = r2 + b; b = p2*b; dx = a + b
+ *   a = 2*yy; a = r2 + a; a = p1*a; b = (2*p2)*xy; dy = a + b
+ *   xd = x*rad; xd = xd + dx        yd = y*rad; yd = yd + dy
+ *   xs = fx*xd; xs = xs + cx        ys = fy*yd; ys = ys + cy
+ * then xs is clamped to [-1, Ws] and ys to [-1, Hs] (NaN becomes -1) and X = floor(xs*32 + 0.5), Y likewise.
+ * Checked before any HIP call, in this order: a negative size is GSR_ERR_INVALID_ARGUMENT; a side above 32768
+ * GSR_ERR_UNSUPPORTED; a NULL source_host or target_host, a parameter that is not finite, or fx, fy, fx', fy' not above
+ * 0 GSR_ERR_INVALID_ARGUMENT; Hd == 0 or Wd == 0 is GSR_OK with no launch; a NULL map_out, looked at last,
+ * GSR_ERR_INVALID_ARGUMENT.
+ *
+ * gsr_image_remap_u8.  src (B, Hs, Ws, C) -> dst (B, Hd, Wd, C) through map [Hd, Wd, 2] (8-byte aligned), one map for
+ * the whole batch; both images contiguous with interleaved channels, C in {1, 3}, no alignment asked of either; src and
+ * dst must not overlap (not checked).  An entry (X, Y), any int32, is first clamped to [-32, 32 Ws] x [-32, 32 Hs];
+ * x0 = X >> 5 (floor) and ax = X & 31 give the taps x0 with weight 32 - ax and x0 + 1 with weight ax, likewise in y; a
+ * tap outside the source, or one of weight 0, contributes 0, and out = (sum of wy wx byte + 512) >> 10.  All integer:
+ * the result is a function of the inputs alone, the same bits on every run.  An empty source (Hs == 0 or Ws == 0) has
+ * every tap outside: dst is zero-filled.
+ * Checked before any HIP call, in this order: a negative size is GSR_ERR_INVALID_ARGUMENT; C outside {1, 3}, or a side
+ * above 32768, GSR_ERR_UNSUPPORTED; B == 0, Hd == 0 or Wd == 0 is GSR_OK with no launch and dst untouched; a NULL map or
+ * dst, or a NULL src of a source that has pixels, looked at last, GSR_ERR_INVALID_ARGUMENT. */
+int gsr_undistort_map(const double* source_host, const double* target_host, int32_t Hs, int32_t Ws, int32_t Hd,
+                      int32_t Wd, int32_t* map_out, void* stream);
+int gsr_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map,
+                       uint8_t* dst, int32_t Hd, int32_t Wd, void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -32,6 +32,7 @@ from .camera_table import (Camera, CameraRigTable, CameraTable, Cameras, Label, 
 from .normalization import Normalization, NormalizationConfig, median_knn
 from .histogram import Histogram, tensor_histogram
 from .image import resize_area
+from .undistort import LensCamera, Undistortion, optimal_pinhole, remap, undistort_map
 from .colmap_io import read_model, write_model
 from .colmap import COLMAPDataset, export_colmap
 from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
@@ -67,4 +68,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "from_pointcloud", "from_scaled_pointcloud", "to_pointcloud", "get_initial_gaussians", "TargetOverlapConfig",
            "TargetOverlap", "TrainConfig", "TrainerState", "TrainingException", "NaNParameterException",
            "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer",
-           "resize_area", "read_model", "write_model", "COLMAPDataset", "export_colmap"]
+           "resize_area", "LensCamera", "Undistortion", "optimal_pinhole", "undistort_map", "remap", "read_model",
+           "write_model", "COLMAPDataset", "export_colmap"]

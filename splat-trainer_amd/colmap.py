@@ -5,7 +5,9 @@ dataset's device, the same arithmetic on the host when there is no GPU -- the tw
 
 Deliberate deviations from the reference: images come in ascending ``image_id`` (``colmap_io``), so the split is defined
 by the files alone; SIMPLE_PINHOLE is accepted beside PINHOLE and any other model raises ``ValueError`` (the reference
-asserts); a scale above 1 raises, because the resize only shrinks; the normalisation is fitted on the host in float64
+asserts) unless ``undistort=True``, which takes SIMPLE_RADIAL, RADIAL and OPENCV cameras too: their images are remapped
+onto the optimal pinhole view of the same size (``undistort.Undistortion``, csrc/undistort.hip) before the resize, and
+the projection table holds that view; a scale above 1 raises, because the resize only shrinks; the normalisation is fitted on the host in float64
 (``median_knn`` over the camera centres needs no device and has no limit on ``normalize_knn``); a model without points
 gives ``pointcloud() is None``.  The resize is the exact area mean rounded half up, where cv2's ``INTER_AREA`` computes
 the same mean in float ("COLMAP datasets").
@@ -25,26 +27,32 @@ from .camera_table import CameraTable, Label, MultiCameraTable, Projections, rot
 from .dataset import Dataset, ImageView, PointCloud, split_every
 from .image import resize_area
 from .normalization import Normalization, NormalizationConfig
+from .undistort import LensCamera, Undistortion, to_colmap_intrinsics
 
 STAGING_BYTES = 256 << 20            # full-resolution images held at once while loading
+DISTORTED_MODELS = ("SIMPLE_RADIAL", "RADIAL", "OPENCV")      # what undistort=True takes beside the pinhole models
 
 
 def decode_threads() -> int:
   return max(1, min(16, (os.cpu_count() or 2) // 2))
 
 
-def colmap_projection(camera: colmap_io.Camera, image_scale: Optional[float] = None, resize_longest: Optional[int] = None
-                      ) -> Tuple[np.ndarray, Tuple[int, int]]:
+def colmap_projection(camera: colmap_io.Camera, image_scale: Optional[float] = None, resize_longest: Optional[int] = None,
+                      undistortion: Optional[Undistortion] = None) -> Tuple[np.ndarray, Tuple[int, int]]:
   """(fx, fy, cx, cy as float64, (width, height)) of a PINHOLE or SIMPLE_PINHOLE camera after the resize: intrinsics
-  times the scale and ``round`` of the scaled size, as the reference computes them."""
-  if camera.model == "PINHOLE":
+  times the scale and ``round`` of the scaled size, as the reference computes them.  With ``undistortion`` (of this
+  camera) the intrinsics are its target's, taken back to COLMAP's pixel-centre convention, whatever the model."""
+  if undistortion is not None:
+    proj = np.array(to_colmap_intrinsics(undistortion.target), np.float64)
+  elif camera.model == "PINHOLE":
     proj = np.array(camera.params, np.float64)
   elif camera.model == "SIMPLE_PINHOLE":
     f, cx, cy = (float(v) for v in camera.params)
     proj = np.array([f, f, cx, cy], np.float64)
   else:
     raise ValueError(f"camera model {camera.model} is not supported: only PINHOLE and SIMPLE_PINHOLE are, so the images "
-                     "must be undistorted first (COLMAP's image_undistorter)")
+                     "must be undistorted first (COLMAP's image_undistorter, or undistort=True for "
+                     f"{', '.join(DISTORTED_MODELS)})")
   w, h = int(camera.width), int(camera.height)
   if resize_longest is not None:
     image_scale = resize_longest / max(w, h)
@@ -100,7 +108,7 @@ class COLMAPDataset(Dataset):
   def __init__(self, base_path: Union[str, Path], model_dir: str = "sparse/0", image_dir: str = "images",
                image_scale: Optional[float] = None, resize_longest: Optional[int] = None, test_every: int = 8,
                depth_range: Tuple[float, float] = (0.1, 100.0), normalize: NormalizationConfig = NormalizationConfig(),
-               device=None, resident: bool = False):
+               device=None, resident: bool = False, undistort: bool = False):
     if image_scale is not None and resize_longest is not None:
       raise ValueError("Specify either resize_longest or image_scale (not both)")
     self.base_path, self.image_dir = str(base_path), image_dir
@@ -116,8 +124,11 @@ class COLMAPDataset(Dataset):
     if not images:
       raise ValueError(f"{Path(base_path) / model_dir}: the model has no images")
     id_to_camera_idx, projections, self.source_sizes = {}, [], []
+    self.undistortions: List[Optional[Undistortion]] = []                       # per camera; None: a pinhole as it is
     for i, (camera_id, camera) in enumerate(cameras.items()):                   # ascending camera id
-      proj, size = colmap_projection(camera, image_scale, resize_longest)
+      lens = LensCamera.from_colmap(camera) if undistort and camera.model in DISTORTED_MODELS else None
+      self.undistortions.append(Undistortion(lens) if lens is not None else None)
+      proj, size = colmap_projection(camera, image_scale, resize_longest, self.undistortions[-1])
       projections.append((proj, size))
       self.source_sizes.append((int(camera.width), int(camera.height)))
       id_to_camera_idx[camera_id] = i
@@ -172,7 +183,8 @@ class COLMAPDataset(Dataset):
     return torch.from_numpy(pixels.copy())
 
   def _load(self) -> List[torch.Tensor]:
-    """Every image, decoded by a pool of threads and resized one batch of one camera's images at a time: no more than
+    """Every image, decoded by a pool of threads, undistorted where its camera asks for it and resized, one batch of
+    one camera's images at a time: no more than
     STAGING_BYTES of full-resolution pixels (or one image) are held at once."""
     out: List[Optional[torch.Tensor]] = [None] * self.num_images
     on_device = self.device.type == "cuda"
@@ -186,6 +198,8 @@ class COLMAPDataset(Dataset):
           stack = torch.stack(pool.map(self._decode, batch))
           if on_device:
             stack = stack.to(self.device)
+          if self.undistortions[cam] is not None:                                 # at full resolution, before the resize
+            stack = self.undistortions[cam](stack)
           if (wd, hd) != (ws, hs):
             stack = resize_area(stack, (hd, wd))
           if on_device and not self.resident:

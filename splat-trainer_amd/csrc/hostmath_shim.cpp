@@ -19,6 +19,7 @@
 #include "gsr_eval.h"
 #include "gsr_histogram.h"
 #include "gsr_image.h"
+#include "gsr_undistort.h"
 
 extern "C" {
 
@@ -691,6 +692,63 @@ int hm_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t W
 void hm_image_round_div(const uint64_t* sum, int64_t n, int32_t Ws, int32_t Hs, uint32_t* out) {
   const GsrImageDivisor dv = gsr_image_divisor(Ws, Hs);
   for (int64_t i = 0; i < n; ++i) out[i] = gsr_image_round_div(sum[i], dv.m, dv.D, dv.shift);
+}
+
+// ---- lens undistortion (gsr_undistort.h) ----
+int hm_undistort_map(const double* source, const double* target, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd,
+                     int32_t* map_out) {
+  int launch = 0;
+  const int rc = gsr_undistort_map_check(source, target, Hs, Ws, Hd, Wd, map_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrLens m = gsr_lens_make(source, target);
+  for (int32_t v = 0; v < Hd; ++v)
+    for (int32_t u = 0; u < Wd; ++u) {
+      double xs, ys;
+      gsr_undistort_point(m, (double)u, (double)v, &xs, &ys);
+      int32_t* out = map_out + 2 * ((int64_t)v * Wd + u);
+      out[0] = gsr_undistort_quantise(xs, Ws);
+      out[1] = gsr_undistort_quantise(ys, Hs);
+    }
+  return GSR_OK;
+}
+
+void hm_undistort_points(const double* source, const double* target, int32_t Hs, int32_t Ws, int64_t n, const double* uv,
+                         int32_t* out) {
+  const GsrLens m = gsr_lens_make(source, target);
+  for (int64_t i = 0; i < n; ++i) {
+    double xs, ys;
+    gsr_undistort_point(m, uv[2 * i], uv[2 * i + 1], &xs, &ys);
+    out[2 * i] = gsr_undistort_quantise(xs, Ws);
+    out[2 * i + 1] = gsr_undistort_quantise(ys, Hs);
+  }
+}
+
+int hm_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map, uint8_t* dst,
+                      int32_t Hd, int32_t Wd) {
+  int launch = 0;
+  const int rc = gsr_image_remap_check(src, B, Hs, Ws, C, map, dst, Hd, Wd, &launch);
+  if (rc < 0 || !launch) return rc;
+  const int64_t n_px = (int64_t)Hd * Wd;
+  if (Hs == 0 || Ws == 0) {                                            // every tap lies outside an empty source
+    memset(dst, 0, (size_t)B * n_px * C);
+    return GSR_OK;
+  }
+  for (int64_t i = 0; i < n_px; ++i) {
+    const GsrRemapAxis ax = gsr_remap_axis(map[2 * i], Ws), ay = gsr_remap_axis(map[2 * i + 1], Hs);
+    const uint32_t w[4] = {ay.w0 * ax.w0, ay.w0 * ax.w1, ay.w1 * ax.w0, ay.w1 * ax.w1};
+    const int64_t at[4] = {((int64_t)ay.i0 * Ws + ax.i0) * C, ((int64_t)ay.i0 * Ws + ax.i1) * C,
+                           ((int64_t)ay.i1 * Ws + ax.i0) * C, ((int64_t)ay.i1 * Ws + ax.i1) * C};
+    for (int64_t b = 0; b < B; ++b) {
+      const uint8_t* image = src + b * Hs * (int64_t)Ws * C;
+      for (int32_t c = 0; c < C; ++c) {
+        uint32_t sum = 0;
+        for (int k = 0; k < 4; ++k)
+          if (w[k]) sum += w[k] * image[at[k] + c];
+        dst[(b * n_px + i) * C + c] = (uint8_t)gsr_remap_round(sum);
+      }
+    }
+  }
+  return GSR_OK;
 }
 
 }  // extern "C"

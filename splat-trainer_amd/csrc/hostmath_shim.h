@@ -137,6 +137,17 @@ int hm_image_resize_area_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t W
 /* out [n] = floor((2 sum[i] + D) / (2 D)) by the multiply-shift of gsr_image_divisor(Ws, Hs); sum[i] <= 255 Ws Hs */
 void hm_image_round_div(const uint64_t* sum, int64_t n, int32_t Ws, int32_t Hs, uint32_t* out);
 
+/* ---- lens undistortion (gsr_undistort.h): the device's arithmetic in plain loops ---- */
+/* gsr_undistort_map on host memory, with its argument checks and its codes: source [9], target [4], map_out [Hd, Wd, 2] */
+int hm_undistort_map(const double* source, const double* target, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd,
+                     int32_t* map_out);
+/* the same map at n destination coordinates uv [n, 2] (whole numbers held as doubles): out [n, 2].  No checks. */
+void hm_undistort_points(const double* source, const double* target, int32_t Hs, int32_t Ws, int64_t n, const double* uv,
+                         int32_t* out);
+/* gsr_image_remap_u8 on host memory, with its argument checks and its codes */
+int hm_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map, uint8_t* dst,
+                      int32_t Hd, int32_t Wd);
+
 #ifdef __cplusplus
 }
 #endif

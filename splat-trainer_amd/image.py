@@ -21,12 +21,14 @@ from . import _lib
 HOST_LIB_PATH = os.path.join(_lib.PKG_DIR, "libgsr_hostmath.so")
 HOST_HEADER_PATH = os.path.join(_lib.PKG_DIR, "csrc", "hostmath_shim.h")
 MAX_SIDE = 32768
+# what the package itself calls of the host library: the area resize, and the undistortion (undistort.py)
+HOST_FUNCTIONS = ("hm_image_resize_area_u8", "hm_undistort_map", "hm_undistort_points", "hm_image_remap_u8")
 _host_lib = None
 _lock = threading.Lock()
 
 
 def _host():
-  """The host library with ``hm_image_resize_area_u8`` bound from its header's declaration (once)."""
+  """The host library with ``HOST_FUNCTIONS`` bound from its header's declarations (once)."""
   global _host_lib
   with _lock:
     if _host_lib is None:
@@ -34,10 +36,10 @@ def _host():
         raise _lib.GsplatHipError(f"{HOST_LIB_PATH} not found: build it with `python splat-trainer_amd/build.py`")
       with open(HOST_HEADER_PATH) as f:
         functions = _lib.parse_header(f.read(), prefix="hm_", filename="hostmath_shim.h")[2]
-      name = "hm_image_resize_area_u8"
       lib = C.CDLL(HOST_LIB_PATH)
-      fn = getattr(lib, name)
-      fn.restype, fn.argtypes = _lib.make_prototypes({name: functions[name]}, {})[name]
+      for name in HOST_FUNCTIONS:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.make_prototypes({name: functions[name]}, {})[name]
       _host_lib = lib
   return _host_lib
 
