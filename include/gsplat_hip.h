@@ -745,6 +745,60 @@ int gsr_mcmc_noise(float* position, const float* log_scaling, const float* rotat
                    float noise_level, float scale_eps, uint64_t seed, uint64_t step, void* stream);
 int gsr_mcmc_draws(int64_t N, uint64_t seed, uint64_t step, uint32_t* words_out, float* normals_out, void* stream);
 
+/* ---- MCMC relocation (Kheradmand et al., "3D Gaussian Splatting as Markov Chain Monte Carlo", 2024; no reference
+ *      counterpart; csrc/relocate.hip) -------------------------------------------------------------------------------
+ * Dead Gaussians are moved onto live ones drawn with probability proportional to opacity, and the opacity and scale of a
+ * source and its copies are corrected so that the rendered distribution stays (Eq. 9).  csrc/gsr_relocate.h is the one
+ * statement of the arithmetic, shared with the host shim.  Every call is enqueued on the stream without a host wait.
+ *
+ * gsr_weighted_draws (integers only).  weights [N] uint32, 0 = cannot be drawn; P_i the inclusive prefix sum of the
+ *   weights in uint64, S = P_{N-1} (0 for N == 0).  Draw k = 0..n-1 takes the Philox4x32-10 words at key (seed lo, seed hi),
+ *   counter (k lo, k hi, step lo, (step hi & 0x00FFFFFF) | domain << 24) -- gsr_mcmc_noise's counter is domain 0 for every
+ *   step below 2^56, relocation uses 1 and growth 2, so the streams of one seed never share a counter --,
+ *   r = word0 2^32 + word1, t = floor(r S / 2^64) (the high half of the 128-bit product), and
+ *   sources_out[k] = the smallest i with P_i > t.  counts_out [N] int32 is zero-filled by the call and then
+ *   counts_out[i] = the number of draws that gave i (integer atomics: order cannot change the result);
+ *   total_out[0] = S, a device uint64.  S == 0: every source is -1, every count 0, GSR_OK.  The result is a function of
+ *   (weights, seed, step, domain, k) alone -- not of n, of the launch shape or of the device -- and equals an integer
+ *   oracle bit for bit.  t takes every value of [0, S) floor(2^64 / S) or one more time: a weight's share of the draws is
+ *   off by at most S / 2^64 of itself, below 2^-18 at 3 M rows of weight 2^24.  S < 2^56 is the caller's to keep (any
+ *   weights of gsr_relocate_weights do).  weights and counts_out 16-byte aligned; workspace (16-byte aligned) of
+ *   gsr_weighted_draws_workspace_bytes(N): one uint64 per 256 rows, the prefix at the end of each block of rows.
+ *   Checked in this order: N, n outside [0, GSR_NEIGHBOURS_MAX_N] or domain outside [0, 255] GSR_ERR_INVALID_ARGUMENT; a
+ *   NULL total_out, a NULL weights or counts_out with N > 0, a NULL sources_out with n > 0, or weights / counts_out not
+ *   16-byte aligned GSR_ERR_INVALID_ARGUMENT; a NULL or short workspace GSR_ERR_WORKSPACE_TOO_SMALL; a workspace not
+ *   16-byte aligned GSR_ERR_INVALID_ARGUMENT.
+ * gsr_relocate_weights: weights_out[i] = 0 where alive[i] == 0 (alive [N] bytes; NULL: every row is alive), else
+ *   max(1, floor(2^24 sigmoid(alpha_logit[i]))), the sigmoid in fp64 from the float32 logit (a NaN logit gives 1).  Device
+ *   and host libm differ in the last bits of exp: within 1 of an exact oracle.  0 <= N <= GSR_NEIGHBOURS_MAX_N (0: GSR_OK,
+ *   no launch, before any pointer is looked at).
+ * gsr_relocate_rescale, in place on alpha_logit [N] and log_scaling [N, 3] float32.  A row with counts[i] = c >= 1 is the
+ *   source of c copies; a row with c <= 0 is neither read beyond its count nor written.  n = min(c + 1, 51),
+ *   o = sigmoid(a), o' = 1 - (1 - o)^(1/n), D = sum_{k=0..n-1} C(n, k+1) (-1)^k o'^(k+1) / sqrt(k+1), coeff = o / D, in fp64;
+ *   alpha_logit <- float32(logit(clamp(o', o_floor, 1 - 2^-24))), log_scaling_j <- float32(double(log_scaling_j) +
+ *   log(coeff)).  The coefficient uses the unclamped o'.  0 < o_floor < 1; N as above (0: GSR_OK before the pointers).
+ * gsr_relocate_rows: one launch over n_columns <= GSR_MAX_COLUMNS columns of N rows.  For k < n, row dst_rows[k] of every
+ *   column with zero == 0 takes row src_rows[k]; rows dst_rows[k] and src_rows[k] of every column with zero != 0 are
+ *   zero-filled.  PRECONDITION: the dst rows are unique and disjoint from the src rows; then the result does not depend
+ *   on order.  A k whose dst or src index lies outside [0, N) (the -1 of S == 0 included) is skipped.  data 4-byte aligned;
+ *   a column whose width and address allow it moves 16 or 8 bytes at a time.  Checked in this order: a negative or too
+ *   large n, N or n_columns GSR_ERR_INVALID_ARGUMENT; n, N or n_columns == 0 GSR_OK; a NULL dst_rows, src_rows or
+ *   columns_host, or a column with NULL or misaligned data or width_dwords outside [1, 2^20], GSR_ERR_INVALID_ARGUMENT. */
+typedef struct GsrRowColumnC {
+  void* data;            /* [N, width] 4-byte words, moved in place */
+  int32_t width_dwords;
+  int32_t zero;          /* 0: row dst takes row src; otherwise both rows are zero-filled */
+} GsrRowColumnC;
+size_t gsr_weighted_draws_workspace_bytes(int64_t N);
+int gsr_weighted_draws(const uint32_t* weights, int64_t N, int64_t n, uint64_t seed, uint64_t step, int32_t domain,
+                       int32_t* sources_out, int32_t* counts_out, uint64_t* total_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int gsr_relocate_weights(const float* alpha_logit, const uint8_t* alive, int64_t N, uint32_t* weights_out, void* stream);
+int gsr_relocate_rescale(float* alpha_logit, float* log_scaling, const int32_t* counts, int64_t N, float o_floor,
+                         void* stream);
+int gsr_relocate_rows(const int32_t* dst_rows, const int32_t* src_rows, int64_t n, int64_t N,
+                      const GsrRowColumnC* columns_host, int32_t n_columns, void* stream);
+
 /* ---- SH export fit: per-point least squares of SH coefficients to view-dependent colours (no reference counterpart) ----
  * One row of gsr_sh_fit_row_doubles(K) = K (K + 1) / 2 + 3 K + 1 doubles per point (0 for a K outside {1, 4, 9, 16}): the
  * lower triangle of G = sum w Y Y^T, b_c = sum w Y (y_c - 0.5) channel-major, W = sum w, with Y the basis of gsr_sh_forward

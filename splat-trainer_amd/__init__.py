@@ -25,7 +25,8 @@ from .evaluation import (Evaluation, compute_psnr, evaluate_scene, fit_colors, f
 from .filter3d import sampling_rate, smooth_gaussians
 from .sh_fit import ShFit, fit_sh
 from .controller import (Controller, ControllerConfig, DisabledConfig, DisabledController, MCMCConfig, MCMCController,
-                         Progress, TargetConfig, TargetController, densify_and_prune, mcmc_noise)
+                         Progress, TargetConfig, TargetController, densify_and_prune, grow_points, growth_target,
+                         mcmc_noise, relocate_points, relocate_rescale, relocate_rows, relocate_weights, weighted_draws)
 from .camera_table import (Camera, CameraRigTable, CameraTable, Cameras, Label, MultiCameraTable, PoseTable, Projections,
                            RigPoseTable, camera_adjacency_matrix, camera_json, camera_scene_extents, camera_similarity,
                            check_indices, pose_adjacency, pose_matrices)
@@ -69,4 +70,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "TargetOverlap", "TrainConfig", "TrainerState", "TrainingException", "NaNParameterException",
            "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer",
            "resize_area", "LensCamera", "Undistortion", "optimal_pinhole", "undistort_map", "remap", "read_model",
-           "write_model", "COLMAPDataset", "export_colmap"]
+           "write_model", "COLMAPDataset", "export_colmap", "weighted_draws", "relocate_weights", "relocate_rescale",
+           "relocate_rows", "relocate_points", "grow_points", "growth_target"]

@@ -2,6 +2,8 @@
 ``mcmc_controller.py`` and ``densify_and_prune`` / ``log_histograms`` of ``point_state.py:59-110``) over this package's
 pieces: ``controller_math.PointState`` / ``take_n`` / ``find_split_prune_indexes``, the scene's ``split_and_prune`` and one
 native kernel for the MCMC controller's per-step position noise (csrc/controller.hip, maths in csrc/gsr_controller.h).
+Beyond the reference: ``MCMCConfig.relocate`` switches the MCMC controller's prune step to the relocation move of the
+MCMC paper -- ``relocate_points`` / ``grow_points`` over ``weighted_draws``, native too (csrc/relocate.hip).
 
 What differs from the reference's surface, because the packages behind it are not here: no hydra, beartype or tensordict.
 A schedule-valued field (``TargetConfig.densify_prune_interval``, ``MCMCConfig.noise_level``) is a number or a callable of
@@ -25,8 +27,10 @@ left out.
 """
 from __future__ import annotations
 
+import math
 from abc import ABCMeta, abstractmethod
 from dataclasses import dataclass, fields
+from fractions import Fraction
 from typing import Callable, Optional, Tuple, Union
 
 import torch
@@ -330,9 +334,159 @@ def mcmc_draws(num_points: int, seed: int, step: int, device="cuda") -> Tuple[to
   return words, normals
 
 
+# ----------------------------------------------------------------------------------------------------------- relocation
+# The relocation move of "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al., 2024), which the
+# reference's mcmc_controller.py does not have: csrc/relocate.hip, arithmetic in csrc/gsr_relocate.h, contracts in
+# include/gsplat_hip.h.  Every function enqueues on the current stream and waits for nothing, except where it says so.
+RELOCATE_DOMAIN, GROW_DOMAIN = 1, 2           # the noise step is domain 0 of the same (seed, step)
+_WHAT = "the MCMC relocation"
+
+
+@torch.no_grad()
+def relocate_weights(alpha_logit: torch.Tensor, alive: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """(N,) int32 draw weights: 0 where ``alive`` (bool, optional) is False, else ``max(1, floor(2^24 sigmoid(a)))`` with
+  the sigmoid in fp64."""
+  a = require("alpha_logit", alpha_logit, shape=[("N", 1), ("N",)], dtype=torch.float32, what=_WHAT)
+  n = int(a.shape[0])
+  if alive is not None:
+    require("alive", alive, shape=(n,), dtype=torch.bool, what=_WHAT)
+    on_one_device({"alpha_logit": a, "alive": alive})
+    alive = alive.contiguous()
+  with _lib.on_device(a.device) as stream:
+    weights = torch.empty(n, dtype=torch.int32, device=a.device)
+    _lib.call("gsr_relocate_weights", _ptr(a.detach().contiguous()), _ptr(alive), n, _ptr(weights), stream)
+  return weights
+
+
+@torch.no_grad()
+def weighted_draws(weights: torch.Tensor, n: int, seed: int, step: int, domain: int
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+  """``n`` draws over the rows of ``weights`` (N,) -- uint32 values, held as int32 or uint32 bit patterns; 0 cannot be
+  drawn -- with probability proportional to the weight: ``(sources (n,) int32, counts (N,) int32, total (1,) int64)``.
+  Draw ``k`` is a function of (weights, seed, step, domain, k) alone: Philox4x32-10 at the counter
+  (k, step, domain), ``t = floor(r S / 2^64)`` and the smallest row whose inclusive prefix sum exceeds ``t``; all
+  integers, no generator state.  A total of 0 gives sources of -1 and counts of 0."""
+  w = require("weights", weights, shape=("N",), what=_WHAT)
+  if w.dtype not in (torch.int32, torch.uint32):
+    raise ValueError(f"weights must be torch.int32 or torch.uint32, got {w.dtype}")
+  N, n, domain = int(w.shape[0]), int(n), int(domain)
+  if n < 0 or not 0 <= domain < 256:
+    raise ValueError(f"need n >= 0 and a domain in [0, 256), got {n} and {domain}")
+  seed, step = _u64("seed", seed), _u64("step", step)
+  with _lib.on_device(w.device) as stream:
+    sources = torch.empty(n, dtype=torch.int32, device=w.device)
+    counts = torch.empty(N, dtype=torch.int32, device=w.device)
+    total = torch.empty(1, dtype=torch.int64, device=w.device)
+    ws = _lib.workspace(_lib.load().gsr_weighted_draws_workspace_bytes(N), w.device)
+    _lib.call("gsr_weighted_draws", _ptr(w.contiguous()), N, n, seed, step, domain, _ptr(sources), _ptr(counts),
+              _ptr(total), _ptr(ws), ws.numel(), stream)
+  return sources, counts, total
+
+
+@torch.no_grad()
+def relocate_rescale(alpha_logit: torch.Tensor, log_scaling: torch.Tensor, counts: torch.Tensor, o_floor: float):
+  """The correction of Eq. 9, IN PLACE on ``alpha_logit`` (N, 1) or (N,) and ``log_scaling`` (N, 3), for every row with
+  ``counts`` (N,) int32 >= 1: the row and its ``counts`` copies, ``n = min(counts + 1, 51)`` Gaussians in all, get the
+  opacity ``1 - (1 - o)^(1/n)`` (clamped to [o_floor, 1 - 2^-24]) and their scales the factor ``o / D``; fp64 inside."""
+  a = require("alpha_logit", alpha_logit, shape=[("N", 1), ("N",)], dtype=torch.float32, what=_WHAT)
+  n = int(a.shape[0])
+  ls = require("log_scaling", log_scaling, shape=(n, 3), dtype=torch.float32, what=_WHAT)
+  c = require("counts", counts, shape=(n,), dtype=torch.int32, what=_WHAT)
+  on_one_device({"alpha_logit": a, "log_scaling": ls, "counts": c})
+  if not (a.is_contiguous() and ls.is_contiguous()):
+    raise ValueError("alpha_logit and log_scaling must be contiguous: they are updated in place")
+  if not 0.0 < float(o_floor) < 1.0:
+    raise ValueError(f"need 0 < o_floor < 1, got {o_floor}")
+  with _lib.on_device(a.device) as stream:
+    _lib.call("gsr_relocate_rescale", _ptr(a.detach()), _ptr(ls.detach()), _ptr(c.contiguous()), n, float(o_floor), stream)
+
+
+@torch.no_grad()
+def relocate_rows(columns, dst_rows: torch.Tensor, src_rows: torch.Tensor):
+  """One launch over ``columns`` = [(tensor (N, ...), zero)]: for every k, row ``dst_rows[k]`` of a column with
+  ``zero`` False takes row ``src_rows[k]``, and both rows of a column with ``zero`` True are zero-filled; IN PLACE.
+  The dst rows must be unique and disjoint from the src rows.  A k with an index outside [0, N) is skipped."""
+  dst = require("dst_rows", dst_rows, shape=("n",), dtype=torch.int32, what=_WHAT)
+  src = require("src_rows", src_rows, shape=(int(dst.shape[0]),), dtype=torch.int32, what=_WHAT)
+  if len(columns) > _lib.MAX_COLUMNS:
+    raise ValueError(f"at most {_lib.MAX_COLUMNS} columns per call")
+  if not columns:
+    return
+  N = int(columns[0][0].shape[0])
+  arr = (_lib.GsrRowColumnC * len(columns))()
+  for i, (t, zero) in enumerate(columns):
+    if not (t.is_cuda and t.element_size() == 4 and t.is_contiguous() and t.shape[0] == N and t.device == dst.device):
+      raise ValueError("columns must be contiguous CUDA tensors of 4-byte elements with the same number of rows, on the "
+                       "device of the row lists")
+    arr[i] = _lib.GsrRowColumnC(data=_ptr(t.detach()), width_dwords=max(t[0].numel(), 1) if N else 1, zero=int(bool(zero)))
+  with _lib.on_device(dst.device) as stream:
+    _lib.call("gsr_relocate_rows", _ptr(dst.contiguous()), _ptr(src.contiguous()), int(dst.shape[0]), N, arr, len(columns),
+              stream)
+
+
+def _optimizer_columns(points):
+  """The optimizer-state columns of a ``ParameterClass``."""
+  st = points._state
+  return [st["step"], st["vis_avg"]] + [v for g in st["groups"].values() for v in g.values()]
+
+
+@torch.no_grad()
+def relocate_points(points, state: PointState, dead_mask: torch.Tensor, o_floor: float, seed: int, step: int) -> int:
+  """Teleports the rows of ``dead_mask`` (N,) bool onto live rows drawn with probability proportional to opacity, IN
+  PLACE on the tensors and the optimizer state of ``points`` (a ``ParameterClass``) and on ``state``; returns the
+  number of dead rows.  The row count does not change.
+
+  weights (0 for a dead row) -> one draw per dead row at (seed, step, domain 1) -> the opacity / scale correction of
+  every drawn source for itself and its copies -> one launch that gives every dead row its source's NEW row in every
+  column and zero-fills the optimizer state of both.  The dead rows of ``state`` are zeroed, as children start from zero
+  in ``densify_and_prune``; the sources keep theirs.  One host wait: the dead count."""
+  from .densify import compact_rows
+  n = points.num_points
+  dead = require("dead_mask", dead_mask, shape=(n,), dtype=torch.bool, what=_WHAT)
+  dev = points.device
+  rows = torch.arange(n, dtype=torch.int32, device=dev)
+  dead_rows, = compact_rows(dead, [(rows, None)], n_tail=0)              # (the wait: the count sizes the list)
+  n_dead = int(dead_rows.shape[0])
+  if n_dead == 0:
+    return 0
+  weights = relocate_weights(points.alpha_logit, alive=~dead)
+  sources, counts, _ = weighted_draws(weights, n_dead, seed, step, RELOCATE_DOMAIN)
+  relocate_rescale(points.alpha_logit, points.log_scaling, counts, o_floor)
+  columns = [(t, False) for t in points.tensors.values()] + [(t, True) for t in _optimizer_columns(points)]
+  relocate_rows(columns, dead_rows, sources)
+  for _, v in _columns(state):
+    v.masked_fill_(dead, 0)
+  return n_dead
+
+
+@torch.no_grad()
+def grow_points(points, state: PointState, n_new: int, o_floor: float, seed: int, step: int):
+  """``n_new`` copies of rows drawn over ALL rows at (seed, step, domain 2), appended: ``(points, state)``, new objects
+  with N + n_new rows.  The sources are corrected in place first, so a copy equals its source's new row; the appended
+  rows get fresh optimizer state and zero ``PointState`` rows."""
+  n, n_new = points.num_points, int(n_new)
+  if n_new <= 0 or n == 0:
+    return points, state
+  sources, counts, _ = weighted_draws(relocate_weights(points.alpha_logit), n_new, seed, step, GROW_DOMAIN)
+  relocate_rescale(points.alpha_logit, points.log_scaling, counts, o_floor)
+  idx = sources.to(torch.int64)              # (every row is alive and weighs 1 or more: no source is -1)
+  keep = torch.ones(n, dtype=torch.bool, device=points.device)
+  grown = points.keep_and_append(keep, {k: t.detach()[idx] for k, t in points.tensors.items()})
+  return grown, PointState(**{k: torch.cat([v, v.new_zeros(n_new)]) for k, v in _columns(state)})
+
+
+def growth_target(num_points: int, target_points: int, grow_rate: float) -> int:
+  """``min(target_points, ceil((1 + grow_rate) N))``, never below N; the rate is read as the nearest fraction with a
+  denominator up to 10^6, so that 0.05 of 300 is 15 and not 15.000000000000002."""
+  n = int(num_points)
+  return max(n, min(int(target_points), n + math.ceil(Fraction(float(grow_rate)).limit_denominator(10 ** 6) * n)))
+
+
 @dataclass
 class MCMCConfig(ControllerConfig):
-  """mcmc_controller.py:24-50 without ``max_prune_rate`` (read nowhere there) and with ``seed``, the key of the noise."""
+  """mcmc_controller.py:24-50 without ``max_prune_rate`` (read nowhere there) and with ``seed``, the key of the noise.
+  ``relocate`` (beyond the reference) replaces the prune-and-split round by the paper's relocation move and a growth
+  of ``grow_rate`` per round towards ``target_points``."""
   opacity_threshold: float = 0.1
   prune_interval: int = 50
   min_views: int = 5
@@ -340,6 +494,8 @@ class MCMCConfig(ControllerConfig):
   min_split_px: float = 0.0
   noise_level: Schedule = 100.0
   seed: int = 0
+  relocate: bool = False
+  grow_rate: float = 0.05
 
   def make_controller(self, scene, target_points: int, progress: Progress, logger=None) -> "MCMCController":
     return MCMCController(self, scene, target_points, progress, logger)
@@ -354,7 +510,8 @@ class MCMCConfig(ControllerConfig):
 class MCMCController(Controller):
   """mcmc_controller.py:54-112.  Every ``prune_interval`` steps: prune the oversized and the nearly transparent points
   and split as many top-scored ones (never a pruned one: the count falls by the overlap the reference's unstable sort
-  may produce); the statistics are carried across the round, the children start from zero.  Every other step: the
+  may produce); the statistics are carried across the round, the children start from zero.  With ``config.relocate``
+  that step is ``relocate_round`` instead: nothing is deleted, the dead rows move onto live ones.  Every other step: the
   native noise step on ``scene.points.position`` in place -- the reference's own code perturbs a copy (a bool-mask
   index), so its noise never reaches the scene; see the module docstring."""
 
@@ -384,12 +541,31 @@ class MCMCController(Controller):
     return split_mask, prune_mask
 
   @torch.no_grad()
+  def relocate_round(self, progress: Progress):
+    """``MCMCConfig.relocate``: the dead rows -- oversized or below ``opacity_threshold`` -- are relocated onto live
+    ones, then the count grows to ``growth_target``.  Both moves draw at (``config.seed``, ``progress.step``), in their
+    own domains, so replicas with equal parameters make equal moves.  ``scene.points`` must be a ``ParameterClass``."""
+    c, scene = self.config, self.scene
+    opacity = torch.sigmoid(scene.points.alpha_logit.detach()).reshape(-1)
+    dead = (self.points.max_scale_px > c.max_scale_px) | (opacity < c.opacity_threshold)
+    n = scene.num_points
+    n_dead = relocate_points(scene.points, self.points, dead, c.opacity_threshold, c.seed, progress.step)
+    n_new = growth_target(n, self.target_points, c.grow_rate) - n
+    if n_new > 0:
+      scene.points, self.points = grow_points(scene.points, self.points, n_new, c.opacity_threshold, c.seed, progress.step)
+    self.num_points = scene.num_points
+    if self.logger is not None:
+      self.logger.log_values("relocate", dict(n=n, dead=n_dead, grown=max(n_new, 0)))
+
+  @torch.no_grad()
   def step(self, progress: Progress, log_details: bool = False, generator: Optional[torch.Generator] = None):
     """``generator`` (beyond the reference): passed on to ``scene.split_and_prune`` on a prune step."""
     c = self.config
     if log_details and self.logger is not None:
       log_histograms(self.points, self.logger, "step")
-    if progress.step % c.prune_interval == 0:
+    if progress.step % c.prune_interval == 0 and c.relocate:
+      self.relocate_round(progress)
+    elif progress.step % c.prune_interval == 0:
       split_mask, prune_mask = self.find_split_prune_masks()
       self.points = densify_and_prune(self.points, self.scene, split_mask, prune_mask, logger=self.logger,
                                       generator=generator)

@@ -27,20 +27,6 @@ __device__ __forceinline__ void load_row(const float* __restrict__ src, int64_t 
   for (int k = 0; k < W; ++k) v[k] = src[r * W + k];
 }
 
-// position of the n-th set bit of m, n < popcount(m)
-__device__ __forceinline__ int nth_set_bit(uint64_t m, int n) {
-  int pos = 0;
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) {
-    const int c = __popcll(m & ((1ull << w) - 1ull));
-    const bool skip = n >= c;
-    n -= skip ? c : 0;
-    m >>= skip ? w : 0;
-    pos += skip ? w : 0;
-  }
-  return pos;
-}
-
 __global__ __launch_bounds__(MN_BLOCK) void mcmc_noise_kernel(float* __restrict__ position,
                                                               const float* __restrict__ log_scaling,
                                                               const float* __restrict__ rotation,
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(MN_BLOCK) void mcmc_noise_kernel(float* __restrict_
     const int k = (j >= s1) + (j >= s2) + (j >= s3);
     const uint64_t m = k == 0 ? mask[0] : k == 1 ? mask[1] : k == 2 ? mask[2] : mask[3];
     const int first = k == 0 ? 0 : k == 1 ? s1 : k == 2 ? s2 : s3;
-    const int64_t r = wave_row0 + 64 * k + nth_set_bit(m, j - first);      // a live row: r < N
+    const int64_t r = wave_row0 + 64 * k + gsr_nth_set_bit(m, j - first);      // a live row: r < N
     const float level = gsr_mcmc_level(alpha_logit[r], opacity_threshold, margin, noise_level);   // the bits tested above
     float p[3], ls[3], q[4];
     load_row<3>(log_scaling, r, ls);

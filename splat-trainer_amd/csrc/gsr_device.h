@@ -63,6 +63,37 @@ __device__ __forceinline__ int gsr_mbcnt(uint64_t mask) {  // number of set bits
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
 
+// position of the n-th set bit of m, n < popcount(m)
+__device__ __forceinline__ int gsr_nth_set_bit(uint64_t m, int n) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const int c = __popcll(m & ((1ull << w) - 1ull));
+    const bool skip = n >= c;
+    n -= skip ? c : 0;
+    m >>= skip ? w : 0;
+    pos += skip ? w : 0;
+  }
+  return pos;
+}
+
+// inclusive prefix sum across the wave, and the wave's total in every lane, in uint64
+__device__ __forceinline__ uint64_t gsr_wave_scan_incl_u64(uint64_t v) {
+  const int lane = gsr_lane();
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t n = __shfl_up((unsigned long long)v, o, 64);
+    if (lane >= o) v += n;
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint64_t gsr_wave_sum_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, 64);
+  return v;
+}
+
 // Depth -> sortable u32 key.  The IEEE bit pattern of a positive float is monotone (sign bit set keeps negatives, which
 // the cull never lets through, below); `bias` = key of the near plane makes the keys of a frame start at 0, so that
 // they span only bits(far) - bits(near) (27 bits for 0.1 .. 100) and the radix sort needs fewer passes.  Depths outside

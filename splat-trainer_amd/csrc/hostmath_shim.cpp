@@ -20,6 +20,7 @@
 #include "gsr_histogram.h"
 #include "gsr_image.h"
 #include "gsr_undistort.h"
+#include "gsr_relocate.h"
 
 extern "C" {
 
@@ -550,6 +551,104 @@ void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotat
       gsr_mcmc_noise_row(position + 3 * i, log_scaling + 3 * i, rotation_xyzw + 4 * i, level, scale_eps, (uint64_t)i, seed,
                          step);
   }
+}
+
+}  // extern "C"
+
+// MCMC relocation (gsr_relocate.h): the device's arithmetic and its argument checks in plain loops.
+extern "C" {
+
+void hm_reloc_words(uint64_t k, uint64_t seed, uint64_t step, int32_t domain, uint32_t* out) {
+  gsr_reloc_words(k, seed, step, (uint32_t)domain, out);
+}
+
+int hm_weighted_draws(const uint32_t* weights, int64_t N, int64_t n, uint64_t seed, uint64_t step, int32_t domain,
+                      int32_t* sources_out, int32_t* counts_out, uint64_t* total_out, void* workspace,
+                      size_t workspace_bytes) {
+  const int rc = gsr_weighted_draws_check(weights, N, n, domain, sources_out, counts_out, total_out, workspace,
+                                          workspace_bytes);
+  if (rc < 0) return rc;
+  uint64_t* block_incl = (uint64_t*)workspace;
+  const int64_t blocks = (N + GSR_RELOC_BLOCK - 1) / GSR_RELOC_BLOCK;
+  uint64_t S = 0;
+  for (int64_t b = 0; b < blocks; ++b) {
+    for (int64_t i = b * GSR_RELOC_BLOCK; i < N && i < (b + 1) * GSR_RELOC_BLOCK; ++i) {
+      S += weights[i];
+      counts_out[i] = 0;
+    }
+    block_incl[b] = S;
+  }
+  *total_out = S;
+  for (int64_t k = 0; k < n; ++k) {
+    sources_out[k] = -1;
+    if (S == 0) continue;
+    const uint64_t t = gsr_reloc_target((uint64_t)k, seed, step, (uint32_t)domain, S);
+    int64_t lo = 0, hi = blocks - 1;                                  // block_incl[blocks - 1] = S > t
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (block_incl[mid] > t) hi = mid;
+      else lo = mid + 1;
+    }
+    uint64_t P = lo ? block_incl[lo - 1] : 0;
+    for (int64_t i = lo * GSR_RELOC_BLOCK; i < N; ++i) {
+      P += weights[i];
+      if (P > t) {
+        sources_out[k] = (int32_t)i;
+        counts_out[i] += 1;
+        break;
+      }
+    }
+  }
+  return GSR_OK;
+}
+
+int hm_relocate_weights(const float* alpha_logit, const uint8_t* alive, int64_t N, uint32_t* weights_out) {
+  int launch = 0;
+  const int rc = gsr_relocate_weights_check(alpha_logit, N, weights_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  for (int64_t i = 0; i < N; ++i) weights_out[i] = gsr_reloc_weight(alpha_logit[i], alive ? alive[i] != 0 : true);
+  return GSR_OK;
+}
+
+int hm_relocate_rescale(float* alpha_logit, float* log_scaling, const int32_t* counts, int64_t N, float o_floor) {
+  int launch = 0;
+  const int rc = gsr_relocate_rescale_check(alpha_logit, log_scaling, counts, N, o_floor, &launch);
+  if (rc < 0 || !launch) return rc;
+  for (int64_t r = 0; r < N; ++r) {
+    if (!(counts[r] > 0)) continue;
+    float a_new;
+    double log_coeff;
+    gsr_reloc_rescale(alpha_logit[r], counts[r], (double)o_floor, &a_new, &log_coeff);
+    alpha_logit[r] = a_new;
+    for (int j = 0; j < 3; ++j) log_scaling[3 * r + j] = (float)((double)log_scaling[3 * r + j] + log_coeff);
+  }
+  return GSR_OK;
+}
+
+void hm_reloc_rescale_rows(const float* alpha_logit, const int32_t* counts, int64_t n, float o_floor, float* a_out,
+                           double* log_coeff) {
+  for (int64_t i = 0; i < n; ++i) gsr_reloc_rescale(alpha_logit[i], counts[i], (double)o_floor, a_out + i, log_coeff + i);
+}
+
+int hm_relocate_rows(const int32_t* dst_rows, const int32_t* src_rows, int64_t n, int64_t N, const void* columns,
+                     int32_t n_columns) {
+  const GsrRowColumnC* cols = (const GsrRowColumnC*)columns;
+  int launch = 0;
+  const int rc = gsr_relocate_rows_check(dst_rows, src_rows, n, N, cols, n_columns, &launch);
+  if (rc < 0 || !launch) return rc;
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t dst = dst_rows[k], src = src_rows[k];
+    if (dst < 0 || dst >= N || src < 0 || src >= N) continue;
+    for (int c = 0; c < n_columns; ++c) {
+      uint32_t* data = (uint32_t*)cols[c].data;
+      const int64_t w = cols[c].width_dwords;
+      for (int64_t d = 0; d < w; ++d) {
+        if (cols[c].zero) data[dst * w + d] = data[src * w + d] = 0u;
+        else data[dst * w + d] = data[src * w + d];
+      }
+    }
+  }
+  return GSR_OK;
 }
 
 }  // extern "C"

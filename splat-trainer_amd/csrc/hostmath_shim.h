@@ -5,6 +5,7 @@
 #ifndef GSR_HOSTMATH_SHIM_H
 #define GSR_HOSTMATH_SHIM_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -102,6 +103,23 @@ void hm_mcmc_level(const float* alpha_logit, int64_t N, float opacity_threshold,
 void hm_mcmc_noise(float* position, const float* log_scaling, const float* rotation_xyzw, const float* alpha_logit,
                    const int16_t* points_in_view, int64_t N, int32_t min_views, float opacity_threshold, float margin,
                    float noise_level, float scale_eps, uint64_t seed, uint64_t step);
+
+/* ---- MCMC relocation (gsr_relocate.h): the device's arithmetic and argument checks in plain loops ---- */
+/* out [4]: the Philox words of draw k at (seed, step) in `domain` */
+void hm_reloc_words(uint64_t k, uint64_t seed, uint64_t step, int32_t domain, uint32_t* out);
+/* gsr_weighted_draws on host memory, with its checks and codes: a binary search over the block prefixes, then the rows of
+ * the block in order */
+int hm_weighted_draws(const uint32_t* weights, int64_t N, int64_t n, uint64_t seed, uint64_t step, int32_t domain,
+                      int32_t* sources_out, int32_t* counts_out, uint64_t* total_out, void* workspace,
+                      size_t workspace_bytes);
+int hm_relocate_weights(const float* alpha_logit, const uint8_t* alive, int64_t N, uint32_t* weights_out);
+int hm_relocate_rescale(float* alpha_logit, float* log_scaling, const int32_t* counts, int64_t N, float o_floor);
+/* the new logit and the fp64 log(coeff) of n source rows, counts >= 1 each */
+void hm_reloc_rescale_rows(const float* alpha_logit, const int32_t* counts, int64_t n, float o_floor, float* a_out,
+                           double* log_coeff);
+/* columns: n_columns GsrRowColumnC of include/gsplat_hip.h (16 bytes each: data, width_dwords, zero) */
+int hm_relocate_rows(const int32_t* dst_rows, const int32_t* src_rows, int64_t n, int64_t N, const void* columns,
+                     int32_t n_columns);
 
 /* ---- pose tables (gsr_camera_table.h): the device's order of operations ---- */
 /* q [A, 4], t [A, 3], idx [B]; the right table may be absent (all three NULL).  T [B, 4, 4].  Returns -1 when an index is
