@@ -5,7 +5,8 @@
 // outside the image) is staged in LDS once; the separable 11-tap Gaussian is applied as a horizontal pass into LDS
 // (5 moment images x 42 rows x 32 columns) and a vertical pass in registers, 4 outputs per work item, so every input
 // pixel is read from HBM once per tile and all 5 (forward) / 3 (backward) convolutions share the staging.
-// Forward reads 2 and writes 3 planes, backward reads 5 and writes 1.
+// Forward reads 2 and writes 3 planes, backward reads 5 and writes 1.  The forward's variances come from moments of
+// the tile shifted by its centre pixel (see ssim_fwd_kernel): near-constant tiles no longer cancel in float32.
 // The mean is reduced without atomics: per-block partial sums in a fixed order, then one block adds them in order.
 #include "gsr_device.h"
 #include "gsr_host.h"
@@ -25,6 +26,12 @@ struct Strides {
   int64_t sB, sC, sH, sW;
 };
 
+// clamp(v, lo, hi) as torch.clamp computes it: a NaN stays a NaN (fminf(fmaxf(v, lo), hi) would return lo for it and a
+// non-finite rendering would pass the trainer's guard as a finite loss).  lo = -inf, hi = +inf: no clamp.
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
 __device__ __forceinline__ float block_sum_256(float v, float* s_red) {
   v = gsr_wave_sum(v);                                   // fixed-order DPP tree
   const int wave = threadIdx.x >> 6;
@@ -41,7 +48,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
                                                        float C1, float C2, float inv_count, Gauss11 g,
                                                        float* __restrict__ block_sums, float* __restrict__ dm_dmu1,
                                                        float* __restrict__ dm_dm11, float* __restrict__ dm_dm12,
-                                                       float lo = -3.0e38f, float hi = 3.0e38f) {
+                                                       float lo = -INFINITY, float hi = INFINITY) {
   __shared__ float s_x[IN][IN + 1], s_y[IN][IN + 1];
   __shared__ float s_h[5][IN][TS + 1];
   __shared__ float s_red[4];
@@ -49,12 +56,20 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
   const int x0 = blockIdx.x * TS, y0 = blockIdx.y * TS;
   const float* p1 = img1 + b * st1.sB + c * st1.sC;
   const float* p2 = img2 + b * st2.sB + c * st2.sC;
+  // Shifted moments.  G*x^2 - (G*x)^2 cancels: on a near-constant tile float32 leaves 1e-7 of it against C2 = 9e-4, the
+  // same at every pixel, which the mean cannot average away.  So the tile is staged as x - c1, y - c2 (c: the tile's
+  // centre pixel, any constant is exact) and the variances are put together below from the shifted moments, where the
+  // cancelling part is c^2 smaller; the window mass outside the image (zero padding is not shift invariant) enters exactly.
+  const int cy = min(y0 + TS / 2, H - 1), cx = min(x0 + TS / 2, W - 1);
+  float c1 = clamp_keep_nan(p1[cy * st1.sH + cx * st1.sW], lo, hi), c2 = p2[cy * st2.sH + cx * st2.sW];
+  c1 = fabsf(c1) <= 3.0e38f ? c1 : 0.f;                 // a NaN / inf pixel stays one pixel's matter
+  c2 = fabsf(c2) <= 3.0e38f ? c2 : 0.f;
   for (int i = threadIdx.x; i < IN * IN; i += 256) {
     const int ly = i / IN, lx = i % IN;
     const int gy = y0 + ly - HALO, gx = x0 + lx - HALO;
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    s_x[ly][lx] = in ? fminf(fmaxf(p1[gy * st1.sH + gx * st1.sW], lo), hi) : 0.f;     // (img1 clamped at load: fused loss)
-    s_y[ly][lx] = in ? p2[gy * st2.sH + gx * st2.sW] : 0.f;
+    s_x[ly][lx] = in ? clamp_keep_nan(p1[gy * st1.sH + gx * st1.sW], lo, hi) - c1 : 0.f;     // (img1 clamped at load: fused loss)
+    s_y[ly][lx] = in ? p2[gy * st2.sH + gx * st2.sW] - c2 : 0.f;
   }
   __syncthreads();
   // horizontal pass: 42 rows x 8 groups of 4 columns
@@ -98,13 +113,23 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
       for (int k = 0; k < 11; ++k) acc[o][q] += g.w[k] * col[o + k];
   }
   float local = 0.f;
+  float out_x = 0.f;                                    // window mass left of column 0 and right of column W - 1
+#pragma unroll
+  for (int k = 0; k < 11; ++k) out_x += (gx + k - HALO < 0 || gx + k - HALO >= W) ? g.w[k] : 0.f;
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
     const int gy = y0 + tg * 4 + o;
-    const float mu1 = acc[o][0], mu2 = acc[o][1], m11 = acc[o][2], m22 = acc[o][3], m12 = acc[o][4];
+    float out_y = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) out_y += (gy + k - HALO < 0 || gy + k - HALO >= H) ? g.w[k] : 0.f;
+    const float mass = (1.f - out_x) * (1.f - out_y), rest = out_x + (1.f - out_x) * out_y;    // rest = 1 - mass, 0 inside
+    const float n1 = acc[o][0], n2 = acc[o][1];          // moments of the shifted tile
+    const float mu1 = n1 + c1 * mass, mu2 = n2 + c2 * mass;
+    const float s1 = (acc[o][2] - n1 * n1) + c1 * rest * (2.f * n1 + c1 * mass);
+    const float s2 = (acc[o][3] - n2 * n2) + c2 * rest * (2.f * n2 + c2 * mass);
+    const float s12 = (acc[o][4] - n1 * n2) + rest * (c2 * n1 + c1 * n2 + c1 * c2 * mass);
     const bool inside = gx < W && gy < H;
     const bool counted = inside && gx >= crop && gx < W - crop && gy >= crop && gy < H - crop;
-    const float s1 = m11 - mu1 * mu1, s2 = m22 - mu2 * mu2, s12 = m12 - mu1 * mu2;
     const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2;
     const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
     const float iB = 1.f / (B1 * B2);
@@ -142,7 +167,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ dm_dm11,
                                                        const float* __restrict__ dm_dm12,
                                                        const float* __restrict__ gscale_dev, float* __restrict__ dimg1,
-                                                       float lo = -3.0e38f, float hi = 3.0e38f) {
+                                                       float lo = -INFINITY, float hi = INFINITY) {
   __shared__ float s_in[3][IN][IN + 1];
   __shared__ float s_h[3][IN][TS + 1];
   const int plane = blockIdx.z, b = plane / C, c = plane % C;
@@ -197,7 +222,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
   for (int o = 0; o < 4; ++o) {
     const int gy = y0 + tg * 4 + o;
     if (gy >= H) continue;
-    const float x = fminf(fmaxf(img1[b * st1.sB + c * st1.sC + gy * st1.sH + gx * st1.sW], lo), hi);
+    const float x = clamp_keep_nan(img1[b * st1.sB + c * st1.sC + gy * st1.sH + gx * st1.sW], lo, hi);
     const float y = img2[b * st2.sB + c * st2.sC + gy * st2.sH + gx * st2.sW];
     dimg1[b * sto.sB + c * sto.sC + gy * sto.sH + gx * sto.sW] = gs * (acc[o][0] + 2.f * x * acc[o][1] + y * acc[o][2]);
   }
@@ -232,11 +257,11 @@ __global__ __launch_bounds__(PL_THREADS) void pixel_loss_fwd_kernel(const float*
       xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w; tv[0] = b.x; tv[1] = b.y; tv[2] = b.z; tv[3] = b.w;
     } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { xv[k] = i + k < n ? x[i + k] : 0.f; tv[k] = i + k < n ? t[i + k] : fminf(fmaxf(0.f, lo), hi); }
+      for (int k = 0; k < 4; ++k) { xv[k] = i + k < n ? x[i + k] : 0.f; tv[k] = i + k < n ? t[i + k] : clamp_keep_nan(0.f, lo, hi); }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float d = fminf(fmaxf(xv[k], lo), hi) - tv[k];
+      const float d = clamp_keep_nan(xv[k], lo, hi) - tv[k];
       acc += KIND == 0 ? d * d : fabsf(d);
     }
   }
@@ -266,7 +291,7 @@ __global__ __launch_bounds__(PL_THREADS) void pixel_loss_bwd_kernel(const float*
   const float gs = grad_scale[0] * inv_n;
   for (int64_t i = (int64_t)blockIdx.x * PL_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * PL_THREADS) {
     const float xv = x[i];
-    const float d = fminf(fmaxf(xv, lo), hi) - t[i];
+    const float d = clamp_keep_nan(xv, lo, hi) - t[i];
     const bool pass = xv >= lo && xv <= hi;                       // torch.clamp backward: inclusive on both ends
     const float g = KIND == 0 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
     dx[i] = pass ? gs * g : 0.f;
@@ -318,7 +343,7 @@ __global__ __launch_bounds__(256) void msloss_pyramid_kernel(const float* __rest
             const int y = by * 8 + 2 * j + dy, x = bx * 8 + 2 * i + dx;
             if (y < H && x < W) {
               const int64_t o = ((int64_t)y * W + x) * C + c;
-              const float xv = fminf(fmaxf(image[o], lo), hi), tv = target[o];
+              const float xv = clamp_keep_nan(image[o], lo, hi), tv = target[o];
               const float d = xv - tv;
               l1 += fabsf(d);
               mse += d * d;
@@ -566,7 +591,7 @@ int gsr_msloss_forward(const float* image, const float* target, int32_t H, int32
     const size_t plane = (size_t)h * w * C;
     ssim_fwd_kernel<true><<<grid, 256, 0, stream>>>(x, t, st, st, C, h, w, 5, 0.01f * 0.01f, 0.03f * 0.03f, inv_count, g,
                                                    reinterpret_cast<float*>(base + p.sums[l]), maps, maps + plane,
-                                                   maps + 2 * plane, l ? -3.0e38f : lo, l ? 3.0e38f : hi);
+                                                   maps + 2 * plane, l ? -INFINITY : lo, l ? INFINITY : hi);
     GSR_CHECK_LAUNCH();
     sm.ssim[l] = reinterpret_cast<const float*>(base + p.sums[l]);
     sm.ssim_n[l] = p.sums_n[l];
@@ -600,7 +625,7 @@ int gsr_msloss_backward(const float* image, const float* target, int32_t H, int3
     const size_t plane = (size_t)h * w * C;
     const dim3 grid((w + TS - 1) / TS, (h + TS - 1) / TS, C);
     ssim_bwd_kernel<<<grid, 256, 0, stream>>>(x, t, st, st, st, C, h, w, g, maps, maps + plane, maps + 2 * plane, nullptr,
-                                             l ? p.lv.dlev[l] : d_image, l ? -3.0e38f : lo, l ? 3.0e38f : hi);
+                                             l ? p.lv.dlev[l] : d_image, l ? -INFINITY : lo, l ? INFINITY : hi);
     GSR_CHECK_LAUNCH();
   }
   const int64_t n = (int64_t)H * W * C;

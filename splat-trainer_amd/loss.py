@@ -46,7 +46,11 @@ class _SSIMFn(torch.autograd.Function):
     if maps is None:
       raise _lib.GsplatHipError("fused_ssim(train=False) result cannot be back-propagated")
     B, Cc, H, W = x.shape
-    d = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device)
+    # the prediction's own layout, unless it overlaps itself (one image expanded over a batch): planes that share
+    # addresses would overwrite each other's gradient, so that case gets a dense one and autograd sums it
+    dense = torch._debug_has_internal_overlap(x) != 0     # 0: dense or a permutation of it; else overlapping or unknown
+    d = (torch.empty(x.shape, dtype=torch.float32, device=x.device) if dense else
+         torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=x.device))
     _lib.call("gsr_ssim_backward", _ptr(x), _ptr(y), _strides(x), _strides(y), _strides(d), B, Cc, H, W, _ptr(maps[0]),
               _ptr(maps[1]), _ptr(maps[2]), _ptr(f32(g)), _ptr(d), _stream())                   # (g: one scalar)
     return d.to(ctx.in_dtype), None, None, None
@@ -69,8 +73,8 @@ def fused_ssim(img1: torch.Tensor, img2: torch.Tensor, padding: str = "same", tr
 class _PixelLossFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, image, target, kind, lo, hi):
-    x = f32(image)
-    t = f32(target if target.shape == x.shape else target.detach().to(torch.float32).expand_as(x))
+    x = f32(image, align16=True)                   # the kernel moves four floats at a time
+    t = f32(target if target.shape == x.shape else target.detach().to(torch.float32).expand_as(x), align16=True)
     n = x.numel()
     out = torch.empty(1, dtype=torch.float32, device=x.device)
     ws = _lib.workspace(_lib.load().gsr_pixel_loss_workspace_bytes(n), x.device)
@@ -91,7 +95,7 @@ class _PixelLossFn(torch.autograd.Function):
 def _pixel_loss(image, target, kind, clamp):
   if not (image.is_cuda and target.is_cuda):
     raise _lib.GsplatHipError("the fused pixel losses run only on a HIP device; there is no CPU fallback")
-  lo, hi = (float(clamp[0]), float(clamp[1])) if clamp is not None else (-3.0e38, 3.0e38)
+  lo, hi = (float(clamp[0]), float(clamp[1])) if clamp is not None else (-float("inf"), float("inf"))
   return _PixelLossFn.apply(image, target, kind, lo, hi)
 
 

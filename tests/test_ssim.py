@@ -40,6 +40,14 @@ def test_oracle_matches_definition_and_properties():
   assert abs(g.sum().item() - 1) < 1e-15 and g.argmax().item() == 5
   xg = x.clone().requires_grad_(True)
   assert torch.autograd.gradcheck(lambda t: ssim_oracle.fused_ssim(t, y, "valid"), (xg,), eps=1e-6, atol=1e-7)
+  # the explicit per-pixel terms (ssim_terms: what tests/loss_contract.py compares against) are autograd's
+  for padding, crop in (("same", 0), ("valid", 5)):
+    for form in ("conv2d", "separable"):
+      xa = x.clone().requires_grad_(True)
+      ssim_oracle.fused_ssim(xa, y, padding).backward()
+      terms = ssim_oracle.ssim_terms(x, y, crop, form=form)
+      assert (terms["grad"] - xa.grad).abs().max().item() < 1e-12
+      assert (terms["map"] - m).abs().max().item() < 1e-12 and (terms["scale"] >= terms["grad"].abs() * (1 - 1e-12)).all()
 
 
 def test_fused_ssim_refuses_cpu():
