@@ -9,7 +9,9 @@
   c2     one-call c2 fwd+bwd steps (render_gaussians(use_sh=True) + clamped MSE + backward) without and with the corrector
          (correct + corrector.step), alternating in one process
 
-Device-event timing, warm-up first, median of --reps.  ``--only``: one variant alone, for a
+Device-event timing, warm-up first, median of --reps (tools/timing.py's loop: --warmup interleaved rounds, one call per
+window, the forms mirrored on odd repetitions, a fresh event pair per window, the mean-of-middles median).
+``--only``: one variant alone, for a
 `rocprofv3 --kernel-trace --stats -- python tools/bilagrid_bench.py --parts slice --only native --reps 5` run.
 """
 from __future__ import annotations
@@ -17,7 +19,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,24 +30,12 @@ import torch.nn.functional as F  # noqa: E402
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import synthetic  # noqa: E402
 from splat_trainer_amd.bilateral import BilateralCorrectorConfig  # noqa: E402
+from timing import mid_median, repetitions  # noqa: E402
 
 
 def timed(fns: dict, reps: int, warmup: int) -> dict:
-  names = list(fns)
-  for _ in range(warmup):
-    for n in names:
-      fns[n]()
-  torch.cuda.synchronize()
-  times = {n: [] for n in names}
-  for rep in range(reps):
-    for n in (names if rep % 2 == 0 else list(reversed(names))):
-      a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      a.record()
-      fns[n]()
-      b.record()
-      b.synchronize()
-      times[n].append(a.elapsed_time(b))
-  return {n: dict(median_ms=statistics.median(t), min_ms=min(t)) for n, t in times.items()}
+  times = repetitions(fns, reps, warmup, order="mirrored", fresh_events=True)
+  return {n: dict(median_ms=mid_median(t), min_ms=min(t)) for n, t in times.items()}
 
 
 def torch_slice(grids, k, image):

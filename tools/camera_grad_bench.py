@@ -4,7 +4,8 @@ c3 with and without T_camera_world / projection requiring grad, in the same proc
     python tools/camera_grad_bench.py [--workloads c2,c3] [--reps 30] [--warmup 5] [--only base|camera]
 
 Device-event timing of whole steps, warm-up first, then the two variants alternate (order flipped every repetition);
-prints the median ms per step of each and the difference.  ``--only``: one variant alone, for a
+prints the median ms per step of each and the difference (tools/timing.py's loop: --warmup interleaved rounds, one call
+per window, mirrored order, a fresh event pair per window, the mean-of-middles median).  ``--only``: one variant alone, for a
 `rocprofv3 --kernel-trace --stats -- python tools/camera_grad_bench.py --only camera --reps 5` run.
 """
 from __future__ import annotations
@@ -12,7 +13,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,6 +22,7 @@ import torch  # noqa: E402
 
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import synthetic  # noqa: E402
+from timing import mid_median, repetitions  # noqa: E402
 
 SCENES = {"c2": lambda: synthetic.scene_a(500_000, 1920, 1080, sh_degree=3, seed=0),
           "c3": lambda: (lambda g, cams: (g, cams[0]))(*synthetic.scene_b(3_000_000, 1920, 1080, sh_degree=3, seed=1))}
@@ -44,20 +45,8 @@ def measure(name: str, reps: int, warmup: int, only=None) -> dict:
     for p in params + [Tg, pg]:
       p.grad = None
 
-  for _ in range(warmup):
-    for v in variants:
-      step(v)
-  torch.cuda.synchronize()
-  times = {v: [] for v in variants}
-  for rep in range(reps):
-    for v in (variants if rep % 2 == 0 else list(reversed(variants))):
-      a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      a.record()
-      step(v)
-      b.record()
-      b.synchronize()
-      times[v].append(a.elapsed_time(b))
-  out = {v: dict(median_ms=statistics.median(t), min_ms=min(t), max_ms=max(t)) for v, t in times.items()}
+  times = repetitions([(v, lambda v=v: step(v)) for v in variants], reps, warmup, order="mirrored", fresh_events=True)
+  out = {v: dict(median_ms=mid_median(t), min_ms=min(t), max_ms=max(t)) for v, t in times.items()}
   if not only:
     out["camera_minus_base_ms"] = out["camera"]["median_ms"] - out["base"]["median_ms"]
     out["overhead_pct"] = 100.0 * out["camera_minus_base_ms"] / out["base"]["median_ms"]

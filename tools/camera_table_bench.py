@@ -12,6 +12,9 @@ wall_us     host clock around one forward + backward that ends in a device synch
 device_us   device events around CALLS forward + backward calls enqueued back to back, divided by CALLS.  The work is
             launch-bound, so this is the rate at which the host can feed the queue, not kernel time.
 
+The loop is tools/timing.py's: 50 warm-up calls per form, then REPS repetitions of one call on the host clock, then 7
+repetitions of CALLS calls on a fresh event pair per window, without a second warm-up; fixed order, lower median.
+
 The kernels' own times are a rocprofv3 --kernel-trace run's business; the trace of this tool under it lists
 pose_forward_kernel and pose_backward_kernel.
 """
@@ -21,7 +24,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
 import torch.nn.functional as F
@@ -29,6 +31,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
+from timing import HostClock, repetitions  # noqa: E402
 
 CALLS = 200
 REPS = 300
@@ -81,31 +84,12 @@ def main():
     for a, b in zip(native(), reference()):
       assert torch.allclose(a, b, rtol=1e-3, atol=1e-4), "the two forms disagree"
     forms = (("native", native), ("torch", reference))
-    for _, fn in forms:
-      for _ in range(50):
-        fn()
-    torch.cuda.synchronize()
-    wall = {name: [] for name, _ in forms}
-    for _ in range(REPS):
-      for name, fn in forms:
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        wall[name].append((time.perf_counter() - t0) * 1e6)
-    device = {name: [] for name, _ in forms}
-    for _ in range(7):
-      for name, fn in forms:
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(CALLS):
-          fn()
-        end.record()
-        end.synchronize()
-        device[name].append(start.elapsed_time(end) * 1e3 / CALLS)
+    wall = repetitions(forms, REPS, warmup=50, warmup_form="per_form", clock=HostClock())
+    device = repetitions(forms, 7, warmup=0, calls=CALLS, fresh_events=True)
     r = dict(case=f"rig forward+backward B={B}")
     for name, _ in forms:
-      r[f"{name}_wall_us"] = stats(wall[name])
-      r[f"{name}_device_us"] = stats(device[name])
+      r[f"{name}_wall_us"] = stats([t * 1e3 for t in wall[name]])
+      r[f"{name}_device_us"] = stats([t * 1e3 for t in device[name]])
     r["wall_speedup"] = round(r["torch_wall_us"]["median"] / r["native_wall_us"]["median"], 2)
     r["native_no_slower"] = r["native_wall_us"]["median"] <= r["torch_wall_us"]["median"]
     rows.append(r)

@@ -1,7 +1,8 @@
 """Times the neural colour model (splat_trainer_amd.ColorModel, csrc/color_model.hip) with device events after warm-up,
 next to the reference's path today (the torch modules under fp16 autocast, tests/color_model_oracle.py's restatement), in
 the shipped configuration (scene/mlp.yaml: 16 point features, 32 GLO features, H 32, L 1, S 5), and reports bytes,
-FLOPs and the share of the chip's peaks.
+FLOPs and the share of the chip's peaks.  The loop is tools/timing.py's: each form alone, 3 warm-up calls, --reps
+repetitions of one call, one reused event pair, lower median, in microseconds.
 
     python tools/color_model_bench.py [--rows 500000 3000000] [--json out.json]
 
@@ -25,6 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import splat_trainer_amd as sta  # noqa: E402
 import color_model_oracle as cmo  # noqa: E402
+from timing import lower_median, repetitions  # noqa: E402
 
 HBM = 6.3e12
 MFMA_F16 = 2.5e15
@@ -32,19 +34,7 @@ P, G, H, L, S = 16, 32, 32, 1, 5
 
 
 def timed(fn, reps, warmup=3):
-  for _ in range(warmup):
-    fn()
-  torch.cuda.synchronize()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  ts = []
-  for _ in range(reps):
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    ts.append(a.elapsed_time(b) * 1e3)
-  ts.sort()
-  return ts[len(ts) // 2]
+  return lower_median(repetitions({"fn": fn}, reps, warmup)["fn"]) * 1e3
 
 
 def main():

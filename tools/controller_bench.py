@@ -1,7 +1,8 @@
 """Times one noise step of the MCMC controller (splat_trainer_amd.controller.mcmc_noise, csrc/controller.hip) against the
 torch form of the reference's mcmc_controller.py:93-100 written out below and made to hit the scene (the reference's own
 lines perturb a copy), on the same GPU in the same process: the two are alternated repetition by repetition after a
-warm-up, timed with device events, and reported as median and [min, max] (tools/visibility_bench.py's harness).
+warm-up, timed with device events, and reported as median and [min, max] (tools/timing.py's loop: 2 interleaved warm-up
+rounds, 9 repetitions, one call per window, fixed order, one reused event pair, lower median).
 
     python tools/controller_bench.py [--quick] [--json out.json]
 
@@ -10,13 +11,15 @@ The torch form is eager: a bool-mask gather of every column of the point table (
 scale) -- the reference compiles that one function with torch.compile, here it is its eager ops --, a batched mat-vec and
 the masked write back.  Two opacity mixes: every point nearly transparent (alpha_logit -4: every eligible row is
 perturbed) and 5 % nearly transparent (the rest at +3: an opaque row costs the kernel its view count and its logit).
-The kernel alone is timed through the C ABI, twenty launches between two events.  It runs no reference code.
+The kernel alone is timed through the C ABI, twenty launches between two events (1 warm-up launch, 5 windows, a fresh
+event pair per window, every launch at the next step number).  It runs no reference code.
 
 A native call counts as faster only when its slowest repetition beats torch's fastest (``clear``).
 """
 from __future__ import annotations
 
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -26,10 +29,9 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib  # noqa: E402
-from visibility_bench import alternated, row  # noqa: E402
+from timing import comparison_row, lower_median, repetitions, spread  # noqa: E402
 
 MIN_VIEWS, THRESHOLD, NOISE, MARGIN, EPS = 5, 0.1, 1e-3, 16.0, 1e-4
 
@@ -59,22 +61,12 @@ def torch_noise(table, views):
 def kernel_alone(table, views, launches=20):
   lib, n, stream = _lib.load(), views.shape[0], _lib.current_stream_ptr()
   p = lambda t: t.data_ptr()
-  fn = lambda step: _lib.check(lib.gsr_mcmc_noise(p(table["position"]), p(table["log_scaling"]), p(table["rotation"]),
-                                                  p(table["alpha_logit"]), p(views), n, MIN_VIEWS, THRESHOLD, MARGIN, NOISE,
-                                                  EPS, 0, step, stream), "gsr_mcmc_noise")
-  fn(0)
-  torch.cuda.synchronize()
-  times = []
-  for rep in range(5):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for k in range(launches):
-      fn(1 + rep * launches + k)
-    end.record()
-    end.synchronize()
-    times.append(start.elapsed_time(end) / launches)
-  times.sort()
-  return [round(t, 4) for t in (times[len(times) // 2], times[0], times[-1])]
+  steps = itertools.count()                                   # the warm-up launch is step 0, the timed ones follow on
+  fn = lambda: _lib.check(lib.gsr_mcmc_noise(p(table["position"]), p(table["log_scaling"]), p(table["rotation"]),
+                                             p(table["alpha_logit"]), p(views), n, MIN_VIEWS, THRESHOLD, MARGIN, NOISE,
+                                             EPS, 0, next(steps), stream), "gsr_mcmc_noise")
+  times = repetitions({"kernel": fn}, 5, warmup=1, calls=launches, fresh_events=True)["kernel"]
+  return [round(t, 4) for t in (lower_median(times), *spread(times))]
 
 
 def main():
@@ -100,8 +92,8 @@ def main():
         sta.mcmc_noise(table["position"], table["log_scaling"], table["rotation"], table["alpha_logit"], views,
                        min_views=MIN_VIEWS, opacity_threshold=THRESHOLD, noise_level=NOISE, seed=0, step=step[0])
 
-      a, b = alternated(native, lambda: torch_noise(table, views), reps=9)
-      r = row(f"noise step N={n} {mix}", a, b)
+      ms = repetitions(dict(native=native, torch=lambda: torch_noise(table, views)), 9, warmup=2)
+      r = comparison_row(f"noise step N={n} {mix}", ms["native"], ms["torch"])
       r["kernel_alone_ms"] = kernel_alone(table, views)
       live = int(((views > MIN_VIEWS) & (table["alpha_logit"].squeeze(1) < 0)).sum())
       r["perturbed_rows"] = live

@@ -5,7 +5,9 @@
 resize        ``gsr_image_resize_area_u8`` alone on B = 8 images of 4032 x 3024 x 3 (293 MB: past the 256 MiB Infinity
               Cache) to scale 0.5, scale 0.25 and ``resize_longest=1600``, beside the torch form on the same GPU: uint8
               -> float, ``F.interpolate(mode="area")``, round, -> uint8.  Device events around CALLS calls enqueued back
-              to back, the two forms alternated, median and [min, max] over the repetitions.  ``GBps`` is (bytes read +
+              to back, the two forms alternated, median and [min, max] over the repetitions (tools/timing.py's loop: 3
+              warm-up calls per form, REPS repetitions of CALLS calls per window, fixed order, a fresh event pair per
+              window, lower median).  ``GBps`` is (bytes read +
               bytes written) of the uint8 tensors over that time -- for the torch form too, so it is the rate at which it
               does the same job, not its own traffic -- and ``hbm_share`` is that over the 6.29 TB/s a float4 copy
               reaches on this GPU.  ``differing_bytes`` counts where the float form is not the exact mean rounded half up.
@@ -32,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import colmap, colmap_io  # noqa: E402
+from timing import repetitions  # noqa: E402
 
 W, H, B = 4032, 3024, 8
 HBM_COPY_TBPS = 6.29
@@ -57,20 +60,7 @@ def bench_resize():
                           ("resize_longest 1600", (round(H * s), round(W * s)))):
     forms = (("native", lambda: sta.resize_area(src, (hd, wd))), ("torch", lambda: torch_area(src, (hd, wd))))
     differing = int((forms[0][1]() != forms[1][1]()).sum())
-    for _, fn in forms:
-      for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ms = {name: [] for name, _ in forms}
-    for _ in range(REPS):
-      for name, fn in forms:
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(CALLS):
-          fn()
-        end.record()
-        end.synchronize()
-        ms[name].append(start.elapsed_time(end) / CALLS)
+    ms = repetitions(forms, REPS, warmup=3, warmup_form="per_form", calls=CALLS, fresh_events=True)
     moved = B * 3 * (H * W + hd * wd)
     r = dict(case=f"resize {B} x {W}x{H}x3 -> {wd}x{hd} ({label})", bytes_read_plus_written=moved, differing_bytes=differing,
              differing_share=round(differing / (B * 3 * hd * wd), 6))

@@ -4,21 +4,21 @@ torch form the reference runs (trainer/evaluation.py, util/colors.py), written o
     python tools/eval_bench.py [--height 1080 --width 1920 --repeats 5]
 
 Each figure is the median over ``--repeats`` images of the wall time from the call to the values being on the host (the
-metrics are read back, the corrected image is synchronised), after one warm-up image.
+metrics are read back, the corrected image is synchronised), after one warm-up image (tools/timing.py's loop: each form
+alone, 1 warm-up call, --repeats repetitions of one call, host clock, the mean-of-middles median).
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import splat_trainer_amd as sta  # noqa: E402
+from timing import HostClock, mid_median, repetitions  # noqa: E402
 
 
 def torch_metrics(image, source):
@@ -48,15 +48,7 @@ def torch_fit_colors(img, ref, num_iters=5, eps=0.5 / 255):
 
 
 def timed(fn, repeats):
-  fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(repeats):
-    t0 = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    times.append((time.perf_counter() - t0) * 1e3)
-  return statistics.median(times)
+  return mid_median(repetitions({"fn": fn}, repeats, warmup=1, clock=HostClock())["fn"])
 
 
 def main():

@@ -1,6 +1,8 @@
 """Times the 3-D smoothing filter's kernels (splat_trainer_amd.filter3d) against the torch form a user would write, on
 the same GPU in the same process: the two are alternated repetition by repetition after a warm-up, timed with device
-events, and reported as median and [min, max] over the repetitions (tools/visibility_bench.py's harness).
+events, and reported as median and [min, max] over the repetitions (tools/timing.py's loop: 2 interleaved warm-up
+rounds, 5 to 9 repetitions, one call per window, fixed order, one reused event pair, lower median; the kernels alone:
+1 warm-up call, 5 windows of twenty launches, a fresh event pair per window).
 
     python tools/filter3d_bench.py [--quick] [--json out.json]
 
@@ -29,7 +31,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib, visibility as vis  # noqa: E402
-from visibility_bench import alternated, ring, row  # noqa: E402
+from timing import comparison_row, lower_median, repetitions, spread  # noqa: E402
+from visibility_bench import ring, row  # noqa: E402  (a scene and the issue-bound arithmetic of a row; no timing)
 
 RATE_OPS = 26
 STRENGTH = 0.2
@@ -68,20 +71,9 @@ def kernels_alone(ls, a, rate, g_ls, g_a, launches=20):
                                                           p(out_a), stream), "gsr_filter3d_backward")
   out = {}
   for name, fn in (("forward_kernel_ms", forward), ("backward_kernel_ms", backward)):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(5):
-      start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      start.record()
-      for _ in range(launches):
-        fn()
-      end.record()
-      end.synchronize()
-      times.append(start.elapsed_time(end) / launches)
-    times.sort()
-    out[name] = round(times[2], 4)
-    out[name.replace("_ms", "_range")] = [round(times[0], 4), round(times[-1], 4)]
+    times = repetitions({name: fn}, 5, warmup=1, calls=launches, fresh_events=True)[name]
+    out[name] = round(lower_median(times), 4)
+    out[name.replace("_ms", "_range")] = [round(t, 4) for t in spread(times)]
   return out
 
 
@@ -105,13 +97,13 @@ def main():
       focal = cams.intrinsics[:, :2].max(dim=1).values.tolist()
       native = lambda: sta.sampling_rate(cams, points, margin=margin, unseen="zero")
       reps = 7 if V <= 64 else 5
-      t_native, t_torch = alternated(native, lambda: torch_rate(m, sizes, ranges, focal, points, margin), reps=reps)
-      r = row(f"sampling_rate N={N} V={V}", t_native, t_torch, N * V, RATE_OPS)
-      t_rate, t_frustum = alternated(native, lambda: vis.frustum_counts(cams, points), reps=9)
-      med = lambda ts: ts[len(ts) // 2]
-      r.update(beside_frustum_ms=round(med(t_rate), 4), beside_frustum_range=[round(t_rate[0], 4), round(t_rate[-1], 4)],
-               frustum_ms=round(med(t_frustum), 4), frustum_range=[round(t_frustum[0], 4), round(t_frustum[-1], 4)],
-               rate_over_frustum=round(med(t_rate) / med(t_frustum), 2))
+      ms = repetitions(dict(native=native, torch=lambda: torch_rate(m, sizes, ranges, focal, points, margin)), reps, warmup=2)
+      r = row(f"sampling_rate N={N} V={V}", ms["native"], ms["torch"], N * V, RATE_OPS)
+      ms = repetitions(dict(rate=native, frustum=lambda: vis.frustum_counts(cams, points)), 9, warmup=2)
+      med, r4 = lower_median, lambda ts: [round(t, 4) for t in spread(ts)]
+      r.update(beside_frustum_ms=round(med(ms["rate"]), 4), beside_frustum_range=r4(ms["rate"]),
+               frustum_ms=round(med(ms["frustum"]), 4), frustum_range=r4(ms["frustum"]),
+               rate_over_frustum=round(med(ms["rate"]) / med(ms["frustum"]), 2))
       rows.append(r)
   for N in sizes_n:
     ls = (-3 + torch.randn(N, 3, generator=g)).cuda().requires_grad_(True)
@@ -128,8 +120,8 @@ def main():
     def reference():
       return torch.autograd.grad(list(torch_smooth(ls, a, rate, STRENGTH)), [ls, a], [g_ls, g_a])
 
-    t_native, t_torch = alternated(native, reference, reps=9)
-    r = row(f"filter forward+backward N={N}", t_native, t_torch)
+    ms = repetitions(dict(native=native, torch=reference), 9, warmup=2)
+    r = comparison_row(f"filter forward+backward N={N}", ms["native"], ms["torch"])
     r.update(kernels_alone(ls.detach(), a.detach(), rate, g_ls, g_a))
     rows.append(r)
   for r in rows:

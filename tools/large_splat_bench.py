@@ -1,6 +1,7 @@
 """What splats that have grown large cost the binning and reduction kernels: the c2 frame (500k splats, 1080p, SH3) with
 G of its splats scaled up to fill most of the frame (x60; faint), kernel times from rocprofv3-free HIP events of the whole
-step plus K6 / K7.  Run under rocprofv3 --kernel-trace --stats for the per-kernel table.
+step plus K6 / K7 (tools/timing.py's single window: 5 warm-up steps, then 10 steps between one event pair with the
+kernel timer on, mean per step).  Run under rocprofv3 --kernel-trace --stats for the per-kernel table.
     python tools/large_splat_bench.py [G ...]"""
 import os
 import sys
@@ -11,6 +12,7 @@ import torch
 
 import splat_trainer_amd as sta
 from splat_trainer_amd import renderer, synthetic
+from timing import repetitions, single_window
 
 counts = [int(a) for a in sys.argv[1:]] or [0, 8, 64, 512]
 cfg = sta.RasterConfig(compute_visibility=True, compute_point_heuristic=True)
@@ -27,25 +29,18 @@ for G in counts:
   scene = sta.Gaussians3D(position=params[0], log_scaling=params[1], rotation=params[2], alpha_logit=params[3], feature=params[4])
 
   def step():
+    global r
     for p in params:
       p.grad = None
     with torch.enable_grad():
       r = sta.render_gaussians(scene, cam, cfg, use_sh=True)
       ((r.image.clamp(0, 1) - 0.5) ** 2).mean().backward()
-    return r
 
-  for _ in range(5):
-    r = step()
-  torch.cuda.synchronize()
+  repetitions({"step": step}, 0, warmup=5)                   # the warm-up alone: the kernel timer goes on after it
   timer = renderer.KernelTimer()
   renderer.KERNEL_TIMER = timer
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for _ in range(10):
-    r = step()
-  e1.record()
-  torch.cuda.synchronize()
+  step_us = single_window(step, 10, warmup=0) * 1e3
   renderer.KERNEL_TIMER = None
   ks = timer.summary()
-  print(f"{G:5d} large splats: O {r.num_overlaps:9d}  step {e0.elapsed_time(e1) / 10 * 1e3:7.0f} us  K6 {ks['composite_forward'][1] * 1e3:6.1f}  "
-        f"K7 {ks['composite_backward'][1] * 1e3:6.1f}  rest {e0.elapsed_time(e1) / 10 * 1e3 - (ks['composite_forward'][1] + ks['composite_backward'][1]) * 1e3:7.0f} us", flush=True)
+  print(f"{G:5d} large splats: O {r.num_overlaps:9d}  step {step_us:7.0f} us  K6 {ks['composite_forward'][1] * 1e3:6.1f}  "
+        f"K7 {ks['composite_backward'][1] * 1e3:6.1f}  rest {step_us - (ks['composite_forward'][1] + ks['composite_backward'][1]) * 1e3:7.0f} us", flush=True)

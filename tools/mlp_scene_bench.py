@@ -2,6 +2,8 @@
 ``MLPScene`` training step at the size of workload c2 (scene A, 500 000 points, 1920 x 1080), next to the torch form a
 user wrote before (tests/test_gpu_dropin_flow.py:38-46 through ``points.visible``).  HIP-event medians after warm-up,
 the two forms alternated in the same process; host synchronisations per call counted with torch's sync debug mode.
+The loop is tools/timing.py's: 3 interleaved warm-up rounds (2 for the whole step), --reps repetitions of one call, fixed
+order, one reused event pair, lower median and minimum in microseconds.
 
     python tools/mlp_scene_bench.py [--points 500000] [--reps 30] [--parts reg post step]
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/mlp_scene_bench.py --trace native --calls 40
@@ -27,6 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import reg, synthetic  # noqa: E402
+from timing import lower_median, repetitions  # noqa: E402
 
 WEIGHTS = dict(scale=0.01, opacity=1.0, aspect=1e-4, specular=1e-5)          # config/scene/mlp.yaml:16-20 at t = 0
 PARAMETERS = dict(position=dict(lr=0.3, type="local_vector"), log_scaling=dict(lr=0.08),
@@ -52,24 +55,7 @@ def torch_reg(points, log_scaling, weights=WEIGHTS):
 
 def timed_pair(fns: dict, reps: int, warmup: int = 3) -> dict:
   """Median us per call of each function, the functions alternated call by call."""
-  for _ in range(warmup):
-    for fn in fns.values():
-      fn()
-  torch.cuda.synchronize()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  ts = {k: [] for k in fns}
-  for _ in range(reps):
-    for k, fn in fns.items():
-      a.record()
-      fn()
-      b.record()
-      b.synchronize()
-      ts[k].append(a.elapsed_time(b) * 1e3)
-  out = {}
-  for k, v in ts.items():
-    v.sort()
-    out[k] = (v[len(v) // 2], v[0])
-  return out
+  return {k: (lower_median(v) * 1e3, min(v) * 1e3) for k, v in repetitions(fns, reps, warmup).items()}
 
 
 def count_syncs(fn) -> int:

@@ -1,6 +1,7 @@
 """Times the neighbour-search kernels (splat_trainer_amd.neighbours) with device events after warm-up, on seeded clouds,
 next to a chunked torch formulation on the same GPU, and reports pairs per second and the share of the fp32 VALU issue
-bound.
+bound.  The loop is tools/timing.py's: each form alone, 2 warm-up calls (1 for the long ones), 1 to 10 repetitions of one
+call, one reused event pair, lower median.
 
     python tools/neighbours_bench.py [--quick] [--json out.json]
 
@@ -21,6 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
+from timing import lower_median, repetitions  # noqa: E402
 
 ISSUE_BOUND = 256 * 4 * 32 * 2.4e9
 OPS = {"knn": 7, "assign": 10}
@@ -32,19 +34,7 @@ def cloud(n, seed):
 
 
 def timed(fn, reps, warmup=2):
-  for _ in range(warmup):
-    fn()
-  torch.cuda.synchronize()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  ts = []
-  for _ in range(reps):
-    a.record()
-    fn()
-    b.record()
-    b.synchronize()
-    ts.append(a.elapsed_time(b))
-  ts.sort()
-  return ts[len(ts) // 2]
+  return lower_median(repetitions({"fn": fn}, reps, warmup)["fn"])
 
 
 def torch_assign(x, c, chunk=1 << 18):

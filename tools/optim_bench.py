@@ -1,9 +1,11 @@
-"""Timing of the fused sparse optimizer step (csrc/optim.hip) at c2 / c3 sizes, all rows visible."""
-import sys, time, torch
+"""Timing of the fused sparse optimizer step (csrc/optim.hip) at c2 / c3 sizes, all rows visible (tools/timing.py's
+single window: 3 warm-up calls, 20 calls in one window on the host clock, mean per call)."""
+import sys, torch
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import splat_trainer_amd as sta
 from splat_trainer_amd import optim
 from splat_trainer_amd.harness import point_basis
+from timing import HostClock, single_window
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 500_000
 GROUPS = dict(position=dict(lr=0.3, type="local_vector"), log_scaling=dict(lr=0.08), rotation=dict(lr=0.01, type="vector"),
               alpha_logit=dict(lr=0.1), feature=dict(lr=5.0, type="vector"))
@@ -21,10 +23,7 @@ def hip_step():
 def hip_step_only(vis_idx, w, basis):
   pc.step(visibility=w, indexes=vis_idx, basis=basis)
 def timeit(f, *a, reps=20):
-  for _ in range(3): f(*a)
-  torch.cuda.synchronize(); t0 = time.perf_counter()
-  for _ in range(reps): f(*a)
-  torch.cuda.synchronize(); return (time.perf_counter() - t0) / reps * 1e3
+  return single_window(lambda: f(*a), reps, warmup=3, clock=HostClock())
 vis_idx = pc.visible.nonzero().squeeze(1); w = pc.visible[vis_idx]
 basis = point_basis(pc.log_scaling[vis_idx].detach(), pc.rotation[vis_idx].detach()).contiguous()
 print(f"n={n}: scene.step (nonzero + basis + fused step) {timeit(hip_step):.3f} ms; fused step alone "

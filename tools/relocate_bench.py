@@ -1,7 +1,8 @@
 """Times one relocation round of the MCMC controller (splat_trainer_amd.controller.relocate_points, csrc/relocate.hip)
 against its torch form written out below, on the same GPU in the same process: the two are alternated repetition by
-repetition after a warm-up, timed with device events, and reported as median and [min, max]
-(tools/visibility_bench.py's harness).  It runs no reference code.
+repetition after a warm-up, timed with device events, and reported as median and [min, max] (tools/timing.py's loop:
+2 interleaved warm-up rounds, 9 repetitions, one call per window, fixed order, one reused event pair, lower median).
+It runs no reference code.
 
     python tools/relocate_bench.py [--quick] [--json out.json]
 
@@ -31,12 +32,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import controller as ctl  # noqa: E402
 from splat_trainer_amd.controller_math import PointState  # noqa: E402
 from splat_trainer_amd.optim import ParameterClass  # noqa: E402
-from visibility_bench import alternated, row  # noqa: E402
+from timing import comparison_row, repetitions  # noqa: E402
 
 PARAMETERS = dict(position=dict(lr=0.003, type="local_vector"), log_scaling=dict(lr=0.005),
                   rotation=dict(lr=0.001, type="vector"), alpha_logit=dict(lr=0.01), feature=dict(lr=0.5, type="vector"))
@@ -117,8 +117,8 @@ def main():
       step[0] += 1
       sta.relocate_points(points, state, dead, O_FLOOR, 0, step[0])
 
-    a, b = alternated(native, lambda: torch_round(twin, twin_state, dead), reps=9)
-    r = row(f"relocation round N={n}, {int(dead.sum())} dead", a, b)
+    ms = repetitions(dict(native=native, torch=lambda: torch_round(twin, twin_state, dead)), 9, warmup=2)
+    r = comparison_row(f"relocation round N={n}, {int(dead.sum())} dead", ms["native"], ms["torch"])
     for k, t in points.tensors.items():
       assert torch.isfinite(t).all() and torch.isfinite(twin.tensors[k]).all(), k
     rows.append(r)

@@ -11,6 +11,9 @@ export           a whole ``MLPScene.to_sh_gaussians(method="lstsq")`` against ``
                  (both spend most of their time in the per-camera visibility query and colour model, which they share);
 quality          both exports' visibility-weighted colour MSE, prediction clamped to [0, 1], on the 32 fitted views and on
                  8 held-out views of the same ring.
+
+The loops are tools/timing.py's.  Kernels alone: 1 warm-up launch, 5 windows of 4 launches, a fresh event pair per window,
+lower median.  Export: 1 warm-up call of each form, 3 repetitions of one call, fixed order, host clock, lower median.
 """
 from __future__ import annotations
 
@@ -18,7 +21,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
 
@@ -26,25 +28,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import _lib, mlp_scene, sh_fit, synthetic  # noqa: E402
+from timing import HostClock, clear, lower_median, repetitions, spread  # noqa: E402
 
 PARAMETERS = dict(position=dict(lr=0.003, type="local_vector"), log_scaling=dict(lr=0.005),
                   rotation=dict(lr=0.001, type="vector"), alpha_logit=dict(lr=0.01), feature=dict(lr=0.5, type="vector"))
 
 
 def timed(fn, launches, reps=5):
-  fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(reps):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(launches):
-      fn()
-    end.record()
-    end.synchronize()
-    times.append(start.elapsed_time(end) / launches)
-  times.sort()
-  return times[len(times) // 2], [round(times[0], 4), round(times[-1], 4)]
+  times = repetitions({"fn": fn}, reps, warmup=1, calls=launches, fresh_events=True)["fn"]
+  return lower_median(times), [round(t, 4) for t in spread(times)]
 
 
 def kernels_alone(N, degree, gen):
@@ -104,31 +96,24 @@ def export(N, width, height, reps):
   fitted = [i for i in range(40) if i not in held]
   fit_cams, held_cams = [cams[i] for i in fitted], [cams[i] for i in held]
 
+  features = {}                                             # each form's last result, for the quality figures
+
   def lstsq():
-    return scene.to_sh_gaussians(fit_cams, fitted, sh_degree=2, method="lstsq").feature
+    features["lstsq"] = scene.to_sh_gaussians(fit_cams, fitted, sh_degree=2, method="lstsq").feature
 
   def adam():
-    return scene.to_sh_gaussians(fit_cams, fitted, epochs=1, sh_degree=2, generator=torch.Generator().manual_seed(0)).feature
+    features["adam"] = scene.to_sh_gaussians(fit_cams, fitted, epochs=1, sh_degree=2,
+                                             generator=torch.Generator().manual_seed(0)).feature
 
-  times, features = dict(lstsq=[], adam=[]), {}
-  for fn in (lstsq, adam):
-    fn()                                                  # warm-up
-  for _ in range(reps):
-    for name, fn in (("lstsq", lstsq), ("adam", adam)):
-      torch.cuda.synchronize()
-      t0 = time.perf_counter()
-      features[name] = fn()
-      torch.cuda.synchronize()
-      times[name].append(1e3 * (time.perf_counter() - t0))
+  times = repetitions(dict(lstsq=lstsq, adam=adam), reps, warmup=1, clock=HostClock())
   out = dict(what=f"to_sh_gaussians N={N} cameras={len(fitted)} at {width // 2}x{height // 2} degree=2")
   for name, ts in times.items():
-    ts.sort()
-    out[f"{name}_ms"] = round(ts[len(ts) // 2], 2)
-    out[f"{name}_range"] = [round(ts[0], 2), round(ts[-1], 2)]
+    out[f"{name}_ms"] = round(lower_median(ts), 2)
+    out[f"{name}_range"] = [round(t, 2) for t in spread(ts)]
     out[f"{name}_mse_fitted"] = float(f"{weighted_mse(scene, features[name], fit_cams, fitted):.4e}")
     out[f"{name}_mse_held_out"] = float(f"{weighted_mse(scene, features[name], held_cams, held):.4e}")
   out["adam_over_lstsq"] = round(out["adam_ms"] / out["lstsq_ms"], 2)
-  out["lstsq_faster_every_repetition"] = times["lstsq"][-1] < times["adam"][0]
+  out["lstsq_faster_every_repetition"] = clear(times["lstsq"], times["adam"])
   return out
 
 

@@ -7,8 +7,9 @@ remap   ``gsr_image_remap_u8`` alone on B = 8 images of 4032 x 3024 x 3 through 
         mode="bilinear", align_corners=True)`` on the unquantised grid, round, -> uint8.  Two source batches of 293 MB
         each (past the 256 MiB Infinity Cache) are taken in turn, so no call finds its source in the cache.  Device
         events around CALLS calls enqueued back to back, the two forms alternated, median and [min, max] over the
-        repetitions.  ``GBps`` is (source bytes + map bytes + destination bytes) over that time -- for the torch form
-        too, so it is the rate at which it does the same job, not its own traffic -- and ``hbm_share`` is that over the
+        repetitions (tools/timing.py's loop: 3 warm-up calls per form, REPS repetitions of CALLS calls per window,
+        fixed order, a fresh event pair per window, lower median; a form is handed the call index).  ``GBps`` is
+        (source bytes + map bytes + destination bytes) over that time -- for the torch form too, so it is the rate at which it does the same job, not its own traffic -- and ``hbm_share`` is that over the
         6.29 TB/s a float4 copy reaches on this GPU.  ``differing_bytes`` counts where the float form on the unquantised
         grid is not the fixed-point result, ``max_difference`` the largest such step.
 map     ``gsr_undistort_map`` of that camera alone, the same way: 12.2 M entries of 8 bytes.
@@ -27,6 +28,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import splat_trainer_amd as sta  # noqa: E402
+from timing import repetitions  # noqa: E402
 
 W, H, B = 4032, 3024, 8
 HBM_COPY_TBPS = 6.29
@@ -64,21 +66,7 @@ def stats(times):
 
 def timed(forms):
   """forms: (name, fn(call index)) -> name -> per-call milliseconds of each repetition, the forms alternated."""
-  for _, fn in forms:
-    for k in range(3):
-      fn(k)
-  torch.cuda.synchronize()
-  ms = {name: [] for name, _ in forms}
-  for _ in range(REPS):
-    for name, fn in forms:
-      start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      start.record()
-      for k in range(CALLS):
-        fn(k)
-      end.record()
-      end.synchronize()
-      ms[name].append(start.elapsed_time(end) / CALLS)
-  return ms
+  return repetitions(forms, REPS, warmup=3, warmup_form="per_form", calls=CALLS, fresh_events=True)
 
 
 def bench_remap(cam, und):

@@ -1,6 +1,7 @@
 """Times the visibility kernels (splat_trainer_amd.visibility) against the torch form of the reference they replace, on
 the same GPU in the same process: the two are alternated repetition by repetition after a warm-up, timed with device
-events, and reported as median and [min, max] over the repetitions.
+events, and reported as median and [min, max] over the repetitions.  The loop is tools/timing.py's: 2 interleaved
+warm-up rounds, 5 to 9 repetitions, one call per window, fixed order, one reused event pair, lower median.
 
     python tools/visibility_bench.py [--quick] [--json out.json]
 
@@ -26,6 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from splat_trainer_amd import visibility as vis  # noqa: E402
+from timing import comparison_row, lower_median, repetitions  # noqa: E402
 
 ISSUE_BOUND = 256 * 4 * 16 * 2.4e9
 FRUSTUM_OPS = 25            # 9 v_fma, 2 v_mul, 6 v_cmp, the count select / add and the ballot's share, per pair
@@ -69,31 +71,16 @@ def torch_view_features(labels, K, idx, v, threshold=0.01):
   return vector
 
 
-def alternated(native, reference, reps, warmup=2):
-  for _ in range(warmup):
-    native()
-    reference()
-  torch.cuda.synchronize()
-  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  times = ([], [])
-  for _ in range(reps):
-    for fn, ts in zip((native, reference), times):
-      a.record()
-      fn()
-      b.record()
-      b.synchronize()
-      ts.append(a.elapsed_time(b))
-  return [sorted(ts) for ts in times]
+def measure(native, reference, reps):
+  ms = repetitions((("native", native), ("torch", reference)), reps, warmup=2)
+  return ms["native"], ms["torch"]
 
 
 def row(name, native, reference, pairs=None, ops=None):
-  med = lambda ts: ts[len(ts) // 2]
-  r = dict(case=name, native_ms=round(med(native), 4), native_range=[round(native[0], 4), round(native[-1], 4)],
-           torch_ms=round(med(reference), 3), torch_range=[round(reference[0], 3), round(reference[-1], 3)],
-           speedup=round(med(reference) / med(native), 1), clear=native[-1] < reference[0])
+  r = comparison_row(name, native, reference)
   if pairs:
-    r["pairs_per_s"] = pairs / (med(native) * 1e-3)
-    r["valu_issue_share"] = round((pairs * ops / ISSUE_BOUND) / (med(native) * 1e-3), 3)
+    r["pairs_per_s"] = pairs / (lower_median(native) * 1e-3)
+    r["valu_issue_share"] = round((pairs * ops / ISSUE_BOUND) / (lower_median(native) * 1e-3), 3)
   return r
 
 
@@ -113,8 +100,8 @@ def main():
       cams = ring(V)
       cams.records()
       m, sizes, ranges = cams.image_t_world(), cams.image_sizes.tolist(), cams.depth_ranges.tolist()
-      native, reference = alternated(lambda: vis.frustum_counts(cams, points),
-                                     lambda: torch_frustum(m, sizes, ranges, points), reps=7 if V <= 64 else 5)
+      native, reference = measure(lambda: vis.frustum_counts(cams, points),
+                                  lambda: torch_frustum(m, sizes, ranges, points), reps=7 if V <= 64 else 5)
       rows.append(row(f"frustum_counts N={N} V={V}", native, reference, N * V, FRUSTUM_OPS))
   N, K = sizes_n[1], 1024                       # the reference's default vis_clusters (config/trainer/default.yaml)
   labels = torch.randint(0, K, (N,), generator=g).cuda()
@@ -122,8 +109,8 @@ def main():
   for M in sizes_n:
     idx = torch.randperm(N, generator=g)[:M].cuda()
     v = (torch.rand(M, generator=g) ** 3).cuda()
-    native, reference = alternated(lambda: clusters.view_features(idx, v),
-                                   lambda: torch_view_features(labels, K, idx, v), reps=9)
+    native, reference = measure(lambda: clusters.view_features(idx, v),
+                                lambda: torch_view_features(labels, K, idx, v), reps=9)
     rows.append(row(f"view_features N={N} M={M} K={K}", native, reference))
   for r in rows:
     print(json.dumps(r))

@@ -5,8 +5,9 @@ workaround the wide path replaces: a C = 3 render plus a C = 1 render of the sam
     python tools/wide_bench.py --clustered [--segments -1 0] [--channels 4 8 16]
 
 Device-event timing of whole steps (projection excluded: it is shared by every variant), warm-up first, then the variants
-run in alternating order `reps` times; prints the median milliseconds per step.  Per-kernel times come from a run of its
-own under `rocprofv3 --kernel-trace --stats -- python tools/wide_bench.py --reps 5`.
+run in alternating order `reps` times; prints the median milliseconds per step (tools/timing.py's loop: --warmup
+interleaved rounds, one call per window, mirrored order, a fresh event pair per window, the mean-of-middles median).
+Per-kernel times come from a run of its own under `rocprofv3 --kernel-trace --stats -- python tools/wide_bench.py --reps 5`.
 
 --clustered: the wide path on the uniform scene and on the clustered one (half of the splats in the central 10 % x 10 %
 of the frame: the construction of tests/test_gpu_segments.py) under every RasterConfig.segment_pairs value of --segments
@@ -30,6 +31,7 @@ import torch  # noqa: E402
 
 import splat_trainer_amd as sta  # noqa: E402
 from splat_trainer_amd import renderer, synthetic  # noqa: E402
+from timing import mid_median, repetitions  # noqa: E402
 
 
 def clustered_scene(n, w, h, frac, region, seed=0):
@@ -76,19 +78,13 @@ def clustered_main(args):
     return r
 
   overlaps = {}
-  for _ in range(args.warmup):
-    for v in variants:
-      overlaps[v[0]] = step(v).num_overlaps
-  torch.cuda.synchronize()
-  steps, k67 = {v: [] for v in variants}, {v: [] for v in variants}
-  for rep in range(args.reps):
-    for v in (variants if rep % 2 == 0 else list(reversed(variants))):
-      a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      a.record()
-      step(v)
-      b.record()
-      b.synchronize()
-      steps[v].append(a.elapsed_time(b))
+
+  def counted(v):                                              # every call notes its scene's pair count
+    overlaps[v[0]] = step(v).num_overlaps
+
+  steps = repetitions([(v, lambda v=v: counted(v)) for v in variants], args.reps, args.warmup, order="mirrored",
+                      fresh_events=True)
+  k67 = {v: [] for v in variants}
   for rep in range(args.reps):
     for v in (variants if rep % 2 == 0 else list(reversed(variants))):
       timer = renderer.KernelTimer()
@@ -109,7 +105,7 @@ def clustered_main(args):
         v = (s, seg, c)
         k6 = statistics.median(t[0] for t in k67[v])
         k7 = statistics.median(t[1] for t in k67[v])
-        row[s] = dict(step_ms=statistics.median(steps[v]), step_min=min(steps[v]), step_max=max(steps[v]), k6_ms=k6, k7_ms=k7)
+        row[s] = dict(step_ms=mid_median(steps[v]), step_min=min(steps[v]), step_max=max(steps[v]), k6_ms=k6, k7_ms=k7)
         print(f"  C={c:2d} segment_pairs={seg:4d} {s:9s}  step {row[s]['step_ms']:8.3f} ms (min {row[s]['step_min']:.3f}, "
               f"max {row[s]['step_max']:.3f})   K6 {k6 * 1e3:7.0f} us  K7 {k7 * 1e3:7.0f} us")
       if len(row) == 2:
@@ -155,21 +151,9 @@ def main():
     g2.grad = None
 
   variants = {"C=3": (3,), "C=4": (4,), "C=8": (8,), "C=16": (16,), "C=3 + C=1": (3, 1)}
-  times = {k: [] for k in variants}
-  for _ in range(args.warmup):
-    for v in variants.values():
-      step(v)
-  torch.cuda.synchronize()
-  for rep in range(args.reps):
-    order = list(variants) if rep % 2 == 0 else list(reversed(variants))
-    for k in order:
-      a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      a.record()
-      step(variants[k])
-      b.record()
-      b.synchronize()
-      times[k].append(a.elapsed_time(b))
-  med = {k: statistics.median(v) for k, v in times.items()}
+  times = repetitions([(k, lambda v=v: step(v)) for k, v in variants.items()], args.reps, args.warmup, order="mirrored",
+                      fresh_events=True)
+  med = {k: mid_median(v) for k, v in times.items()}
   print(f"c2 geometry: M={M} visible splats, 1920x1080; median ms per fwd+bwd step over {args.reps} alternating runs")
   for k, v in med.items():
     print(f"  {k:10s} {v:8.3f} ms   (min {min(times[k]):.3f}, max {max(times[k]):.3f})")
