@@ -402,8 +402,21 @@ struct GsrExtent {            // half-open tile rectangle [x0,x1) x [y0,y1) and 
   float qmax;                 // d^T conic d <= qmax can reach alpha >= alpha_threshold
 };
 
-// Conservative support of a projected splat: q <= min(q_max, 2 ln(opacity / alpha_threshold)) (inflated a
-// hair so that fp32 rounding in the per-pixel test can never include a pixel the binning excluded).
+// Support of a projected splat as K4 bins it: q <= qmax = min(q_max * 1.00001, 2 ln(opacity / alpha_threshold) * 1.0001
+// + 1e-4), inside the tile rectangle of the bounding box with half-widths sqrt(qmax C / det) + 1e-3 and
+// sqrt(qmax A / det) + 1e-3.
+// What the inflation covers: the factors and the 1e-4 on qmax exceed the rounding of logf, of qmax's own arithmetic
+// and of a per-pixel q of that size (a few 2^-24 of qmax), so the per-tile test q <= qmax, taken at the exact minimiser,
+// keeps every pixel the composite can accept; the 1e-3 px on the half-widths covers the rounding of u, v, the square
+// root and the division for a well-conditioned conic.
+// What the conic's conditioning takes away: det = A C - B B cancels.  With u = 2^-24 its relative error is up to
+// rho = 2u (|A C| + B B) / det, and the half-widths inherit it: a needle of 300 x 0.55 px at 45 degrees has rho of
+// about 0.02 and its fp32 box falls about a pixel short of the fp64 box of the same fp32 conic, far more than 1e-3.
+// So the box is not a superset by construction.  What holds, and what tests/binning_contract.py pins row by row: a tile
+// column (row) is inside the extent whenever it is inside for the half-width h (1 - rho - 8u) - 8u (|u| + h + 16), with h
+// the exact half-width, and outside whenever it is outside for h (1 + rho + 8u) + 8u (|u| + h + 16) + 1.01e-3; in between
+// either answer occurs.  The rim that rho gives up is where the ellipse is tangent to the box, so it holds a pixel
+// centre only by accident: the contract's needles and giants lose no pixel that passes the fp64 per-pixel test.
 GSR_HD GsrExtent gsr_splat_extent(float u, float v, float A, float B, float C, float op,
                                   const GsrRasterParams& rp, int tiles_x, int tiles_y) {
   GsrExtent e;

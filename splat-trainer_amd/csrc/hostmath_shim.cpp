@@ -105,6 +105,37 @@ void hm_tile_hits(const void* params, int64_t M, const float* g2d, int tiles_x, 
   }
 }
 
+void hm_splat_extent(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, int32_t* extent,
+                     float* qmax) {
+  GsrRasterParams rp;
+  memcpy(&rp, params, sizeof(rp));
+  for (int64_t m = 0; m < M; ++m) {
+    const float* g = g2d + 6 * m;
+    GsrExtent e = gsr_splat_extent(g[0], g[1], g[2], g[3], g[4], g[5], rp, tiles_x, tiles_y);
+    int32_t* o = extent + 4 * m;
+    o[0] = e.x0; o[1] = e.x1; o[2] = e.y0; o[3] = e.y1;
+    qmax[m] = e.qmax;
+  }
+}
+
+// K4's verdict per tile (binning.hip): the half mask alone for an extent of up to 32 tiles (tile_count_one's map), the
+// whole-tile test in front of it for a larger one (hits_of_large_extent).
+void hm_tile_half_masks(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, uint8_t* masks) {
+  GsrRasterParams rp;
+  memcpy(&rp, params, sizeof(rp));
+  const int64_t nt = (int64_t)tiles_x * tiles_y;
+  for (int64_t m = 0; m < M; ++m) {
+    const float* g = g2d + 6 * m;
+    GsrExtent e = gsr_splat_extent(g[0], g[1], g[2], g[3], g[4], g[5], rp, tiles_x, tiles_y);
+    const bool large = (e.x1 - e.x0) * (e.y1 - e.y0) > 32;
+    for (int ty = e.y0; ty < e.y1; ++ty)
+      for (int tx = e.x0; tx < e.x1; ++tx) {
+        if (large && !gsr_tile_hit(g[0], g[1], g[2], g[3], g[4], e.qmax, tx, ty)) continue;
+        masks[m * nt + ty * tiles_x + tx] = (uint8_t)gsr_tile_half_mask(g[0], g[1], g[2], g[3], g[4], e.qmax, tx, ty);
+      }
+  }
+}
+
 // bilateral-grid slice of one image (gsr_bilagrid.h) with ONE grid [12, L, GH, GW]: the cell's corner columns are gathered
 // per pixel into the cols[4][L][12] layout the kernels stage in LDS.
 static void hm_bg_cols(const float* grid, int L, int GH, int GW, int cx, int cy, float* cols) {

@@ -31,6 +31,13 @@ void hm_in_view(const float* T, const float* proj, int64_t N, const float* pos, 
 void hm_sh_basis(int K, int64_t M, const float* dirs, float* Y);
 /* per-splat tile hit mask over the whole tile grid: hits[m * tiles_x * tiles_y + ty * tiles_x + tx] */
 void hm_tile_hits(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, uint8_t* hits);
+/* gsr_splat_extent per splat: extent [M, 4] int32 = x0 x1 y0 y1 (half-open tile rectangle) and qmax [M] */
+void hm_splat_extent(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, int32_t* extent,
+                     float* qmax);
+/* K4's verdict over the whole tile grid: masks[m * tiles_x * tiles_y + ty * tiles_x + tx] = bit 0 upper / bit 1 lower half
+ * (zero-filled by the caller; tiles outside the extent are not written).  Extents above 32 tiles pass the whole-tile
+ * test first, as the device's wave path does. */
+void hm_tile_half_masks(const void* params, int64_t M, const float* g2d, int tiles_x, int tiles_y, uint8_t* masks);
 
 /* ---- bilateral-grid slice of one image (gsr_bilagrid.h) with ONE grid [12, L, GH, GW] ---- */
 void hm_bilagrid_forward(const float* grid, int L, int GH, int GW, const float* rgb, int H, int W, float* out);
