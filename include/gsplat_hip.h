@@ -604,6 +604,7 @@ typedef struct GsrColumnC {
   const void* tail;      /* [n_tail, width] appended rows, or NULL: the appended rows are zero-filled */
   int32_t width_dwords;
 } GsrColumnC;
+#define GSR_COMPACT_BLOCK 256             /* source rows per block offset: a consumer ranks inside blocks of this size */
 size_t gsr_compact_workspace_bytes(int64_t N);
 /* keep_mask [N] bytes.  block_offsets_out [ceil(N/256)] = kept rows before each block of 256 source rows;
  * kept_total_dev = number of kept rows (read it back to size the destination columns). */
@@ -1005,6 +1006,69 @@ int gsr_undistort_map(const double* source_host, const double* target_host, int3
                       int32_t Wd, int32_t* map_out, void* stream);
 int gsr_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map,
                        uint8_t* dst, int32_t Hd, int32_t Wd, void* stream);
+
+/* ---- depth-map fusion (no reference counterpart): multi-view consistency, point emission, voxel-grid mean -------
+ * The arithmetic is csrc/gsr_fusion.h, shared with the host shim: fp64 throughout, every product and sum rounded on its
+ * own in the order given here, one IEEE division per projection.  Pixel (row i, column j) has its centre at
+ * (j + 0.5, i + 0.5).  A depth is valid when it is above 0 and finite.  Every double travels in a host array (the
+ * binding's type rule has no double by value); the arrays are read before the call returns.
+ *
+ * gsr_fuse_check.  ref_depth [Hr, Wr] float; ref_intrinsics_host [4] = ifx ify cx cy with ifx = 1 / fx, ify = 1 / fy;
+ * sources_host [S] name each source's depth map [H, W]; source_params_host [S, 16] = the rows of src_t_ref (3 x 4), then
+ * fx fy cx cy of the source; tolerances_host [2] = near, rel_tol; counts [Hr, Wr, 2] uint8 = agree, violate.  Per valid
+ * reference pixel of depth d and per source:
+ *   x = ((j + 0.5) - cx) ifx, y = ((i + 0.5) - cy) ify, X = x d, Y = y d, Z = d
+ *   p_k = ((r_k0 X + r_k1 Y) + r_k2 Z) + t_k;  !(p_2 > near): no vote;  iz = 1 / p_2
+ *   us = fx_s (p_0 iz) + cx_s, vs likewise; outside [0, Ws) x [0, Hs) or NaN: no vote; ds = src[floor(vs), floor(us)]
+ *   ds not valid: no vote;  tol = rel_tol p_2, diff = ds - p_2: |diff| <= tol agree, else diff > tol violate, else none.
+ * The pixel's two counters are read, incremented with saturation at 255 and written once; a pixel without a valid
+ * depth keeps its counters.  More than GSR_FUSE_MAX_SOURCES sources are several calls.
+ *   Checked in this order: a negative Hr or Wr GSR_ERR_INVALID_ARGUMENT; one above 32768 GSR_ERR_UNSUPPORTED; S outside
+ *   [1, GSR_FUSE_MAX_SOURCES], a NULL host array, a host value that is not finite or rel_tol < 0
+ *   GSR_ERR_INVALID_ARGUMENT; a source side below 0 GSR_ERR_INVALID_ARGUMENT, above 32768 GSR_ERR_UNSUPPORTED; Hr == 0 or
+ *   Wr == 0 GSR_OK; a NULL ref_depth or counts, or a NULL depth of a source that has pixels, GSR_ERR_INVALID_ARGUMENT.
+ *
+ * gsr_fuse_mask writes keep_out [Hr Wr] bytes: 1 where the depth is valid, agree >= min_agree and violate <=
+ * max_violate -- the input of gsr_compact_offsets, whose blocks of GSR_COMPACT_BLOCK pixels the emit kernel ranks inside.  gsr_fuse_emit writes the kept pixels in row-major order: the r-th
+ * kept pixel goes to row base + r of points_out [capacity, 3] float, colors_out [capacity, 3] uint8 and agree_out
+ * [capacity] uint8; a row at or beyond capacity is not written.  The point is ((w_k0 X + w_k1 Y) + w_k2 Z) + t_k of
+ * world_t_ref_host [12] (3 x 4 rows) rounded to float; the colour floor(clamp(c, 0, 1) 255 + 0.5) of image [Hr, Wr, 3]
+ * float (NaN -> 0), 255 without an image; agree the pixel's agree count.  block_offsets: what gsr_compact_offsets made of
+ * the mask.
+ *   Checked in this order: a negative size, base or capacity GSR_ERR_INVALID_ARGUMENT; a side above 32768
+ *   GSR_ERR_UNSUPPORTED; min_agree or max_violate outside [0, 255], a NULL or non-finite host array
+ *   GSR_ERR_INVALID_ARGUMENT; Hr == 0, Wr == 0 or (emit) base >= capacity GSR_OK; a NULL device pointer other than image
+ *   GSR_ERR_INVALID_ARGUMENT.
+ *
+ * gsr_voxel_downsample.  points [N, 3] float, colors [N, 3] uint8, grid_host [4] = voxel ox oy oz.  Per axis:
+ * s = (p - origin) inv with inv = 1 / voxel; q = floor(s) clamped to [-2^20, 2^20 - 1] (NaN -> -2^20); f = s - q clamped
+ * to [0, 1] (NaN -> 0); F = floor(f 2^20 + 0.5); key = (qz + 2^20) << 42 | (qy + 2^20) << 21 | (qx + 2^20), 63 bits.  Per occupied
+ * voxel of n points, with the int64 sums S = sum F and C = sum of a colour byte: mean = (float)(origin + (q + (S / n)
+ * 2^-20) voxel), colour = (2 C + n) / (2 n) in integer division.  points_out [K, 3], colors_out [K, 3], counts_out [K]
+ * int32 (capacity N each) in ascending key order, K_dev[0] = K.  The sums are integers: the result does not depend on
+ * the order of addition.
+ *   Checked in this order: N outside [0, 2^31 - 1], a NULL or non-finite grid_host, voxel not above 0 (or 1 / voxel not
+ *   finite) GSR_ERR_INVALID_ARGUMENT; N == 0 GSR_OK before any pointer is looked at (nothing is written, K_dev
+ *   included); a NULL array or K_dev GSR_ERR_INVALID_ARGUMENT; a NULL or short workspace (gsr_voxel_workspace_bytes)
+ *   GSR_ERR_WORKSPACE_TOO_SMALL. */
+#define GSR_FUSE_MAX_SOURCES 16
+typedef struct GsrFuseSource {
+  const float* depth;    /* [H, W] */
+  int32_t H, W;
+} GsrFuseSource;
+int gsr_fuse_check(const float* ref_depth, int32_t Hr, int32_t Wr, const double* ref_intrinsics_host,
+                   const GsrFuseSource* sources_host, const double* source_params_host, int32_t S,
+                   const double* tolerances_host, uint8_t* counts, void* stream);
+int gsr_fuse_mask(const float* ref_depth, const uint8_t* counts, int32_t Hr, int32_t Wr, int32_t min_agree,
+                  int32_t max_violate, uint8_t* keep_out, void* stream);
+int gsr_fuse_emit(const float* ref_depth, const uint8_t* counts, const float* image, int32_t Hr, int32_t Wr,
+                  const double* ref_intrinsics_host, const double* world_t_ref_host, int32_t min_agree,
+                  int32_t max_violate, const uint32_t* block_offsets, int64_t base, int64_t capacity, float* points_out,
+                  uint8_t* colors_out, uint8_t* agree_out, void* stream);
+size_t gsr_voxel_workspace_bytes(int64_t N);
+int gsr_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, const double* grid_host,
+                         float* points_out, uint8_t* colors_out, int32_t* counts_out, uint32_t* K_dev, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the

@@ -34,6 +34,8 @@ from .normalization import Normalization, NormalizationConfig, median_knn
 from .histogram import Histogram, tensor_histogram
 from .image import resize_area
 from .undistort import LensCamera, Undistortion, optimal_pinhole, remap, undistort_map
+from .fusion import (FusionConfig, depth_consistency, fuse_depth_maps, fuse_scene, select_sources,
+                     voxel_downsample)
 from .colmap_io import read_model, write_model
 from .colmap import COLMAPDataset, export_colmap
 from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
@@ -71,4 +73,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "NoProgressException", "TrainingTimeoutException", "find_checkpoint", "load_checkpoint", "Trainer",
            "resize_area", "LensCamera", "Undistortion", "optimal_pinhole", "undistort_map", "remap", "read_model",
            "write_model", "COLMAPDataset", "export_colmap", "weighted_draws", "relocate_weights", "relocate_rescale",
-           "relocate_rows", "relocate_points", "grow_points", "growth_target"]
+           "relocate_rows", "relocate_points", "grow_points", "growth_target", "FusionConfig", "depth_consistency",
+           "select_sources", "fuse_depth_maps", "voxel_downsample", "fuse_scene"]

@@ -118,6 +118,7 @@ __global__ __launch_bounds__(DN_THREADS) void select_mask_kernel(const float* __
 }
 
 // ------------------------------------------------------------------------------------------------ compaction
+static_assert(DN_THREADS == GSR_COMPACT_BLOCK, "the block offsets count DN_THREADS rows: the ABI states the number");
 __global__ __launch_bounds__(DN_THREADS) void compact_count_kernel(const uint8_t* __restrict__ keep, int64_t N,
                                                                    uint32_t* __restrict__ block_counts) {
   __shared__ uint32_t s_w[4];

@@ -7,6 +7,10 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "gsr_math.h"
 #include "gsr_bilagrid.h"
 #include "gsr_neighbours.h"
@@ -21,6 +25,7 @@
 #include "gsr_image.h"
 #include "gsr_undistort.h"
 #include "gsr_relocate.h"
+#include "gsr_fusion.h"
 
 extern "C" {
 
@@ -878,6 +883,118 @@ int hm_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int
       }
     }
   }
+  return GSR_OK;
+}
+
+// ---- depth-map fusion (gsr_fusion.h) ----
+int hm_fuse_check(const float* ref_depth, int32_t Hr, int32_t Wr, const double* ref_intrinsics, const void* sources_,
+                  const double* source_params, int32_t S, const double* tolerances, uint8_t* counts) {
+  const GsrFuseSource* sources = reinterpret_cast<const GsrFuseSource*>(sources_);
+  int launch = 0;
+  const int rc = gsr_fuse_check_args(ref_depth, Hr, Wr, ref_intrinsics, sources, source_params, S, tolerances, counts,
+                                     &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrFuseRef ref = {ref_intrinsics[0], ref_intrinsics[1], ref_intrinsics[2], ref_intrinsics[3]};
+  const GsrFuseView* views = reinterpret_cast<const GsrFuseView*>(source_params);      // 16 doubles each
+  for (int32_t i = 0; i < Hr; ++i)
+    for (int32_t j = 0; j < Wr; ++j) {
+      const int64_t px = (int64_t)i * Wr + j;
+      const double d = (double)ref_depth[px];
+      if (!gsr_fuse_valid(d)) continue;
+      double X, Y;
+      gsr_fuse_unproject(ref, i, j, d, &X, &Y);
+      uint32_t agree = 0, violate = 0;
+      for (int s = 0; s < S; ++s) {
+        int32_t is, js;
+        double p2;
+        if (!gsr_fuse_project(views[s], sources[s].H, sources[s].W, tolerances[0], X, Y, d, &is, &js, &p2)) continue;
+        const int vote = gsr_fuse_vote((double)sources[s].depth[(int64_t)is * sources[s].W + js], p2, tolerances[1]);
+        agree += vote == GSR_FUSE_AGREE;
+        violate += vote == GSR_FUSE_VIOLATE;
+      }
+      counts[2 * px] = gsr_fuse_saturate(counts[2 * px] + agree);
+      counts[2 * px + 1] = gsr_fuse_saturate(counts[2 * px + 1] + violate);
+    }
+  return GSR_OK;
+}
+
+void hm_fuse_votes(const double* ds, const double* p2, int64_t n, const double* rel_tol, int32_t* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = gsr_fuse_vote(ds[i], p2[i], rel_tol[0]);
+}
+
+int hm_fuse_mask(const float* ref_depth, const uint8_t* counts, int32_t Hr, int32_t Wr, int32_t min_agree,
+                 int32_t max_violate, uint8_t* keep_out) {
+  int launch = 0;
+  const int rc = gsr_fuse_mask_args(ref_depth, counts, Hr, Wr, min_agree, max_violate, keep_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  for (int64_t px = 0; px < (int64_t)Hr * Wr; ++px)
+    keep_out[px] = gsr_fuse_keep((double)ref_depth[px], counts[2 * px], counts[2 * px + 1], min_agree, max_violate) ? 1 : 0;
+  return GSR_OK;
+}
+
+int hm_fuse_emit(const float* ref_depth, const uint8_t* counts, const float* image, int32_t Hr, int32_t Wr,
+                 const double* ref_intrinsics, const double* world_t_ref, int32_t min_agree, int32_t max_violate,
+                 int64_t base, int64_t capacity, float* points_out, uint8_t* colors_out, uint8_t* agree_out) {
+  int launch = 0;
+  const uint32_t no_block_offsets = 0;       // the walk below ranks the pixels itself; the check wants a pointer
+  const int rc = gsr_fuse_emit_args(ref_depth, counts, Hr, Wr, ref_intrinsics, world_t_ref, min_agree, max_violate,
+                                    &no_block_offsets, base, capacity, points_out, colors_out, agree_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrFuseRef ref = {ref_intrinsics[0], ref_intrinsics[1], ref_intrinsics[2], ref_intrinsics[3]};
+  int64_t row = base;
+  for (int32_t i = 0; i < Hr; ++i)
+    for (int32_t j = 0; j < Wr; ++j) {
+      const int64_t px = (int64_t)i * Wr + j;
+      const double d = (double)ref_depth[px];
+      if (!gsr_fuse_keep(d, counts[2 * px], counts[2 * px + 1], min_agree, max_violate)) continue;
+      if (row >= capacity) return GSR_OK;
+      double X, Y;
+      gsr_fuse_unproject(ref, i, j, d, &X, &Y);
+      for (int k = 0; k < 3; ++k) {
+        points_out[3 * row + k] = (float)gsr_fuse_row(world_t_ref + 4 * k, X, Y, d);
+        colors_out[3 * row + k] = image ? gsr_fuse_colour(image[3 * px + k]) : (uint8_t)255;
+      }
+      agree_out[row] = counts[2 * px];
+      ++row;
+    }
+  return GSR_OK;
+}
+
+void hm_voxel_keys(const float* points, int64_t n, const double* grid, uint64_t* keys) {
+  const GsrVoxelGrid g = gsr_voxel_grid_make(grid);
+  for (int64_t i = 0; i < n; ++i) keys[i] = gsr_voxel_key_of(g, points + 3 * i);
+}
+
+int hm_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, const double* grid, float* points_out,
+                        uint8_t* colors_out, int32_t* counts_out, int64_t* K_out) {
+  int launch = 0;
+  const int rc = gsr_voxel_args(points, colors, N, grid, points_out, colors_out, counts_out, K_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrVoxelGrid g = gsr_voxel_grid_make(grid);
+  std::vector<std::pair<uint64_t, int64_t>> order((size_t)N);
+  for (int64_t i = 0; i < N; ++i) order[(size_t)i] = {gsr_voxel_key_of(g, points + 3 * i), i};
+  std::sort(order.begin(), order.end());               // (key, index): the stable order
+  int64_t K = 0;
+  for (int64_t b = 0; b < N;) {
+    int64_t e = b, S[3] = {0, 0, 0}, C[3] = {0, 0, 0};
+    for (; e < N && order[(size_t)e].first == order[(size_t)b].first; ++e) {
+      const int64_t at = order[(size_t)e].second;
+      for (int k = 0; k < 3; ++k) {
+        int32_t q;
+        int64_t F;
+        gsr_voxel_axis(points[3 * at + k], g.origin[k], g.inv, &q, &F);
+        S[k] += F;
+        C[k] += colors[3 * at + k];
+      }
+    }
+    for (int k = 0; k < 3; ++k) {
+      points_out[3 * K + k] = gsr_voxel_mean(g.origin[k], g.voxel, gsr_voxel_key_axis(order[(size_t)b].first, k), S[k], e - b);
+      colors_out[3 * K + k] = gsr_voxel_colour(C[k], e - b);
+    }
+    counts_out[K++] = (int32_t)(e - b);
+    b = e;
+  }
+  K_out[0] = K;
   return GSR_OK;
 }
 

@@ -173,6 +173,24 @@ void hm_undistort_points(const double* source, const double* target, int32_t Hs,
 int hm_image_remap_u8(const uint8_t* src, int32_t B, int32_t Hs, int32_t Ws, int32_t C, const int32_t* map, uint8_t* dst,
                       int32_t Hd, int32_t Wd);
 
+/* ---- depth-map fusion (gsr_fusion.h): the device's arithmetic in plain loops, with its argument checks and codes ---- */
+/* gsr_fuse_check on host memory: sources [S] GsrFuseSource of include/gsplat_hip.h (16 bytes each: depth, H, W) */
+int hm_fuse_check(const float* ref_depth, int32_t Hr, int32_t Wr, const double* ref_intrinsics, const void* sources,
+                  const double* source_params, int32_t S, const double* tolerances, uint8_t* counts);
+/* the vote alone, on doubles: out [n] int32 (0 none, 1 agree, 2 violate) of source depths ds [n] against p2 [n] */
+void hm_fuse_votes(const double* ds, const double* p2, int64_t n, const double* rel_tol, int32_t* out);
+int hm_fuse_mask(const float* ref_depth, const uint8_t* counts, int32_t Hr, int32_t Wr, int32_t min_agree,
+                 int32_t max_violate, uint8_t* keep_out);
+/* gsr_fuse_emit on host memory; the kept pixels are ranked in a plain row-major walk, so it takes no block offsets */
+int hm_fuse_emit(const float* ref_depth, const uint8_t* counts, const float* image, int32_t Hr, int32_t Wr,
+                 const double* ref_intrinsics, const double* world_t_ref, int32_t min_agree, int32_t max_violate,
+                 int64_t base, int64_t capacity, float* points_out, uint8_t* colors_out, uint8_t* agree_out);
+/* gsr_voxel_downsample on host memory: a stable sort of the 63-bit keys, then the runs in order; K_out [1] */
+int hm_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, const double* grid, float* points_out,
+                        uint8_t* colors_out, int32_t* counts_out, int64_t* K_out);
+/* keys [n] of points [n, 3] as uint64 */
+void hm_voxel_keys(const float* points, int64_t n, const double* grid, uint64_t* keys);
+
 #ifdef __cplusplus
 }
 #endif

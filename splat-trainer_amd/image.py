@@ -21,8 +21,10 @@ from . import _lib
 HOST_LIB_PATH = os.path.join(_lib.PKG_DIR, "libgsr_hostmath.so")
 HOST_HEADER_PATH = os.path.join(_lib.PKG_DIR, "csrc", "hostmath_shim.h")
 MAX_SIDE = 32768
-# what the package itself calls of the host library: the area resize, and the undistortion (undistort.py)
-HOST_FUNCTIONS = ("hm_image_resize_area_u8", "hm_undistort_map", "hm_undistort_points", "hm_image_remap_u8")
+# what the package itself calls of the host library: the area resize, the undistortion (undistort.py) and the depth
+# fusion (fusion.py)
+HOST_FUNCTIONS = ("hm_image_resize_area_u8", "hm_undistort_map", "hm_undistort_points", "hm_image_remap_u8",
+                  "hm_fuse_check", "hm_fuse_mask", "hm_fuse_emit", "hm_voxel_downsample")
 _host_lib = None
 _lock = threading.Lock()
 

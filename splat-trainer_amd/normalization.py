@@ -8,7 +8,7 @@ native ``knn`` leaves the point itself out, so that column is the ``k - 1``-th n
 point itself, distance 0).  ``knn`` holds at most 16 neighbours: ``k`` above 17 raises (the reference's default
 ``normalize_knn = 20`` is out of reach; there is no second path).  Points on the HIP device only.
 
-``transform_cloud`` is left out with ``PointCloud``.
+``transform_cloud`` takes a ``dataset.PointCloud``; that module imports this one, so the class is looked up on the call.
 """
 from __future__ import annotations
 
@@ -51,6 +51,11 @@ class Normalization:
     while len(t.shape) < len(points.shape):
       t = t.unsqueeze(0)
     return self.scaling * (points + t)
+
+  def transform_cloud(self, cloud):
+    """A ``PointCloud`` with the points transformed and the colours as they are."""
+    from .dataset import PointCloud
+    return PointCloud(self.transform_points(cloud.points), cloud.colors)
 
   def transform_rigid(self, rigid: torch.Tensor) -> torch.Tensor:
     r, t = split_rt(rigid)

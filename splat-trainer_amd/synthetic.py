@@ -79,3 +79,28 @@ def scene_b(n: int, width: int, height: int, sh_degree: int = 3, seed: int = 1, 
     cams.append(CameraParams(T_camera_world=T, projection=torch.tensor([fx, fy, cx, cy]),
                              image_size=(width, height), near_plane=0.1, far_plane=100.0))
   return Gaussians3D(position.float(), rotation.float(), log_scaling.float(), alpha_logit.float(), feature.float()), cams
+
+
+def plane(width: int, height: int, z: float = 4.0, spacing: float = 0.125, half_extent: float = 4.0, seed: int = 2,
+          shifts: Tuple[float, ...] = (0.0, 0.25, 0.5)) -> Tuple[Gaussians3D, List[CameraParams]]:
+  """Scene C "plane" (depth fusion): a square grid of opaque isotropic splats on the plane z = ``z`` with a colour per
+  point (feature (N, 3)), and cameras of identity rotation at (shift, 0, 0), fov_x 60 deg, that look at it.  Every
+  median depth is that of a splat centre, so the views see the same surface."""
+  gen = torch.Generator().manual_seed(seed)
+  steps = int(round(2 * half_extent / spacing)) + 1
+  axis = torch.linspace(-half_extent, half_extent, steps)
+  gy, gx = torch.meshgrid(axis, axis, indexing="ij")
+  n = steps * steps
+  position = torch.stack([gx.reshape(-1), gy.reshape(-1), torch.full((n,), float(z))], dim=1)
+  log_scaling = torch.full((n, 3), math.log(0.6 * spacing))
+  rotation = torch.tensor([0.0, 0.0, 0.0, 1.0]).repeat(n, 1)
+  alpha_logit = torch.full((n, 1), 6.0)
+  feature = torch.rand(n, 3, generator=gen)
+  fx = fy = width / (2.0 * math.tan(math.radians(30.0)))
+  cams = []
+  for shift in shifts:
+    T = torch.eye(4)
+    T[0, 3] = -float(shift)
+    cams.append(CameraParams(T_camera_world=T, projection=torch.tensor([fx, fy, width / 2.0, height / 2.0]),
+                             image_size=(width, height), near_plane=0.1, far_plane=100.0))
+  return Gaussians3D(position.float(), rotation.float(), log_scaling.float(), alpha_logit.float(), feature.float()), cams

@@ -40,8 +40,9 @@ from .cloud_init import CloudInitConfig, get_initial_gaussians, to_pointcloud
 from .compat import count_nonfinite
 from .controller import ControllerConfig, Progress, eval_schedule
 from .data_types import CameraParams, Gaussians3D, Rendering
-from .dataset import Dataset, ImageView
+from .dataset import Dataset, ImageView, PointCloud
 from .evaluation import Evaluation
+from .fusion import FusionConfig, fuse_scene
 from .histogram import tensor_histogram
 from .logger import Logger, LoggerWithState
 from .loss import reference_loss
@@ -325,6 +326,24 @@ class Trainer:
     train_idx = self._train_idx(self.camera_table).tolist()
     cameras = [self.camera_params(i) for i in train_idx]
     return self.unnormalize.transform_gaussians(self.scene.to_sh_gaussians(cameras, train_idx, method="lstsq"))
+
+  def fused_cloud(self, config: Optional[FusionConfig] = None, which: str = "train") -> PointCloud:
+    """The dense cloud fused from the median depth maps of the ``which`` = "train" or "val" views (fusion.fuse_scene),
+    in the original coordinates."""
+    if which not in ("train", "val"):
+      raise ValueError(f"which must be 'train' or 'val', got {which!r}")
+    views = self.dataset.train(shuffle=False) if which == "train" else self.dataset.val()
+    indexes = [int(v.image_idx) for v in views]
+    if not indexes:
+      raise ValueError(f"the dataset has no {which} views")
+    render = lambda camera, idx: self.render(camera, idx, render_median_depth=True)      # noqa: E731
+    cloud, _ = fuse_scene(render, [self.camera_params(i) for i in indexes], config or FusionConfig(), indexes)
+    return self.unnormalize.transform_cloud(cloud)
+
+  def write_fused_cloud(self, path, config: Optional[FusionConfig] = None, which: str = "train") -> PointCloud:
+    cloud = self.fused_cloud(config, which)
+    cloud.save_ply(path)
+    return cloud
 
   def load_cloud(self) -> Gaussians3D:
     paths = self.paths()
