@@ -110,6 +110,8 @@ __global__ __launch_bounds__(BG_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) v
                                                                  float* __restrict__ d_rgb,
                                                                  float* __restrict__ slots) {
   extern __shared__ float cols[];
+  // gsr_block_rows_handoff's layout, kept here: through the helper this kernel's schedule changes, and its float sums
+  // pin it to identical code
   __shared__ float s_rows[16][BG_ACC];        // 4 waves x 4 rows of 16 lanes
   const BgCell b = bg_stage(grid, sh, cols);
   __syncthreads();
@@ -228,15 +230,9 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_tv_kernel(const float* __restrict
       }
     }
   }
-  __shared__ float s_wave[BG_BLOCK / 64];
-  v = gsr_wave_sum_to_lane63(v);
-  if (gsr_lane() == 63) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.f;
-    for (int i = 0; i < BG_BLOCK / 64; ++i) a += s_wave[i];
-    partials[blockIdx.y * gridDim.x + blockIdx.x] = a;
-  }
+  const GsrWaves<float>& s_wave = gsr_block_handoff<63>(gsr_wave_sum_to_lane63(v));
+  if (threadIdx.x == 0)
+    partials[blockIdx.y * gridDim.x + blockIdx.x] = (((0.f + s_wave[0]) + s_wave[1]) + s_wave[2]) + s_wave[3];
 }
 
 // One block: partials in order (thread t: t, t + 256, ...), then the block sum; tv_out[0] = scale * total.
@@ -244,15 +240,8 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_tv_finish_kernel(const float* __r
                                                                  float* __restrict__ tv_out) {
   float v = 0.f;
   for (int i = threadIdx.x; i < n; i += BG_BLOCK) v += partials[i];
-  __shared__ float s_wave[BG_BLOCK / 64];
-  v = gsr_wave_sum_to_lane63(v);
-  if (gsr_lane() == 63) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.f;
-    for (int i = 0; i < BG_BLOCK / 64; ++i) a += s_wave[i];
-    tv_out[0] = scale * a;
-  }
+  const GsrWaves<float>& s_wave = gsr_block_handoff<63>(gsr_wave_sum_to_lane63(v));
+  if (threadIdx.x == 0) tv_out[0] = scale * ((((0.f + s_wave[0]) + s_wave[1]) + s_wave[2]) + s_wave[3]);
 }
 
 void bg_tv_blocks(int64_t N, int L, int GH, int GW, unsigned& bx, unsigned& by) {

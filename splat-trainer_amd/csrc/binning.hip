@@ -160,10 +160,7 @@ __global__ __launch_bounds__(256) void tile_count_kernel(const float* __restrict
   if (k < M) count[k] = n;
   if (block_sums) {
     // also leaves the block's total for offsets_from_sums_kernel (the scan's reduce pass, folded in here)
-    __shared__ uint32_t s_wave[4];
-    n = gsr_wave_sum_u32(n);
-    if (gsr_lane() == 0) s_wave[threadIdx.x >> 6] = n;
-    __syncthreads();
+    const GsrWaves<uint32_t>& s_wave = gsr_block_handoff(gsr_wave_sum_u32(n));
     if (threadIdx.x == 0) block_sums[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
   }
 }
@@ -176,8 +173,8 @@ __global__ __launch_bounds__(256) void offsets_from_sums_kernel(const uint32_t* 
                                                                 uint32_t* __restrict__ offsets,
                                                                 uint32_t* __restrict__ total_out,
                                                                 uint32_t* __restrict__ overflow) {
-  __shared__ uint32_t s_wave[4], s_before[4];
-  __shared__ float s_f[4];
+  __shared__ uint32_t s_wave[4], s_before[4];   // (its own hand-off: through gsr_block_handoff the schedule changes,
+  __shared__ float s_f[4];                      // and the float shadow sum pins this kernel to identical code)
   const int lane = gsr_lane(), w = (int)(threadIdx.x >> 6);
   const uint32_t base = blockIdx.x * 4096u + threadIdx.x * 16u;
   uint32_t v[16], sum = 0u;

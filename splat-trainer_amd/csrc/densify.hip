@@ -90,28 +90,24 @@ __global__ __launch_bounds__(DN_THREADS) void select_equal_count_kernel(const fl
                                                                         int descending,
                                                                         const SelectState* __restrict__ st,
                                                                         uint32_t* __restrict__ block_counts) {
-  __shared__ uint32_t s_w[4];
   const int64_t i = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
   const bool eq = i < N && select_key(values[i], descending != 0) == st->prefix;
-  const uint64_t b = __ballot(eq);
-  if (gsr_lane() == 0) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const uint32_t count = gsr_block_count(eq);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = count;
 }
 
 __global__ __launch_bounds__(DN_THREADS) void select_mask_kernel(const float* __restrict__ values, int64_t N,
                                                                  int descending, const SelectState* __restrict__ st,
                                                                  const uint32_t* __restrict__ block_offsets,
                                                                  uint8_t* __restrict__ mask_out) {
-  __shared__ uint32_t s_w[4];
   const int64_t i = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
   const uint32_t thr = st->prefix, take = st->remaining;
   const uint32_t k = i < N ? select_key(values[i], descending != 0) : 0xffffffffu;
   const bool eq = i < N && k == thr;
+  // gsr_block_rank's sum with the block's offset in front, read behind the barrier
   const uint64_t b = __ballot(eq);
   const int wave = threadIdx.x >> 6;
-  if (gsr_lane() == 0) s_w[wave] = (uint32_t)__builtin_popcountll(b);
-  __syncthreads();
+  const GsrWaves<uint32_t>& s_w = gsr_block_handoff((uint32_t)__builtin_popcountll(b), wave);
   uint32_t before = block_offsets[blockIdx.x] + (uint32_t)gsr_mbcnt(b);
   for (int w = 0; w < wave; ++w) before += s_w[w];
   if (i < N) mask_out[i] = (k < thr || (eq && before < take)) ? 1 : 0;   // equal entries: lowest indexes first
@@ -121,12 +117,9 @@ __global__ __launch_bounds__(DN_THREADS) void select_mask_kernel(const float* __
 static_assert(DN_THREADS == GSR_COMPACT_BLOCK, "the block offsets count DN_THREADS rows: the ABI states the number");
 __global__ __launch_bounds__(DN_THREADS) void compact_count_kernel(const uint8_t* __restrict__ keep, int64_t N,
                                                                    uint32_t* __restrict__ block_counts) {
-  __shared__ uint32_t s_w[4];
   const int64_t i = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
-  const uint64_t b = __ballot(i < N && keep[i] != 0);
-  if (gsr_lane() == 0) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const uint32_t count = gsr_block_count(i < N && keep[i] != 0);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = count;
 }
 
 struct ColumnSet {
@@ -159,26 +152,19 @@ __global__ __launch_bounds__(DN_THREADS) void compact_gather_kernel(const uint8_
     }
     return;
   }
-  __shared__ uint32_t s_w[4];
   __shared__ uint16_t s_src[DN_THREADS];
   const int64_t row0 = (int64_t)blockIdx.x * DN_THREADS;
   const int64_t i = row0 + threadIdx.x;
   const bool k = i < N && keep[i] != 0;
-  const uint64_t b = __ballot(k);
-  const int wave = threadIdx.x >> 6;
-  if (gsr_lane() == 0) s_w[wave] = (uint32_t)__builtin_popcountll(b);
-  __syncthreads();
-  uint32_t rank = (uint32_t)gsr_mbcnt(b);
-  for (int w = 0; w < wave; ++w) rank += s_w[w];
-  const uint32_t kept = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  if (k) s_src[rank] = (uint16_t)threadIdx.x;
+  const GsrBlockRank rank = gsr_block_rank(k);
+  if (k) s_src[rank.before] = (uint16_t)threadIdx.x;
   __syncthreads();
   const int64_t base = block_offsets[blockIdx.x];
   for (int c = 0; c < cs.n; ++c) {
     const int w = cs.col[c].width_dwords;
     const word* src = reinterpret_cast<const word*>(cs.col[c].src) + row0 * w;
     word* dst = reinterpret_cast<word*>(cs.col[c].dst) + base * w;
-    const uint32_t total = kept * (uint32_t)w;
+    const uint32_t total = rank.total * (uint32_t)w;
     if (w == 1) {
       for (uint32_t e = threadIdx.x; e < total; e += DN_THREADS) dst[e] = src[s_src[e]];
     } else {

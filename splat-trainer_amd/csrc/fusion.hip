@@ -68,7 +68,6 @@ __global__ __launch_bounds__(FB) void fuse_emit_kernel(const float* __restrict__
                                                        int32_t max_violate, const uint32_t* __restrict__ block_offsets,
                                                        int64_t base, int64_t capacity, float* __restrict__ points_out,
                                                        uint8_t* __restrict__ colors_out, uint8_t* __restrict__ agree_out) {
-  __shared__ uint32_t s_w[FB / 64];
   const uint32_t px = blockIdx.x * FB + threadIdx.x;      // n_px <= 2^30
   double d = 0.0;
   uint32_t agree = 0;
@@ -78,12 +77,7 @@ __global__ __launch_bounds__(FB) void fuse_emit_kernel(const float* __restrict__
     agree = counts[2 * (int64_t)px];
     k = gsr_fuse_keep(d, agree, counts[2 * (int64_t)px + 1], min_agree, max_violate);
   }
-  const uint64_t b = __ballot(k);
-  const int wave = (int)(threadIdx.x >> 6);
-  if (gsr_lane() == 0) s_w[wave] = (uint32_t)__builtin_popcountll(b);
-  __syncthreads();
-  uint32_t rank = (uint32_t)gsr_mbcnt(b);
-  for (int w = 0; w < wave; ++w) rank += s_w[w];
+  const uint32_t rank = gsr_block_rank(k).before;
   const int64_t row = base + (int64_t)block_offsets[blockIdx.x] + rank;
   if (!k || row >= capacity) return;
   const uint32_t i = px / Wr, j = px - i * Wr;

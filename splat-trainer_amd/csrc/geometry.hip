@@ -158,21 +158,10 @@ constexpr int CAM_PARTIAL_FLOATS = 20;
 constexpr int CAM_POS_AT = GSR_CAM_GRAD_FLOATS;    // columns 16..18: dL/d(camera position)
 
 __device__ __forceinline__ void gsr_block_cam_sum(float (&v)[CAM_PARTIAL_FLOATS], float* __restrict__ out) {
-  __shared__ float s_rows[16][CAM_PARTIAL_FLOATS];  // 4 waves x 4 rows of 16 lanes
-  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
 #pragma unroll
   for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) v[j] = gsr_row_sum_to_lane15(v[j]);
-  if ((lane & 15) == 15) {
-#pragma unroll
-    for (int j = 0; j < CAM_PARTIAL_FLOATS; ++j) s_rows[4 * wave + (lane >> 4)][j] = v[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < CAM_PARTIAL_FLOATS) {
-    float a = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a += s_rows[r][threadIdx.x];
-    out[threadIdx.x] = a;
-  }
+  const GsrRows<CAM_PARTIAL_FLOATS>& s_rows = gsr_block_rows_handoff(v);
+  if (threadIdx.x < CAM_PARTIAL_FLOATS) out[threadIdx.x] = gsr_rows_sum(s_rows, threadIdx.x);
 }
 
 // One block: rows of partials in order (thread t: rows t, t + 256, ...), then the block sum as above.  Tcw given: writes

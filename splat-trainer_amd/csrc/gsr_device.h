@@ -94,6 +94,107 @@ __device__ __forceinline__ uint64_t gsr_wave_sum_u64(uint64_t v) {
   return v;
 }
 
+// ---- Block-wide hand-offs: a value every wave has agreed on goes through a small LDS array to the whole block.
+// The helpers own their array as a function-local __shared__, one per instantiation, so a kernel that calls a helper
+// twice REUSES ONE ARRAY: a __syncthreads() must stand between the last read of one call's values and the publish of the
+// next call.  The call site places that barrier (only gsr_block_scan_excl, whose reads end inside it, brings its own).
+// None of them adds floating-point values: the association order of a float sum is part of the stage contracts
+// ("Block-wide sums, ranks and scans"), so every site writes its sum as one visible expression.
+// A caller that uses the wave index itself passes it as `wave`: a helper is simplified before it is inlined, and a
+// second threadIdx.x >> 6 in here would be folded into the store's address apart from the caller's (other code).
+template <typename T, int WAVES = 4>
+using GsrWaves = T[WAVES];
+
+// One value per wave -> the waves' values, readable by every thread.  Lane LANE of every wave publishes (0, or 63, where
+// gsr_wave_sum_to_lane63 and the inclusive wave scans leave the wave's total), then the block's barrier.
+template <int LANE = 0, int WAVES = 4, typename T>
+__device__ __forceinline__ const GsrWaves<T, WAVES>& gsr_block_handoff(T v, int wave = threadIdx.x >> 6) {
+  __shared__ T s_w[WAVES];
+  if (gsr_lane() == LANE) s_w[wave] = v;
+  __syncthreads();
+  return s_w;
+}
+
+// Two values per wave under ONE barrier.
+template <typename A, typename B, int WAVES>
+struct GsrWavesPair {
+  const GsrWaves<A, WAVES>& a;
+  const GsrWaves<B, WAVES>& b;
+};
+
+template <int LANE = 0, int WAVES = 4, typename A, typename B>
+__device__ __forceinline__ GsrWavesPair<A, B, WAVES> gsr_block_handoff(A a, B b, int wave = threadIdx.x >> 6) {
+  __shared__ A s_a[WAVES];
+  __shared__ B s_b[WAVES];
+  if (gsr_lane() == LANE) { s_a[wave] = a; s_b[wave] = b; }
+  __syncthreads();
+  return {s_a, s_b};
+}
+
+// flag -> before: set flags in the threads below this one; total: set flags of the block.  256 threads.
+struct GsrBlockRank {
+  uint32_t before, total;
+};
+
+__device__ __forceinline__ GsrBlockRank gsr_block_rank(bool flag) {
+  const uint64_t b = __ballot(flag);
+  const int wave = threadIdx.x >> 6;
+  const GsrWaves<uint32_t>& w = gsr_block_handoff((uint32_t)__builtin_popcountll(b), wave);
+  GsrBlockRank r;
+  r.before = (uint32_t)gsr_mbcnt(b);
+  for (int i = 0; i < wave; ++i) r.before += w[i];
+  r.total = w[0] + w[1] + w[2] + w[3];
+  return r;
+}
+
+__device__ __forceinline__ uint32_t gsr_block_count(bool flag) {   // set flags of the block, in every thread
+  const GsrWaves<uint32_t>& w = gsr_block_handoff((uint32_t)__builtin_popcountll(__ballot(flag)));
+  return w[0] + w[1] + w[2] + w[3];
+}
+
+// Block-wide exclusive scan of one value per thread (256 threads); returns the exclusive prefix, the block's total in
+// *total_out (the same in every thread).  Ends with a barrier: it may be called again at once.
+__device__ __forceinline__ uint32_t gsr_block_scan_excl(uint32_t v, uint32_t* total_out) {
+  const int wave = threadIdx.x >> 6;
+  const uint32_t incl = gsr_wave_scan_incl_u32(v);
+  const GsrWaves<uint32_t>& s_wave = gsr_block_handoff<63>(incl, wave);
+  uint32_t base = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    uint32_t c = s_wave[w];
+    if (w < wave) base += c;
+    total += c;
+  }
+  __syncthreads();
+  *total_out = total;
+  return base + incl - v;
+}
+
+// The 16-lane form (256 threads = 16 DPP rows): lane 15 of every row stores its K values (row sums, from
+// gsr_row_sum_to_lane15 of gsr_dpp_reduce.h), barrier; gsr_rows_sum adds column j over the rows in row order, from 0.
+template <int K>
+using GsrRows = float[16][K];
+
+template <int K>
+__device__ __forceinline__ const GsrRows<K>& gsr_block_rows_handoff(const float (&v)[K]) {
+  __shared__ float s_rows[16][K];                 // 4 waves x 4 rows of 16 lanes
+  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
+  if ((lane & 15) == 15) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) s_rows[4 * wave + (lane >> 4)][j] = v[j];
+  }
+  __syncthreads();
+  return s_rows;
+}
+
+template <int K>
+__device__ __forceinline__ float gsr_rows_sum(const GsrRows<K>& rows, int j) {
+  float a = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) a += rows[r][j];
+  return a;
+}
+
 // Depth -> sortable u32 key.  The IEEE bit pattern of a positive float is monotone (sign bit set keeps negatives, which
 // the cull never lets through, below); `bias` = key of the near plane makes the keys of a frame start at 0, so that
 // they span only bits(far) - bits(near) (27 bits for 0.1 .. 100) and the radix sort needs fewer passes.  Depths outside

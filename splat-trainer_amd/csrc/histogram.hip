@@ -126,7 +126,6 @@ __device__ __forceinline__ double wave_sum_f64(double v) {     // the fixed xor 
 
 template <int VEC>
 __global__ __launch_bounds__(HB) void hist_range_kernel(HistIn in, void* __restrict__ workspace) {
-  __shared__ uint32_t s_min[HB_WAVES], s_max[HB_WAVES];
   uint32_t min_c = 0u, max_k = 0u;
   hist_for_each<VEC>(in, [&](int cls, float t) {
     if (cls == GSR_HIST_KEPT) {
@@ -137,16 +136,12 @@ __global__ __launch_bounds__(HB) void hist_range_kernel(HistIn in, void* __restr
   });
   min_c = wave_max_u32(min_c);
   max_k = wave_max_u32(max_k);
-  if ((threadIdx.x & 63) == 0) {
-    s_min[threadIdx.x >> 6] = min_c;
-    s_max[threadIdx.x >> 6] = max_k;
-  }
-  __syncthreads();
+  const auto s = gsr_block_handoff(min_c, max_k);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int w = 1; w < HB_WAVES; ++w) {
-      min_c = s_min[w] > min_c ? s_min[w] : min_c;
-      max_k = s_max[w] > max_k ? s_max[w] : max_k;
+      min_c = s.a[w] > min_c ? s.a[w] : min_c;
+      max_k = s.b[w] > max_k ? s.b[w] : max_k;
     }
     if (max_k != 0u) {                                      // (a key is never 0: a block that kept nothing adds nothing)
       HistHeader* header = hist_replica(workspace, blockIdx.x % HIST_REPLICAS);

@@ -15,34 +15,11 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;   // 4096 elements per block
 
-// block-wide exclusive scan of one value per thread (256 threads = 4 waves); returns exclusive prefix,
-// total in *total_out (same for all threads).
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* total_out) {
-  __shared__ uint32_t s_wave[4];
-  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
-  uint32_t incl = gsr_wave_scan_incl_u32(v);
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    uint32_t c = s_wave[w];
-    if (w < wave) base += c;
-    total += c;
-  }
-  __syncthreads();
-  *total_out = total;
-  return base + incl - v;
-}
-
 // Overflow guard of the u32 scans: every kernel that forms a sum also forms it in float (range, not precision) and
 // raises *overflow when prefix + total reaches 2^31 -- sums the 32-bit index arithmetic downstream cannot hold anyway.
 // A u32 wrap is always preceded by such a crossing, at whichever level of the scan it happens.
 __device__ __forceinline__ void flag_if_large(float mine, uint32_t prefix, uint32_t* overflow) {
-  __shared__ float s_f[4];
-  const float w = gsr_wave_sum(mine);
-  if (gsr_lane() == 0) s_f[threadIdx.x >> 6] = w;
-  __syncthreads();
+  const GsrWaves<float>& s_f = gsr_block_handoff(gsr_wave_sum(mine));
   if (threadIdx.x == 0 && (float)prefix + ((s_f[0] + s_f[1]) + (s_f[2] + s_f[3])) >= 2147000000.f) *overflow = 1u;
 }
 
@@ -60,7 +37,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const uint32_
     fsum += (float)v;
   }
   uint32_t total;
-  block_scan_excl(sum, &total);
+  gsr_block_scan_excl(sum, &total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
   if (overflow) flag_if_large(fsum, 0u, overflow);
 }
@@ -86,7 +63,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(const uint32_t
     fsum += (float)v[i];
   }
   uint32_t total;
-  uint32_t excl = block_scan_excl(sum, &total);
+  uint32_t excl = gsr_block_scan_excl(sum, &total);
   uint32_t boff = 0u;
   if (SELF) {
     uint32_t before = 0;
@@ -96,7 +73,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(const uint32_t
       before += b;
       fbefore += (float)b;
     }
-    block_scan_excl(before, &boff);                          // boff = total over the block = sum of all earlier blocks
+    gsr_block_scan_excl(before, &boff);                         // boff = total over the block = sum of all earlier blocks
     fsum += fbefore;                                         // flag_if_large sums fsum over the block
   } else if (block_offsets) {
     boff = block_offsets[blockIdx.x];
@@ -214,10 +191,9 @@ __global__ __launch_bounds__(RS_THREADS) void rs_hist_kernel(const uint32_t* __r
 __global__ __launch_bounds__(RS_THREADS) void rs_digit_scan_kernel(const uint32_t* __restrict__ hist,
                                                                    uint32_t* __restrict__ offs, uint32_t num_blocks,
                                                                    uint32_t* __restrict__ digit_total) {
-  __shared__ uint32_t s_wave[4];
   __shared__ uint32_t s_carry;
   const uint32_t d = blockIdx.x;
-  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
+  const int wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) s_carry = 0u;
   __syncthreads();
   const uint32_t* row = hist + (size_t)d * num_blocks;
@@ -226,8 +202,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_digit_scan_kernel(const uint32_
     const uint32_t b = b0 + threadIdx.x;
     const uint32_t v = (b < num_blocks) ? row[b] : 0u;
     const uint32_t incl = gsr_wave_scan_incl_u32(v);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
+    const GsrWaves<uint32_t>& s_wave = gsr_block_handoff<63>(incl, wave);
     uint32_t wbase = 0, total = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -298,7 +273,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
   __shared__ uint32_t s_start[BINS];          // first image slot of each digit
   __shared__ uint32_t s_goff[BINS];           // global slot of the digit's first element of this block
   __shared__ uint32_t s_slot[4][BINS];        // per wave: digit counts of its quarter, then its running image slot per digit
-  __shared__ uint32_t s_wave[4], s_wave_t[4];
   __shared__ uint32_t s_key[TILE];
   __shared__ uint32_t s_val[TILE];
   __shared__ uint32_t s_val2[TWO ? TILE : 1];
@@ -330,12 +304,11 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter_kernel(const uint32_t* 
       here_t += t[k];
     }
     const uint32_t incl = gsr_wave_scan_incl_u32(here), incl_t = gsr_wave_scan_incl_u32(here_t);
-    if (lane == 63) { s_wave[wave] = incl; s_wave_t[wave] = incl_t; }
-    __syncthreads();
+    const auto s_wave = gsr_block_handoff<63>(incl, incl_t, wave);
     uint32_t at = incl - here, gbase = incl_t - here_t;
 #pragma unroll
     for (int w = 0; w < 4; ++w)
-      if (w < wave) { at += s_wave[w]; gbase += s_wave_t[w]; }
+      if (w < wave) { at += s_wave.a[w]; gbase += s_wave.b[w]; }
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const uint32_t d = PER * threadIdx.x + k;

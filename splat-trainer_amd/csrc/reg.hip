@@ -57,36 +57,23 @@ __device__ __forceinline__ RegRow reg_row(const GsrReg& a, int64_t i, float vis)
 }
 
 // block sum in a fixed order: DPP row sums (gsr_dpp_reduce.h), then the block's 16 rows of 16 lanes in order through
-// LDS; valid in thread 0
-__device__ __forceinline__ float reg_block_sum(float v, float* s_rows) {
-  v = gsr_row_sum_to_lane15(v);
-  __syncthreads();                               // s_rows may still be read from the previous sum
-  if ((threadIdx.x & 15) == 15) s_rows[threadIdx.x >> 4] = v;
+// LDS; valid in thread 0.  The four sums of a kernel share one hand-off array: the barrier keeps a publish off the
+// previous sum's reads.
+__device__ __forceinline__ float reg_rows_sum(float v) {
+  const float row[1] = {gsr_row_sum_to_lane15(v)};
   __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int r = 0; r < REG_BLOCK / 16; ++r) t += s_rows[r];
-  }
-  return t;
+  const GsrRows<1>& s_rows = gsr_block_rows_handoff(row);
+  return threadIdx.x == 0 ? gsr_rows_sum(s_rows, 0) : 0.f;
 }
 
-__device__ __forceinline__ uint32_t reg_block_count(uint32_t v, uint32_t* s_wave) {
+__device__ __forceinline__ uint32_t reg_count(uint32_t v) {      // the block's count; valid in thread 0
   v = gsr_wave_sum_u32(v);
   __syncthreads();
-  if (gsr_lane() == 0) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t t = 0;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < REG_BLOCK / 64; ++w) t += s_wave[w];
-  }
-  return t;
+  const GsrWaves<uint32_t>& s_wave = gsr_block_handoff(v);
+  return threadIdx.x == 0 ? s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3] : 0u;
 }
 
 __global__ __launch_bounds__(REG_BLOCK) void reg_fwd_kernel(GsrReg a, float* __restrict__ slots) {
-  __shared__ float s_rows[REG_BLOCK / 16];
-  __shared__ uint32_t s_count[REG_BLOCK / 64];
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   uint32_t n = 0;
   for (int64_t i = (int64_t)blockIdx.x * REG_BLOCK + threadIdx.x; i < a.M; i += (int64_t)gridDim.x * REG_BLOCK) {
@@ -102,10 +89,10 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_fwd_kernel(GsrReg a, float* __r
   float* slot = slots + (int64_t)blockIdx.x * REG_SLOT;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const float t = reg_block_sum(acc[k], s_rows);
+    const float t = reg_rows_sum(acc[k]);
     if (threadIdx.x == 0) slot[k] = t;
   }
-  const uint32_t c = reg_block_count(n, s_count);
+  const uint32_t c = reg_count(n);
   if (threadIdx.x == 0) slot[4] = __uint_as_float(c);
 }
 
@@ -113,8 +100,6 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_fwd_kernel(GsrReg a, float* __r
 __global__ __launch_bounds__(REG_BLOCK) void reg_finish_kernel(const float* __restrict__ slots, int n_slots, GsrReg a,
                                                                 float* __restrict__ loss_out,
                                                                 float* __restrict__ terms_out) {
-  __shared__ float s_rows[REG_BLOCK / 16];
-  __shared__ uint32_t s_count[REG_BLOCK / 64];
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   uint32_t n = 0;
   for (int b = threadIdx.x; b < n_slots; b += REG_BLOCK) {
@@ -125,8 +110,8 @@ __global__ __launch_bounds__(REG_BLOCK) void reg_finish_kernel(const float* __re
   }
   float total[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) total[k] = reg_block_sum(acc[k], s_rows);
-  const uint32_t count = reg_block_count(n, s_count);
+  for (int k = 0; k < 4; ++k) total[k] = reg_rows_sum(acc[k]);
+  const uint32_t count = reg_count(n);
   if (threadIdx.x == 0) {
     float loss = 0.f;
 #pragma unroll

@@ -60,23 +60,22 @@ __global__ __launch_bounds__(RL_THREADS) void reloc_block_totals_kernel(const ui
 
 __global__ __launch_bounds__(RL_SCAN_THREADS) void reloc_scan_kernel(uint64_t* __restrict__ block_incl, int64_t blocks,
                                                                      uint64_t* __restrict__ total_out) {
-  __shared__ uint64_t s_wave[RL_SCAN_THREADS / GSR_WAVE];
-  const int lane = gsr_lane(), wave = threadIdx.x >> 6;
+  constexpr int WAVES = RL_SCAN_THREADS / GSR_WAVE;
+  const int wave = threadIdx.x >> 6;
   uint64_t carry = 0;
   for (int64_t base = 0; base < blocks; base += RL_SCAN_THREADS) {
     const int64_t i = base + threadIdx.x;
     const uint64_t incl = gsr_wave_scan_incl_u64(i < blocks ? block_incl[i] : 0ull);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
+    const GsrWaves<uint64_t, WAVES>& s_wave = gsr_block_handoff<63, WAVES>(incl, wave);
     uint64_t before = carry, chunk = 0;
 #pragma unroll
-    for (int w = 0; w < RL_SCAN_THREADS / GSR_WAVE; ++w) {
+    for (int w = 0; w < WAVES; ++w) {
       before += w < wave ? s_wave[w] : 0ull;
       chunk += s_wave[w];
     }
     if (i < blocks) block_incl[i] = before + incl;
     carry += chunk;
-    __syncthreads();                         // s_wave is written again in the next pass
+    __syncthreads();                         // the hand-off array is written again in the next pass
   }
   if (threadIdx.x == 0) *total_out = carry;
 }

@@ -32,11 +32,9 @@ __device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* s_red) {
-  v = gsr_wave_sum(v);                                   // fixed-order DPP tree
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
+// the SSIM sums' block total, in every thread: the fixed-order DPP tree per wave, then the waves left to right
+__device__ __forceinline__ float ssim_block_sum(float v) {
+  const GsrWaves<float>& s_red = gsr_block_handoff(gsr_wave_sum(v));
   return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
@@ -51,7 +49,6 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
                                                        float lo = -INFINITY, float hi = INFINITY) {
   __shared__ float s_x[IN][IN + 1], s_y[IN][IN + 1];
   __shared__ float s_h[5][IN][TS + 1];
-  __shared__ float s_red[4];
   const int plane = blockIdx.z, b = plane / C, c = plane % C;
   const int x0 = blockIdx.x * TS, y0 = blockIdx.y * TS;
   const float* p1 = img1 + b * st1.sB + c * st1.sC;
@@ -145,7 +142,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
       dm_dmu1[oidx] = sc * d_mu1; dm_dm11[oidx] = sc * d_m11; dm_dm12[oidx] = sc * d_m12;
     }
   }
-  const float total = block_sum_256(local, s_red);
+  const float total = ssim_block_sum(local);
   if (threadIdx.x == 0)
     block_sums[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
 }
@@ -153,10 +150,9 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
 // one block adds the per-block partials in index order (fixed association) and scales by 1/count
 __global__ __launch_bounds__(256) void ssim_finish_kernel(const float* __restrict__ block_sums, int n, float inv_count,
                                                           float* __restrict__ out) {
-  __shared__ float s_red[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) acc += block_sums[i];
-  const float total = block_sum_256(acc, s_red);
+  const float total = ssim_block_sum(acc);
   if (threadIdx.x == 0) out[0] = total * inv_count;
 }
 
@@ -248,7 +244,6 @@ template <int KIND>   // 0: squared error, 1: absolute error
 __global__ __launch_bounds__(PL_THREADS) void pixel_loss_fwd_kernel(const float* __restrict__ x,
                                                                     const float* __restrict__ t, int64_t n, float lo,
                                                                     float hi, float* __restrict__ block_sums) {
-  __shared__ float s_w[PL_THREADS / 64];
   float acc = 0.f;
   for (int64_t i = ((int64_t)blockIdx.x * PL_THREADS + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * PL_THREADS * 4) {
     float xv[4], tv[4];
@@ -265,20 +260,15 @@ __global__ __launch_bounds__(PL_THREADS) void pixel_loss_fwd_kernel(const float*
       acc += KIND == 0 ? d * d : fabsf(d);
     }
   }
-  acc = gsr_wave_sum(acc);
-  if (gsr_lane() == 0) s_w[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const GsrWaves<float>& s_w = gsr_block_handoff(gsr_wave_sum(acc));
   if (threadIdx.x == 0) block_sums[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 
 __global__ __launch_bounds__(256) void pixel_loss_finish_kernel(const float* __restrict__ block_sums, int blocks,
                                                                 float inv_n, float* __restrict__ out) {
-  __shared__ float s_w[4];
   float acc = 0.f;
   for (int b = threadIdx.x; b < blocks; b += 256) acc += block_sums[b];
-  acc = gsr_wave_sum(acc);
-  if (gsr_lane() == 0) s_w[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const GsrWaves<float>& s_w = gsr_block_handoff(gsr_wave_sum(acc));
   if (threadIdx.x == 0) out[0] = ((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])) * inv_n;
 }
 
@@ -322,7 +312,6 @@ __global__ __launch_bounds__(256) void msloss_pyramid_kernel(const float* __rest
                                                              const float* __restrict__ target, int C, MsLevels lv,
                                                              float lo, float hi, float* __restrict__ block_l1,
                                                              float* __restrict__ block_mse) {
-  __shared__ float s_a[4], s_b[4];
   const int H = lv.H[0], W = lv.W[0];
   const int bw = (W + 7) / 8, bh = (H + 7) / 8;
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -378,13 +367,10 @@ __global__ __launch_bounds__(256) void msloss_pyramid_kernel(const float* __rest
       }
     }
   }
-  l1 = gsr_wave_sum(l1);
-  mse = gsr_wave_sum(mse);
-  if (gsr_lane() == 0) { s_a[threadIdx.x >> 6] = l1; s_b[threadIdx.x >> 6] = mse; }
-  __syncthreads();
+  const auto s = gsr_block_handoff(gsr_wave_sum(l1), gsr_wave_sum(mse));
   if (threadIdx.x == 0) {
-    block_l1[blockIdx.x] = (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
-    block_mse[blockIdx.x] = (s_b[0] + s_b[1]) + (s_b[2] + s_b[3]);
+    block_l1[blockIdx.x] = (s.a[0] + s.a[1]) + (s.a[2] + s.a[3]);
+    block_mse[blockIdx.x] = (s.b[0] + s.b[1]) + (s.b[2] + s.b[3]);
   }
 }
 
@@ -401,21 +387,20 @@ struct MsSums {
 // metrics_out: [loss, l1, mse, ssim_0 .. ssim_{L-1}]  (what the reference logs with .item(), trainer.py:466-481)
 __global__ __launch_bounds__(256) void msloss_finish_kernel(MsSums sm, int levels, float w_l1, float w_mse, float w_ssim,
                                                             float* __restrict__ metrics_out) {
-  __shared__ float s_red[4];
   float vals[2 + ML_MAX_LEVELS];
   float a = 0.f;
   for (int i = threadIdx.x; i < sm.pix_n; i += 256) a += sm.l1[i];
-  vals[0] = block_sum_256(a, s_red) * sm.pix_inv;
-  __syncthreads();
+  vals[0] = ssim_block_sum(a) * sm.pix_inv;
+  __syncthreads();                              // the sums share one hand-off array: its reads end here
   a = 0.f;
   for (int i = threadIdx.x; i < sm.pix_n; i += 256) a += sm.mse[i];
-  vals[1] = block_sum_256(a, s_red) * sm.pix_inv;
+  vals[1] = ssim_block_sum(a) * sm.pix_inv;
   __syncthreads();
   float ssim_loss = 0.f;
   for (int l = 0; l < levels; ++l) {
     a = 0.f;
     for (int i = threadIdx.x; i < sm.ssim_n[l]; i += 256) a += sm.ssim[l][i];
-    vals[2 + l] = block_sum_256(a, s_red) * sm.ssim_inv[l];
+    vals[2 + l] = ssim_block_sum(a) * sm.ssim_inv[l];
     __syncthreads();
     ssim_loss += 1.f - vals[2 + l];
   }

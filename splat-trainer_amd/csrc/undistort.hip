@@ -53,7 +53,6 @@ struct RemapArgs {
 template <int C>
 __global__ __launch_bounds__(RB) void image_remap_kernel(RemapArgs a) {
   __shared__ uint4 s_words[RM_LDS_WORDS];
-  __shared__ int s_box[4][4];
   __shared__ __attribute__((aligned(16))) uint8_t s_out[4][RM_STRIP];
   const uint8_t* s_bytes = reinterpret_cast<const uint8_t*>(s_words);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -82,14 +81,11 @@ __global__ __launch_bounds__(RB) void image_remap_kernel(RemapArgs a) {
     x_lo = min(x_lo, __shfl_xor(x_lo, o, 64)); x_hi = max(x_hi, __shfl_xor(x_hi, o, 64));
     y_lo = min(y_lo, __shfl_xor(y_lo, o, 64)); y_hi = max(y_hi, __shfl_xor(y_hi, o, 64));
   }
-  if (lane == 0) {
-    s_box[wave][0] = x_lo; s_box[wave][1] = x_hi; s_box[wave][2] = y_lo; s_box[wave][3] = y_hi;
-  }
-  __syncthreads();
+  const GsrWaves<int4>& s_box = gsr_block_handoff(make_int4(x_lo, x_hi, y_lo, y_hi), wave);
 #pragma unroll
   for (int w = 0; w < 4; ++w) {                                        // (one pixel of the workgroup at least is live)
-    x_lo = min(x_lo, s_box[w][0]); x_hi = max(x_hi, s_box[w][1]);
-    y_lo = min(y_lo, s_box[w][2]); y_hi = max(y_hi, s_box[w][3]);
+    x_lo = min(x_lo, s_box[w].x); x_hi = max(x_hi, s_box[w].y);
+    y_lo = min(y_lo, s_box[w].z); y_hi = max(y_hi, s_box[w].w);
   }
   const int seg = (x_hi + 1 - x_lo) * C, nrows = y_hi + 1 - y_lo;      // bytes of a row of the box, and its rows
   const int row_words = (15 + seg + 15) >> 4;                          // with the largest skew in front: >= 1
