@@ -1070,6 +1070,60 @@ int gsr_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, 
                          float* points_out, uint8_t* colors_out, int32_t* counts_out, uint32_t* K_dev, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- TSDF meshing (no reference counterpart): depth maps -> truncated signed distance volume -> surface-nets mesh ----
+ * The arithmetic and the full statement of the contract are csrc/gsr_mesh.h, shared with the host shim: fp64, every
+ * operation rounded on its own, integer accumulation, no atomics.  The volume has nx x ny x nz nodes (at most 2^29), node
+ * (i, j, k) at index (k ny + j) nx + i and position o + idx voxel; grid_host [4] = voxel ox oy oz.  state [6, nodes]
+ * int32 in planes: sum_d, n, colour count, three colour byte sums.  Every double travels in a host array, read before
+ * the call returns.
+ *
+ * gsr_tsdf_integrate adds S <= GSR_FUSE_MAX_SOURCES views in one launch; each thread owns one node.  sources_host [S]
+ * name each view's depth map [H, W] and, optionally, its image [H, W, 3] float (NULL: white);  source_params_host
+ * [S, 16] = the rows of src_t_world (3 x 4), then fx fy cx cy;  tsdf_host [3] = near, trunc, 1 / trunc.  Per node and
+ * source: the projection of gsr_fuse_check; ds = the depth at the pixel, skipped unless valid; diff = ds - p_2, skipped
+ * unless diff >= -trunc; Q = floor(clamp(diff / trunc, -1, 1) 32768 + 0.5) is added to sum_d and 1 to n; where diff <=
+ * trunc the colour count grows by 1 and the colour sums by the pixel's bytes (the rule of gsr_fuse_emit).  A volume
+ * takes at most 65535 views in all (the caller counts them).
+ *   Checked in this order: a negative nx, ny or nz GSR_ERR_INVALID_ARGUMENT; a side or the node count above 2^29
+ *   GSR_ERR_UNSUPPORTED (a side alone, even where another side is 0); S
+ *   outside [1, GSR_FUSE_MAX_SOURCES], a NULL host array, a host value that is not finite, voxel not above 0 (or 1 / voxel
+ *   not finite), trunc or 1 / trunc not above 0 GSR_ERR_INVALID_ARGUMENT; a source side below 0
+ *   GSR_ERR_INVALID_ARGUMENT, above 32768 GSR_ERR_UNSUPPORTED; no node GSR_OK; a NULL state, or a NULL depth of a
+ *   source that has pixels, GSR_ERR_INVALID_ARGUMENT.
+ *
+ * Extraction (surface nets; valid = n >= min_weight, negative = sum_d < 0, m = sum_d / n).  A cell, the box between
+ * eight nodes, is active when all corners are valid and their signs are mixed.  gsr_mesh_vertex_mask writes active_out
+ * [cells] bytes, the input of gsr_compact_offsets;  gsr_mesh_vertex_emit writes cell_vertex_out [cells] int32 (the
+ * cell's vertex index, ascending with the cell index, or -1) whatever the capacity, and row r of vertices_out
+ * [capacity, 3] float and colors_out [capacity, 3] uint8 for vertex r < capacity: the mean of the cell's edge
+ * crossings and the rounded mean colour of its corners.  gsr_mesh_face_mask writes keep_out [3 nodes] bytes: lattice
+ * edge e = 3 node + axis is kept when its upper node is in the grid, both ends are valid and differ in sign and the
+ * four cells around it are in range and active (cell_vertex >= 0);  gsr_mesh_face_emit writes rows 2 r and 2 r + 1 of
+ * faces_out [capacity, 3] int32 for the r-th kept edge, each row only where it is below capacity.  block_offsets: what
+ * gsr_compact_offsets made of the mask before it.
+ *   Checked in this order: a negative nx, ny, nz or capacity GSR_ERR_INVALID_ARGUMENT; a side or the node count above
+ *   2^29 GSR_ERR_UNSUPPORTED; min_weight below 1, (vertex emit) a NULL or non-finite grid_host or a voxel not above 0
+ *   GSR_ERR_INVALID_ARGUMENT; no cell, or (face emit) capacity == 0, GSR_OK and nothing is written; a NULL device
+ *   pointer GSR_ERR_INVALID_ARGUMENT, except vertices_out and colors_out where capacity == 0. */
+typedef struct GsrTsdfSource {
+  const float* depth;    /* [H, W] */
+  const float* image;    /* [H, W, 3], or NULL */
+  int32_t H, W;
+} GsrTsdfSource;
+int gsr_tsdf_integrate(int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid_host,
+                       const GsrTsdfSource* sources_host, const double* source_params_host, int32_t S,
+                       const double* tsdf_host, void* stream);
+int gsr_mesh_vertex_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                         uint8_t* active_out, void* stream);
+int gsr_mesh_vertex_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid_host,
+                         int32_t min_weight, const uint32_t* block_offsets, int64_t capacity, int32_t* cell_vertex_out,
+                         float* vertices_out, uint8_t* colors_out, void* stream);
+int gsr_mesh_face_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                       const int32_t* cell_vertex, uint8_t* keep_out, void* stream);
+int gsr_mesh_face_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                       const int32_t* cell_vertex, const uint32_t* block_offsets, int64_t capacity, int32_t* faces_out,
+                       void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -36,6 +36,7 @@ from .image import resize_area
 from .undistort import LensCamera, Undistortion, optimal_pinhole, remap, undistort_map
 from .fusion import (FusionConfig, depth_consistency, fuse_depth_maps, fuse_scene, select_sources,
                      voxel_downsample)
+from .mesh import TriangleMesh, TsdfConfig, TsdfVolume, mesh_depth_maps, mesh_scene
 from .colmap_io import read_model, write_model
 from .colmap import COLMAPDataset, export_colmap
 from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
@@ -74,4 +75,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "resize_area", "LensCamera", "Undistortion", "optimal_pinhole", "undistort_map", "remap", "read_model",
            "write_model", "COLMAPDataset", "export_colmap", "weighted_draws", "relocate_weights", "relocate_rescale",
            "relocate_rows", "relocate_points", "grow_points", "growth_target", "FusionConfig", "depth_consistency",
-           "select_sources", "fuse_depth_maps", "voxel_downsample", "fuse_scene"]
+           "select_sources", "fuse_depth_maps", "voxel_downsample", "fuse_scene", "TsdfConfig", "TsdfVolume", "TriangleMesh",
+           "mesh_depth_maps", "mesh_scene"]

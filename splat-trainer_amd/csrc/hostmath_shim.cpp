@@ -26,6 +26,7 @@
 #include "gsr_undistort.h"
 #include "gsr_relocate.h"
 #include "gsr_fusion.h"
+#include "gsr_mesh.h"
 
 extern "C" {
 
@@ -995,6 +996,117 @@ int hm_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, c
     b = e;
   }
   K_out[0] = K;
+  return GSR_OK;
+}
+
+// ---- TSDF meshing (gsr_mesh.h) ----
+int hm_tsdf_integrate(int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid, const void* sources_,
+                      const double* source_params, int32_t S, const double* tsdf) {
+  const GsrTsdfSource* sources = reinterpret_cast<const GsrTsdfSource*>(sources_);
+  int launch = 0;
+  const int rc = gsr_tsdf_integrate_args(state, nx, ny, nz, grid, sources, source_params, S, tsdf, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrMeshGrid g = {{nx, ny, nz}};
+  const GsrTsdfParams p = gsr_tsdf_params_make(grid, tsdf);
+  GsrTsdfSourceSet set = {};
+  gsr_tsdf_source_set_make(sources, source_params, S, &set);
+  const int64_t nodes = g.nodes();
+  for (int64_t node = 0; node < nodes; ++node) {
+    int32_t c[3];
+    g.node_coords((uint32_t)node, c);
+    const double X = gsr_tsdf_position(p.origin[0], p.voxel, c[0]), Y = gsr_tsdf_position(p.origin[1], p.voxel, c[1]),
+                 Z = gsr_tsdf_position(p.origin[2], p.voxel, c[2]);
+    GsrTsdfDelta d = {};
+    for (int s = 0; s < S; ++s) gsr_tsdf_observe(set, s, p, X, Y, Z, &d);
+    state[node] += d.sum_d;
+    state[nodes + node] += d.n;
+    state[2 * nodes + node] += d.nc;
+    for (int k = 0; k < 3; ++k) state[(3 + k) * nodes + node] += d.c[k];
+  }
+  return GSR_OK;
+}
+
+int hm_mesh_vertex_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight, uint8_t* active_out) {
+  int launch = 0;
+  const int rc = gsr_mesh_vertex_mask_args(state, nx, ny, nz, min_weight, active_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrMeshGrid g = {{nx, ny, nz}};
+  for (int64_t cell_id = 0; cell_id < g.cells(); ++cell_id) {
+    int32_t c[3];
+    GsrMeshCell cell;
+    g.cell_coords((uint32_t)cell_id, c);
+    gsr_mesh_load_cell(state, g, c, &cell);
+    active_out[cell_id] = gsr_mesh_active(cell, min_weight) ? 1 : 0;
+  }
+  return GSR_OK;
+}
+
+int hm_mesh_vertex_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid, int32_t min_weight,
+                        int64_t capacity, int32_t* cell_vertex_out, float* vertices_out, uint8_t* colors_out) {
+  int launch = 0;
+  const int rc = gsr_mesh_vertex_emit_args(state, nx, ny, nz, grid, min_weight, nullptr, false, capacity, cell_vertex_out,
+                                           vertices_out, colors_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrMeshGrid g = {{nx, ny, nz}};
+  const GsrTsdfParams p = gsr_tsdf_params_make(grid, nullptr);
+  const int64_t nodes = g.nodes();
+  int64_t row = 0;
+  for (int64_t cell_id = 0; cell_id < g.cells(); ++cell_id) {
+    int32_t c[3];
+    GsrMeshCell cell;
+    g.cell_coords((uint32_t)cell_id, c);
+    gsr_mesh_load_cell(state, g, c, &cell);
+    if (!gsr_mesh_active(cell, min_weight)) {
+      cell_vertex_out[cell_id] = -1;
+      continue;
+    }
+    cell_vertex_out[cell_id] = (int32_t)row;
+    if (row < capacity) {
+      gsr_mesh_vertex(cell, c, p, vertices_out + 3 * row);
+      int64_t nc = 0, C[3] = {0, 0, 0};
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t node = gsr_mesh_corner_node(g, c, k);
+        nc += state[2 * nodes + node];
+        for (int ch = 0; ch < 3; ++ch) C[ch] += state[(3 + ch) * nodes + node];
+      }
+      for (int ch = 0; ch < 3; ++ch) colors_out[3 * row + ch] = gsr_mesh_colour(C[ch], nc);
+    }
+    ++row;
+  }
+  return GSR_OK;
+}
+
+int hm_mesh_face_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                      const int32_t* cell_vertex, uint8_t* keep_out) {
+  int launch = 0;
+  const int rc = gsr_mesh_face_mask_args(state, nx, ny, nz, min_weight, cell_vertex, keep_out, &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrMeshGrid g = {{nx, ny, nz}};
+  for (int64_t e = 0; e < 3 * g.nodes(); ++e) {
+    bool lower_negative;
+    int32_t q[4];
+    keep_out[e] = gsr_mesh_edge_kept(state, cell_vertex, g, (uint32_t)e, min_weight, &lower_negative, q) ? 1 : 0;
+  }
+  return GSR_OK;
+}
+
+int hm_mesh_face_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                      const int32_t* cell_vertex, int64_t capacity, int32_t* faces_out) {
+  int launch = 0;
+  const int rc = gsr_mesh_face_emit_args(state, nx, ny, nz, min_weight, cell_vertex, nullptr, false, capacity, faces_out,
+                                         &launch);
+  if (rc < 0 || !launch) return rc;
+  const GsrMeshGrid g = {{nx, ny, nz}};
+  int64_t row = 0;
+  for (int64_t e = 0; e < 3 * g.nodes(); ++e) {
+    bool lower_negative;
+    int32_t q[4], t[6];
+    if (!gsr_mesh_edge_kept(state, cell_vertex, g, (uint32_t)e, min_weight, &lower_negative, q)) continue;
+    gsr_mesh_quad(q, lower_negative, t);
+    for (int k = 0; k < 2; ++k, ++row)
+      if (row < capacity)
+        for (int j = 0; j < 3; ++j) faces_out[3 * row + j] = t[3 * k + j];
+  }
   return GSR_OK;
 }
 

@@ -191,6 +191,20 @@ int hm_voxel_downsample(const float* points, const uint8_t* colors, int64_t N, c
 /* keys [n] of points [n, 3] as uint64 */
 void hm_voxel_keys(const float* points, int64_t n, const double* grid, uint64_t* keys);
 
+/* ---- TSDF meshing (gsr_mesh.h): the device's arithmetic in plain loops, with its argument checks and codes ---- */
+/* gsr_tsdf_integrate on host memory: sources [S] GsrTsdfSource of include/gsplat_hip.h (24 bytes each: depth, image, H, W) */
+int hm_tsdf_integrate(int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid_host, const void* sources_host,
+                      const double* source_params_host, int32_t S, const double* tsdf_host);
+int hm_mesh_vertex_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight, uint8_t* active_out);
+/* the emit twins rank in a plain walk in index order, so they take no block offsets */
+int hm_mesh_vertex_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, const double* grid_host,
+                        int32_t min_weight, int64_t capacity, int32_t* cell_vertex_out, float* vertices_out,
+                        uint8_t* colors_out);
+int hm_mesh_face_mask(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                      const int32_t* cell_vertex, uint8_t* keep_out);
+int hm_mesh_face_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz, int32_t min_weight,
+                      const int32_t* cell_vertex, int64_t capacity, int32_t* faces_out);
+
 #ifdef __cplusplus
 }
 #endif

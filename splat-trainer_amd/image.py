@@ -22,9 +22,10 @@ HOST_LIB_PATH = os.path.join(_lib.PKG_DIR, "libgsr_hostmath.so")
 HOST_HEADER_PATH = os.path.join(_lib.PKG_DIR, "csrc", "hostmath_shim.h")
 MAX_SIDE = 32768
 # what the package itself calls of the host library: the area resize, the undistortion (undistort.py) and the depth
-# fusion (fusion.py)
+# fusion (fusion.py) and the TSDF meshing (mesh.py)
 HOST_FUNCTIONS = ("hm_image_resize_area_u8", "hm_undistort_map", "hm_undistort_points", "hm_image_remap_u8",
-                  "hm_fuse_check", "hm_fuse_mask", "hm_fuse_emit", "hm_voxel_downsample")
+                  "hm_fuse_check", "hm_fuse_mask", "hm_fuse_emit", "hm_voxel_downsample", "hm_tsdf_integrate",
+                  "hm_mesh_vertex_mask", "hm_mesh_vertex_emit", "hm_mesh_face_mask", "hm_mesh_face_emit")
 _host_lib = None
 _lock = threading.Lock()
 

@@ -137,6 +137,83 @@ def read_ply(filename: Union[str, Path]) -> np.ndarray:
   raise ValueError(f"unsupported PLY format {fmt}")
 
 
+_MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_FACE = np.dtype([("count", "u1"), ("vertex_indices", "<i4", (3,))])
+
+
+def write_mesh(filename: Union[str, Path], vertices: np.ndarray, colors: np.ndarray, faces: np.ndarray) -> None:
+  """A triangle mesh as a binary little-endian PLY: ``vertex`` with float x y z and uchar red green blue, ``face`` with
+  ``list uchar int vertex_indices`` -- what mesh viewers and CAD tools read.  vertices (V, 3) float32, colors (V, 3)
+  uint8, faces (F, 3) int32 with every index in [0, V)."""
+  vertices, colors, faces = np.asarray(vertices), np.asarray(colors), np.asarray(faces)
+  if (vertices.ndim != 2 or vertices.shape[1] != 3 or vertices.dtype != np.float32 or colors.shape != vertices.shape or
+      colors.dtype != np.uint8 or faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype != np.int32):
+    raise ValueError("a mesh needs float32 vertices (V, 3), uint8 colors (V, 3) and int32 faces (F, 3), got "
+                     f"{vertices.shape} {vertices.dtype}, {colors.shape} {colors.dtype}, {faces.shape} {faces.dtype}")
+  if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
+    raise ValueError(f"a face names a vertex outside [0, {vertices.shape[0]})")
+  vertex = np.zeros(vertices.shape[0], _MESH_VERTEX)
+  for k, (axis, channel) in enumerate(zip(("x", "y", "z"), ("red", "green", "blue"))):
+    vertex[axis], vertex[channel] = vertices[:, k], colors[:, k]
+  face = np.zeros(faces.shape[0], _MESH_FACE)
+  face["count"], face["vertex_indices"] = 3, faces
+  header = ["ply", "format binary_little_endian 1.0", f"element vertex {vertex.shape[0]}"]
+  header += [f"property float {n}" for n in ("x", "y", "z")] + [f"property uchar {n}" for n in ("red", "green", "blue")]
+  header += [f"element face {face.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+  with open(str(filename), "wb") as f:
+    f.write(("\n".join(header) + "\n").encode("ascii"))
+    f.write(vertex.tobytes())
+    f.write(face.tobytes())
+
+
+def read_mesh(filename: Union[str, Path]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+  """(vertices (V, 3) float32, colors (V, 3) uint8, faces (F, 3) int32) of a binary little-endian PLY whose ``vertex``
+  element comes first with scalar properties (x y z, and red green blue; white without them) and whose ``face`` element
+  follows with one list property of triangles."""
+  with open(str(filename), "rb") as f:
+    data = f.read()
+  if not data.startswith(b"ply") or b"end_header\n" not in data:
+    raise ValueError("not a PLY file")
+  end = data.index(b"end_header\n") + len(b"end_header\n")
+  elements, fmt = [], None                      # [name, count, [property tokens]]
+  for ln in data[:end].decode("ascii").split("\n")[1:]:
+    tok = ln.split()
+    if not tok:
+      continue
+    if tok[0] == "format":
+      fmt = tok[1]
+    elif tok[0] == "element":
+      elements.append([tok[1], int(tok[2]), []])
+    elif tok[0] == "property" and elements:
+      elements[-1][2].append(tok[1:])
+  if fmt != "binary_little_endian":
+    raise ValueError(f"unsupported PLY format {fmt}: a mesh is read from binary_little_endian only")
+  if [e[0] for e in elements[:2]] != ["vertex", "face"]:
+    raise ValueError(f"a mesh needs the elements vertex and face, in that order, got {[e[0] for e in elements]}")
+  (_, V, vprops), (_, F, fprops) = elements[:2]
+  if any(p[0] == "list" for p in vprops):
+    raise ValueError("list properties are not supported in the vertex element")
+  if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][3] not in ("vertex_indices", "vertex_index"):
+    raise ValueError(f"the face element needs one list property vertex_indices, got {fprops}")
+  vdtype = np.dtype([(p[1], _PLY_TYPES[p[0]]) for p in vprops])
+  fdtype = np.dtype([("count", _PLY_TYPES[fprops[0][1]]), ("vertex_indices", _PLY_TYPES[fprops[0][2]], (3,))])
+  if len(data) < end + V * vdtype.itemsize + F * fdtype.itemsize:
+    raise ValueError("the PLY file is shorter than its header says")
+  vertex = np.frombuffer(data, dtype=vdtype, count=V, offset=end)
+  face = np.frombuffer(data, dtype=fdtype, count=F, offset=end + V * vdtype.itemsize)
+  if F and (face["count"] != 3).any():
+    raise ValueError("only triangles are supported")
+  missing = [k for k in ("x", "y", "z") if k not in vdtype.names]
+  if missing:
+    raise KeyError(f"PLY vertex element lacks {missing}")
+  vertices = np.stack([vertex[k].astype(np.float32) for k in ("x", "y", "z")], 1).reshape(V, 3)
+  if all(k in vdtype.names for k in ("red", "green", "blue")):
+    colors = np.stack([vertex[k].astype(np.uint8) for k in ("red", "green", "blue")], 1).reshape(V, 3)
+  else:
+    colors = np.full((V, 3), 255, np.uint8)
+  return vertices, colors, face["vertex_indices"].astype(np.int32).reshape(F, 3)
+
+
 def write_gaussians(filename: Union[str, Path], gaussians: Gaussians3D, with_sh: bool = True) -> None:
   """io.py:119-123."""
   write_ply(filename, to_vertex_array(gaussians, with_sh=with_sh))

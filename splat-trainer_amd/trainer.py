@@ -43,6 +43,7 @@ from .data_types import CameraParams, Gaussians3D, Rendering
 from .dataset import Dataset, ImageView, PointCloud
 from .evaluation import Evaluation
 from .fusion import FusionConfig, fuse_scene
+from .mesh import TriangleMesh, TsdfConfig, mesh_scene
 from .histogram import tensor_histogram
 from .logger import Logger, LoggerWithState
 from .loss import reference_loss
@@ -344,6 +345,24 @@ class Trainer:
     cloud = self.fused_cloud(config, which)
     cloud.save_ply(path)
     return cloud
+
+  def mesh(self, config: Optional[TsdfConfig] = None, which: str = "train") -> TriangleMesh:
+    """The triangle mesh of the TSDF volume integrated from the median depth maps of the ``which`` = "train" or "val"
+    views (mesh.mesh_scene), in the original coordinates."""
+    if which not in ("train", "val"):
+      raise ValueError(f"which must be 'train' or 'val', got {which!r}")
+    views = self.dataset.train(shuffle=False) if which == "train" else self.dataset.val()
+    indexes = [int(v.image_idx) for v in views]
+    if not indexes:
+      raise ValueError(f"the dataset has no {which} views")
+    render = lambda camera, idx: self.render(camera, idx, render_median_depth=True)      # noqa: E731
+    mesh = mesh_scene(render, [self.camera_params(i) for i in indexes], config or TsdfConfig(), indexes)
+    return mesh.transformed(self.unnormalize)
+
+  def write_mesh(self, path, config: Optional[TsdfConfig] = None, which: str = "train") -> TriangleMesh:
+    mesh = self.mesh(config, which)
+    mesh.save_ply(path)
+    return mesh
 
   def load_cloud(self) -> Gaussians3D:
     paths = self.paths()
