@@ -1124,6 +1124,47 @@ int gsr_mesh_face_emit(const int32_t* state, int32_t nx, int32_t ny, int32_t nz,
                        const int32_t* cell_vertex, const uint32_t* block_offsets, int64_t capacity, int32_t* faces_out,
                        void* stream);
 
+/* ---- normal consistency (no reference counterpart; 2DGS section 4.2): splat normals, depth normals, the loss --------
+ * The arithmetic and the full statement of the contract are csrc/gsr_normals.h: fp32, pixel centres at +0.5, projection
+ * [4] = fx fy cx cy and T_camera_world [4, 4] row-major on the device.  No atomics, one writer per element; the loss is a
+ * fixed-order sum, so two runs give the same bits.  A side is at most 32768.
+ *
+ * gsr_splat_normals_forward.  Per visible row i = indexes[m] (unique, inside [0, N); a row outside gets the normal 0) the
+ * column of the rotation matrix that belongs to the smallest log_scaling (the lowest index on ties), in camera space,
+ * turned towards the camera.  depth NULL: out [M, 3].  depth [M]: out [M, 5] = n, depth, 1, the feature rows of the
+ * geometry image.  gsr_splat_normals_backward recomputes the forward and writes row i of d_rotation [N, 4] from
+ * d_out [M, stride] (stride 3 or 5); the other rows are untouched: pass zeros.  d_depth [M] (stride 5 only, may be NULL)
+ * gets column 3 of d_out.  Position, log_scaling and the camera receive no gradient: the axis and the flip are constants.
+ *   Checked in this order: M or N outside [0, GSR_NEIGHBOURS_MAX_N], a stride other than 3 and 5, d_depth with stride 3
+ *   GSR_ERR_INVALID_ARGUMENT; M == 0 GSR_OK; a NULL pointer other than depth / d_depth, a rotation or d_rotation that is
+ *   not 16-byte aligned GSR_ERR_INVALID_ARGUMENT.
+ *
+ * gsr_depth_normals.  depth [H, W] -> normals_out [H, W, 3]: the unit normal of the back-projected central differences,
+ * (0, 0, -1) for a fronto-parallel surface; exactly 0 on the border and wherever the pixel's depth or one of its four
+ * taps' is not finite and above 0.
+ *
+ * gsr_normal_loss_forward.  geometry [H, W, 5] = N^x N^y N^z D A (the composite of the rows above).  d = D / A where
+ * A >= alpha_min, else not valid; normals_out [H, W, 3] = the depth normals of d; loss_out [1] = sum over the valid pixels
+ * of A - N^ . n_d, divided by H W.  partials: gsr_normal_loss_blocks(H, W) floats of workspace (0 for sides outside
+ * [1, 32768]).  gsr_normal_loss_backward recomputes the forward and writes d_geometry [H, W, 5], every element, from the
+ * device scalar d_loss [1]: D and A also receive what passes through d into the normals of the four neighbours, gathered
+ * in the order left, right, up, down.  The projection receives no gradient.
+ *   Checked in this order: a negative side or a NaN alpha_min GSR_ERR_INVALID_ARGUMENT; a side above 32768
+ *   GSR_ERR_UNSUPPORTED; H == 0 or W == 0 GSR_OK and nothing is written; a NULL pointer GSR_ERR_INVALID_ARGUMENT. */
+int gsr_splat_normals_forward(const float* rotation_xyzw, const float* log_scaling, const float* position, int64_t N,
+                              const int64_t* indexes, int64_t M, const float* T_camera_world, const float* depth,
+                              float* out, void* stream);
+int gsr_splat_normals_backward(const float* rotation_xyzw, const float* log_scaling, const float* position, int64_t N,
+                               const int64_t* indexes, int64_t M, const float* T_camera_world, const float* d_out,
+                               int32_t stride, float* d_rotation, float* d_depth, void* stream);
+int gsr_depth_normals(const float* depth, int32_t H, int32_t W, const float* projection, float* normals_out,
+                      void* stream);
+int64_t gsr_normal_loss_blocks(int32_t H, int32_t W);
+int gsr_normal_loss_forward(const float* geometry, int32_t H, int32_t W, const float* projection, float alpha_min,
+                            float* normals_out, float* partials, float* loss_out, void* stream);
+int gsr_normal_loss_backward(const float* geometry, int32_t H, int32_t W, const float* projection, float alpha_min,
+                             const float* d_loss, float* d_geometry, void* stream);
+
 /* ---- data-parallel exchange helpers (no reference counterpart: the reference is single-GPU) ------------- */
 /* One fixed-size block per camera, GSR_DP_BLOCK_FLOATS(N) = 6N + 3 floats: [0,3N) colour-gradient rows (0 where the
  * camera saw nothing), [3N,3N+3) camera position, [3N+3,4N+3) split_score and [4N+3,5N+3) prune_cost (NaN where

@@ -37,6 +37,7 @@ from .undistort import LensCamera, Undistortion, optimal_pinhole, remap, undisto
 from .fusion import (FusionConfig, depth_consistency, fuse_depth_maps, fuse_scene, select_sources,
                      voxel_downsample)
 from .mesh import TriangleMesh, TsdfConfig, TsdfVolume, mesh_depth_maps, mesh_scene
+from .normals import depth_normals, geometry_features, normal_consistency_loss, splat_normals
 from .colmap_io import read_model, write_model
 from .colmap import COLMAPDataset, export_colmap
 from .logger import (CompositeLogger, HistoryLogger, Logger, LoggerWithState, NullLogger, StateLogger, StateTree,
@@ -76,4 +77,5 @@ __all__ = ["CameraParams", "Gaussians3D", "RasterConfig", "RenderedPoints", "Ren
            "write_model", "COLMAPDataset", "export_colmap", "weighted_draws", "relocate_weights", "relocate_rescale",
            "relocate_rows", "relocate_points", "grow_points", "growth_target", "FusionConfig", "depth_consistency",
            "select_sources", "fuse_depth_maps", "voxel_downsample", "fuse_scene", "TsdfConfig", "TsdfVolume", "TriangleMesh",
-           "mesh_depth_maps", "mesh_scene"]
+           "mesh_depth_maps", "mesh_scene", "splat_normals", "geometry_features", "depth_normals",
+           "normal_consistency_loss"]

@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libgsplat_hip.so")
 HOSTMATH_PATH = os.path.join(PKG_DIR, "libgsr_hostmath.so")
 HIP_SOURCES = ["prims.hip", "geometry.hip", "binning.hip", "composite.hip", "frame.hip", "ssim.hip", "optim.hip", "densify.hip",
                "bilagrid.hip", "neighbours.hip", "color_model.hip", "reg.hip", "visibility.hip", "eval.hip", "filter3d.hip", "sh_fit.hip", "controller.hip",
-               "camera_table.hip", "histogram.hip", "image.hip", "undistort.hip", "relocate.hip", "fusion.hip", "mesh.hip"]
+               "camera_table.hip", "histogram.hip", "image.hip", "undistort.hip", "relocate.hip", "fusion.hip", "mesh.hip", "normals.hip"]
 PUBLIC_HEADER = os.path.join(PKG_DIR, "..", "include", "gsplat_hip.h")
 
 

@@ -275,6 +275,7 @@ class Rendering:
   median_depth_image: Optional[torch.Tensor] = None  # (H, W) when render_median_depth=True
   final_transmittance: Optional[torch.Tensor] = None  # (H, W) T after the last composited splat
   num_overlaps: int = 0                              # O = sum of tile overlaps (reported per frame)
+  geometry_image: Optional[torch.Tensor] = None      # (H, W, 5) N^x N^y N^z D A when render_geometry=True (normals.py)
 
   @property
   def image_size(self) -> Tuple[int, int]:
@@ -291,4 +292,5 @@ class Rendering:
   def detach(self) -> "Rendering":
     return _dc_replace(self, image=self.image.detach(), points=self.points.detach(),
                        median_depth_image=_detach(self.median_depth_image),
-                       final_transmittance=_detach(self.final_transmittance))
+                       final_transmittance=_detach(self.final_transmittance),
+                       geometry_image=_detach(self.geometry_image))

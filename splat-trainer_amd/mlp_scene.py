@@ -28,6 +28,7 @@ from .filter3d import sampling_rate, smooth_gaussians
 from .data_types import CameraParams, Gaussians3D, RasterConfig, Rendering, pop_raster_config
 from .harness import split_gaussians_uniform
 from .histogram import tensor_histogram
+from .normals import geometry_features
 from .optim import ParameterClass, VisibilityAwareLaProp, VisibilityOptimizer, point_basis_rows
 from .renderer import project_to_image, render_projected
 from .sh import evaluate_sh_at
@@ -322,18 +323,29 @@ class MLPScene:
     return smooth_gaussians(self.gaussians, self.points.tensors["filter_rate"], self.config.filter_3d)
 
   def render(self, camera_params: CameraParams, image_idx: Optional[int] = None, specular_weight: float = 1.0,
-             **options) -> Rendering:
+             render_geometry: bool = False, **options) -> Rendering:
     """mlp_scene.py:410-427: project, colour the culled points, rasterise ``colors.total(specular_weight)``; the
     rendering's ``points.attributes`` are the ``Colors`` and its image has gone through ``post_activation``.  With
-    ``config.filter_3d`` > 0 the smoothed Gaussians are projected (one autograd node in front of the projection)."""
+    ``config.filter_3d`` > 0 the smoothed Gaussians are projected (one autograd node in front of the projection).
+
+    ``render_geometry`` rasterises the rows of ``geometry_features`` behind the colour, 8 channels on the wide path, and
+    returns them as ``geometry_image`` (H, W, 5), with their graph: the input of ``normal_consistency_loss``."""
     config = pop_raster_config(options)
     prefetch = {}
-    gaussians2d, depth, indexes = project_to_image(self._filtered_gaussians(), camera_params, config, prefetch=prefetch)
+    gaussians = self._filtered_gaussians()
+    gaussians2d, depth, indexes = project_to_image(gaussians, camera_params, config, prefetch=prefetch)
     colors = self.eval_colors(indexes, camera_params, image_idx)
-    rendering = render_projected(indexes, gaussians2d, colors.total(specular_weight), depth, camera_params, config,
+    features = colors.total(specular_weight)
+    if render_geometry:
+      if features.shape[1] != 3:
+        raise ValueError(f"render_geometry needs a 3-channel colour, got {features.shape[1]} channels")
+      features = torch.cat([features, geometry_features(gaussians, indexes, depth, camera_params)], 1)
+    rendering = render_projected(indexes, gaussians2d, features, depth, camera_params, config,
                                  _depth_order=prefetch.get("depth_order"), **options)
+    image = rendering.image[..., :3] if render_geometry else rendering.image
     return replace(rendering, points=rendering.points.replace(attributes=colors),
-                   image=self.color_model.post_activation(rendering.image))
+                   image=self.color_model.post_activation(image),
+                   geometry_image=rendering.image[..., 3:8] if render_geometry else None)
 
   @torch.no_grad()
   def query_visibility(self, camera_params: CameraParams) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -47,6 +47,7 @@ from .mesh import TriangleMesh, TsdfConfig, mesh_scene
 from .histogram import tensor_histogram
 from .logger import Logger, LoggerWithState
 from .loss import reference_loss
+from .normals import normal_consistency_loss
 from .visibility import PointClusters, ViewClustering
 
 try:
@@ -104,6 +105,10 @@ class TrainConfig:
   mse_weight: float = 0.0
   l1_weight: float = 0.0
   ssim_levels: int = 4
+
+  normal_weight: float = 0.0                 # depth-normal consistency (normals.py); 0 = off: the step is unchanged
+  normal_from: float = 0.3                   # fraction of the training progress from which the term is added
+  normal_alpha_min: float = 0.5              # pixels below this accumulated alpha have no depth for the term
 
   vis_clusters: int = 1024
 
@@ -379,6 +384,11 @@ class Trainer:
   def is_logging_step(self) -> bool:
     return self.step % self.config.log_interval == 0
 
+  @property
+  def normal_term_active(self) -> bool:
+    """Whether this step renders the geometry image and adds the depth-normal consistency term."""
+    return self.config.normal_weight > 0 and self.progress.t >= self.config.normal_from
+
   def camera_params(self, cam_idx: int) -> CameraParams:
     """The camera of image ``cam_idx`` on the device.  The table is not trained by this loop, so each is read once."""
     cam_idx = int(cam_idx)
@@ -498,19 +508,30 @@ class Trainer:
     return {k: float(eval_schedule(v, progress)) for k, v in self.scene.config.reg_weight.items()}
 
   def compute_losses(self, rendering: Rendering, image: torch.Tensor) -> torch.Tensor:
-    """One fused loss call plus the scene's regulariser.  The logged scalars come from the metrics tensor
-    [loss, l1, mse, ssim_0, ...] and are read on logging steps only."""
+    """One fused loss call plus the scene's regulariser and, on a rendering with a geometry image while
+    ``normal_term_active``, ``normal_weight`` times the depth-normal consistency loss.  The logged scalars come from the
+    metrics tensor [loss, l1, mse, ssim_0, ...] and are read on logging steps only, in one read."""
     config = self.config
     loss, metrics = reference_loss(rendering.image, image, l1_weight=config.l1_weight, mse_weight=config.mse_weight,
                                    ssim_weight=config.ssim_weight, ssim_levels=config.ssim_levels, return_metrics=True)
     reg_loss = self.scene.reg_loss(rendering, self.reg_weights())
     total = loss + reg_loss
+    normal_loss = None
+    if rendering.geometry_image is not None and self.normal_term_active:
+      normal_loss = config.normal_weight * normal_consistency_loss(rendering.geometry_image, rendering.camera.projection,
+                                                                   alpha_min=config.normal_alpha_min)
+      total = total + normal_loss
     if self.is_logging_step:
-      values = torch.cat([metrics.detach().reshape(-1), reg_loss.detach().reshape(1)]).tolist()     # one read
+      extra = [reg_loss.detach().reshape(1)] + ([] if normal_loss is None else [normal_loss.detach().reshape(1)])
+      values = torch.cat([metrics.detach().reshape(-1)] + extra).tolist()                            # one read
+      terms = {}
+      if normal_loss is not None:
+        terms["normal"] = values.pop()
       image_loss, l1, mse, ssim, reg = values[0], values[1], values[2], values[3], values[-1]
       ssim_loss = sum(1.0 - s for s in values[3:-1]) / config.ssim_levels
       self.logger.log_values("train/loss", dict(l1=l1 * config.l1_weight, mse=mse * config.mse_weight,
-                                                ssim=ssim_loss * config.ssim_weight, reg=reg, total=image_loss + reg))
+                                                ssim=ssim_loss * config.ssim_weight, reg=reg, **terms,
+                                                total=image_loss + reg + terms.get("normal", 0.0)))
       psnr = 10 * math.log10(1 / mse) if mse > 0 else math.inf
       self.logger.log_values("train/metrics", dict(l1=l1, mse=mse, ssim=ssim, psnr=psnr))
     return total
@@ -519,7 +540,8 @@ class Trainer:
     for image_view in batch:
       camera_params = self.camera_params(image_view.image_idx)
       with torch.enable_grad():
-        rendering = self.render(camera_params, image_view.image_idx)
+        geometry = dict(render_geometry=True) if self.normal_term_active else {}
+        rendering = self.render(camera_params, image_view.image_idx, **geometry)
         if rendering.points.idx.shape[0] == 0:
           raise TrainingException(f"No visible points: {image_view.filename} - check training parameters or dataset "
                                   "camera poses")
